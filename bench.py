@@ -2,18 +2,33 @@
 """Benchmark of the MI355X CMSIS-DSP backend — the BASELINE.json headline.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload WL] [--batch B]
-                  [--scaling weak|strong] [--global-batch G]
+                  [--scaling weak|strong] [--global-batch G] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it generates the seeded
+inputs, settles the clock, runs W untimed and K timed steps, writes the outputs of the last
+timed step if --dump-outputs is given, and prints the line (value, ms_per_step and the
+roofline of the same K launches).  Everything else is behind --full: the parity replay
+against the CPU checker, config3, cpu_baseline and the --scatter leg.
+
+--dump-outputs DIR: after the timed steps, every array a caller of the timed path would
+hold after the last step is written to DIR/<name>.npy (DIR/<name>_rank<r>.npy with more than
+one rank) as float32, or float64 for q31 words; arrays too large for the 64 MB total are
+cut to a fixed, seeded sample of their rows.  The inputs depend only on the arguments, and
+the buffers a launch updates in place are put back to their seeded state after the clock
+settle (whose number of launches depends on the clock), so two runs with the same arguments
+write the outputs of the same W + K launches on the same data.
 
 Default line (BASELINE.json metric "Gsamples/sec batched arm_cfft_f32 N=1024 (+ q31
 bit-exact) at 1/2/4/8 GPU"):
   * value: configs[1] — batched arm_cfft_f32, fftLen 1024, 2^20 transforms per GPU (8 GiB
     in HBM, in place), bitReverseFlag 1; a step is one pass over the batch, alternating
     forward / inverse; whole-job complex samples per second; weak scaling.
-  * config3: configs[3] — arm_cfft_q31 AND arm_cfft_q15, fftLen 4096, ONE global batch of
+  * --full, config3: configs[3] — arm_cfft_q31 AND arm_cfft_q15, fftLen 4096, ONE global batch of
     2^20 transforms split over the ranks in contiguous slices (strong scaling), each
     bit-exact against the reference scalar C on replayed rows of every rank.
   * roofline of the dominant kernel (HIP-event average launch duration on the launch
-    stream), cpu_baseline (the reference scalar C on this host: one core and all cores).
+    stream); --full: cpu_baseline (the reference scalar C on this host: one core and all
+    cores).
 
 --gpus N > 1 without a torchrun environment: this process starts
 `python -m torch.distributed.run --nproc-per-node N ... bench.py` as a CHILD before any
@@ -38,6 +53,8 @@ METRIC = "Gsamples/sec batched arm_cfft_f32 N=1024 (+ q31 bit-exact) at 1/2/4/8 
 CONFIG3_GLOBAL_BATCH = 1 << 20   # BASELINE configs[3]: N=4096 batch=1M, sharded
 CPU_THREADS_MAX = 16             # the GPU box's CPU share per GPU
 SETTLE_MS = 40.0                 # device time of untimed launches before the W warmup steps
+DUMP_BYTES_MAX = 60_000_000      # --dump-outputs: array bytes of all ranks (the files stay under 64 MB)
+DUMP_SEED = 0x5EED               # --dump-outputs: the row sample of an array over its share
 
 WORKLOADS = {
     # name: (kind, fftLen / taps, default batch per GPU, algorithmic bytes per sample)
@@ -87,6 +104,12 @@ def parse_args(argv=None):
     ap.add_argument("--global-batch", type=int, default=CONFIG3_GLOBAL_BATCH)
     ap.add_argument("--fftlen", type=int, default=0,
                     help="cfft workloads: another fftLen (16..4096), batch scaled to the same bytes")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the parity replay against the CPU checker, "
+                         "config3, cpu_baseline and --scatter")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step produced to DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-config3", "--no-companion", dest="no_config3", action="store_true",
                     help="skip the configs[3] q31 + q15 N=4096 strong-scaling measurement")
@@ -284,17 +307,21 @@ def main_rank(args):
 
     settle = {"launches": 0}
 
-    def time_launches(launch, steps, warmup):
+    def time_launches(launch, steps, warmup, state=()):
         """Clock settle, W untimed, then K timed launches between barriers; returns (wall s,
         avg kernel ms).  The settle phase repeats the launch until >= SETTLE_MS of device
         time has passed (at most 64 launches): the GPU's power management dips the clock for
         the first ~10-30 ms of a sustained load (kernel traces: the first launch is fast, the
         next few 5-30 % slow, then steady), which W short warmup steps do not cover.  The
-        number of settle launches is reported (settle_launches) and every launch, settle
-        included, is replayed by the parity check.  The HIP events are recorded on the stream
-        the library launches on (torch's current stream)."""
+        number of settle launches is reported (settle_launches) but depends on the clock, so
+        `state`, the tensors a launch updates in place, is copied before the settle phase and
+        put back after it (device copies: the GPU stays loaded), and the W + K launches that
+        follow are numbered from 0: what they compute depends on the arguments alone, and
+        they are the launches the --full parity check replays.  The HIP events are recorded
+        on the stream the library launches on (torch's current stream)."""
         stream = torch.cuda.current_stream()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        seeded = [t.clone() for t in state]
         s = 0
         e0.record(stream)
         while s < 64:
@@ -305,27 +332,47 @@ def main_rank(args):
             if e0.elapsed_time(e1) >= SETTLE_MS:
                 break
         settle["launches"] = s
+        for t, t_seeded in zip(state, seeded):
+            t.copy_(t_seeded)
+        del seeded
         for w in range(warmup):
-            launch(s + w)
-        s += warmup
+            launch(w)
         parallel.barrier(world)
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
         t0 = time.perf_counter()
         for k in range(steps):
             evs[k][0].record(stream)
-            launch(s + k)
+            launch(warmup + k)
             evs[k][1].record(stream)
         parallel.barrier(world)
         wall = time.perf_counter() - t0
         kern_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
-        settle["total"] = s + steps
+        settle["total"] = warmup + steps
         return wall, kern_ms
 
+    dumped = {}
+
+    def keep_outputs(**arrays):
+        """--dump-outputs: take what the last timed step left in `arrays` (2-D views, rows =
+        items) to the host as float32 (float64 for 32-bit words); an array over its share of
+        the 64 MB is cut to a sorted, seeded choice of its rows."""
+        if not args.dump_outputs:
+            return
+        share = DUMP_BYTES_MAX // (world.size * len(arrays))
+        for name, t in arrays.items():
+            wide = t.dtype == torch.int32
+            n_rows = max(1, min(t.shape[0], share // (t.shape[1] * (8 if wide else 4))))
+            if n_rows < t.shape[0]:
+                pick = np.sort(np.random.default_rng(DUMP_SEED).choice(t.shape[0], n_rows, replace=False))
+                t = t[torch.from_numpy(pick).to(t.device)]
+            dumped[name] = t.cpu().numpy().astype(np.float64 if wide else np.float32)
+
     # ---------------------------------------------------------------- workloads
-    def run_cfft(kind, n, batch, steps, warmup, strong_span=None):
+    def run_cfft(kind, n, batch, steps, warmup, strong_span=None, headline=True):
         """Weak: `batch` rank-local transforms.  Strong: strong_span = (start, count) of the
-        global batch.  Parity: the timed buffer's sampled rows replayed through the exact
-        flag sequence with the CPU checker, plus a fresh 64-transform launch, on every rank."""
+        global batch.  Parity (--full): the timed buffer's sampled rows replayed through the
+        exact flag sequence with the CPU checker, plus a fresh 64-transform launch, on every
+        rank.  headline: this is the line's own workload (its outputs are the ones dumped)."""
         S = dsp.const_instance(f"arm_cfft_sR_{kind}_len{n}")
         if strong_span is None:
             data = synth(kind, batch * 2 * n).view(batch, 2 * n)
@@ -333,12 +380,18 @@ def main_rank(args):
             data = synth_global(kind, n, *strong_span)
             batch = strong_span[1]
         rows = sorted({0, 1, batch // 2, batch - 1})
-        before = data[rows].cpu().numpy().copy()
+        before = data[rows].cpu().numpy().copy()     # also completes the generation before the settle phase
 
         def launch(s):
             dsp.cfft_batch(S, data, s & 1, 1)          # fwd, inv, fwd, ...
 
-        wall, kern_ms = time_launches(launch, steps, warmup)
+        wall, kern_ms = time_launches(launch, steps, warmup, state=[data])
+        if headline:
+            keep_outputs(data=data)
+        if not args.full:
+            del data
+            torch.cuda.empty_cache()
+            return wall, kern_ms, None
         flags = flag_sequence(settle["total"])
         host, hk = cpu_checker()
         want = before
@@ -390,7 +443,10 @@ def main_rank(args):
         def launch(s):
             dsp.fir_batch(S, src, dst, hist, kind=kind)
 
-        wall, kern_ms = time_launches(launch, steps, warmup)
+        wall, kern_ms = time_launches(launch, steps, warmup, state=[hist])
+        keep_outputs(dst=dst, state=hist)
+        if not args.full:
+            return wall, kern_ms, None
         host, hk = cpu_checker()
         h0 = torch.zeros((2, taps - 1), dtype=src.dtype, device="cuda")
         d0 = torch.empty((2, block), dtype=src.dtype, device="cuda")
@@ -425,7 +481,8 @@ def main_rank(args):
             dsp.mat_mult_batch(a, b, c)
 
         wall, kern_ms = time_launches(launch, steps, warmup)
-        return wall, kern_ms, mat_parity(a[0], b[0], c[0])
+        keep_outputs(c=c.view(-1, dim))
+        return wall, kern_ms, mat_parity(a[0], b[0], c[0]) if args.full else None
 
     def mat_parity(a, b, c):
         """Tolerance vs float64 (elementwise K 2^-24 (|A||B|)ij, and rms <= sqrt(K) 2^-24 -- the
@@ -480,7 +537,13 @@ def main_rank(args):
         def launch(s):
             dsp.rfft_fast_batch(S, p, out, 0, p_scratch=p_scratch)
 
-        wall, kern_ms = time_launches(launch, steps, warmup)
+        wall, kern_ms = time_launches(launch, steps, warmup, state=[p])
+        if p_scratch:
+            keep_outputs(out=out)
+        else:
+            keep_outputs(out=out, p=p)
+        if not args.full:
+            return wall, kern_ms, None
         host, hk = cpu_checker()
         fresh = synth("f32", 64 * n, salt=41).view(64, n)
         refs_ = [host.rfft(n, r, 0) for r in fresh.cpu().numpy()]
@@ -509,7 +572,10 @@ def main_rank(args):
         def launch(s):
             dsp.rfft_fixed_batch(S, src, out)
 
-        wall, kern_ms = time_launches(launch, steps, warmup)
+        wall, kern_ms = time_launches(launch, steps, warmup, state=[src])
+        keep_outputs(out=out, src=src)
+        if not args.full:
+            return wall, kern_ms, None
         host, hk = cpu_checker()
         fresh = synth(kind, 16 * n, salt=43).view(16, n)
         fin = fresh.cpu().numpy()
@@ -533,6 +599,9 @@ def main_rank(args):
             dsp.conv_batch(a, b, out)
 
         wall, kern_ms = time_launches(launch, steps, warmup)
+        keep_outputs(out=out)
+        if not args.full:
+            return wall, kern_ms, None
         host, hk = cpu_checker()
         ok = all(out[i].cpu().numpy().tobytes() == host.conv("f32", a[i].cpu().numpy(), b.cpu().numpy()).tobytes()
                  for i in (0, batch - 1))
@@ -550,7 +619,10 @@ def main_rank(args):
         def launch(s):
             m.batch(frames, out, work)
 
-        wall, kern_ms = time_launches(launch, steps, warmup)
+        wall, kern_ms = time_launches(launch, steps, warmup, state=[frames])
+        keep_outputs(out=out)
+        if not args.full:
+            return wall, kern_ms, None
         host, hk = cpu_checker()
         fresh = synth("f32", 64 * n, salt=29).view(64, n)
         want = host.mfcc(cfg, fresh.cpu().numpy())
@@ -585,7 +657,10 @@ def main_rank(args):
         def launch(s):
             m.batch(frames, out, work)
 
-        wall, kern_ms = time_launches(launch, steps, warmup)
+        wall, kern_ms = time_launches(launch, steps, warmup, state=[frames])
+        keep_outputs(out=out)
+        if not args.full:
+            return wall, kern_ms, None
         host, hk = cpu_checker()
         fresh = synth(t, 64 * n, salt=31).view(64, n)
         want = getattr(host, f"mfcc_{t}")(cfg, fresh.cpu().numpy())
@@ -605,6 +680,9 @@ def main_rank(args):
             dsp.mat_mult_batch(a, b, c, fast=fast)
 
         wall, kern_ms = time_launches(launch, steps, warmup)
+        keep_outputs(c=c.view(-1, dim))
+        if not args.full:
+            return wall, kern_ms, None
         host, hk = cpu_checker()
         if kind == "q7":
             # the reference's q7 body keeps its output row offset in a uint16_t (arm_mat_mult_q7.c:704,
@@ -670,7 +748,7 @@ def main_rank(args):
             scaling = "strong"
         wall, kern_ms, parity = run_cfft(kind, n, batch, args.steps, args.warmup, strong_span=span)
         if span is not None:
-            batch = max(r["span"][1] for r in parity["per_rank"])   # the largest slice sets the time
+            batch = parallel.shard(args.global_batch, 0, world_n)[1]   # the largest slice sets the time
         units = batch * n                                 # complex samples per launch per GPU
         algo_bytes = units * bps
     elif args.workload.startswith("fir"):
@@ -858,17 +936,25 @@ def main_rank(args):
             line["roofline"]["valu_fp32"] = {"achieved_gsamples": round(gs, 1), "peak_gsamples": 614.0,
                                              "frac": round(gs / 614.0, 4),
                                              "note": "157.3 TFLOP/s FP32 VALU / (2 flop x 128 taps)"}
-    line["parity"] = parity
+    line["full"] = bool(args.full)
+    if parity is not None:
+        line["parity"] = parity
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        tag = f"_rank{rank}" if world_n > 1 else ""
+        for name, arr in dumped.items():
+            np.save(os.path.join(args.dump_outputs, f"{name}{tag}.npy"), arr)
+        line["dumped_outputs"] = {name: list(arr.shape) for name, arr in dumped.items()}
 
     # ---------------------------------------------------------------- configs[3]
-    if args.workload == "cfft_f32_1024" and not args.no_config3:
+    if args.workload == "cfft_f32_1024" and args.full and not args.no_config3:
         torch.cuda.empty_cache()
         span = parallel.shard(args.global_batch, rank, world_n)
         c3 = {"workload": f"arm_cfft_q31 + arm_cfft_q15 N=4096, global batch={args.global_batch} split over "
                           f"{world_n} ranks in contiguous slices, in place, bitReverseFlag=1, alternating fwd/inv "
                           f"(BASELINE configs[3])", "scaling": "strong", "global_batch": args.global_batch}
         for qk, qbps in (("q31", 16), ("q15", 8)):
-            w2, k2, p2 = run_cfft(qk, 4096, 0, args.steps, args.warmup, strong_span=span)
+            w2, k2, p2 = run_cfft(qk, 4096, 0, args.steps, args.warmup, strong_span=span, headline=False)
             w2 = parallel.reduce_max(world, w2)
             k2 = parallel.reduce_max(world, k2)
             biggest = max(r["span"][1] for r in p2["per_rank"])
@@ -892,7 +978,7 @@ def main_rank(args):
                 c3[qk]["scatter"] = run_scatter(qk, 4096)
         line["config3"] = c3
 
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         secs = (args.cpu_secs, args.cpu_secs) if args.cpu_secs else (1.0, 3.0)
         try:
             line["cpu_baseline"] = cpu_baseline(args.workload, n, *secs)
@@ -940,7 +1026,7 @@ def dry_run(args, world, parallel):
         oks = parallel.gather_objects(world, ok)
         if line is not None:
             line["scatter"] = {"rows": G, "slices_verified": bool(all(oks)), "ranks": world.size}
-    if world.rank == 0 and not args.no_cpu_baseline:
+    if world.rank == 0 and args.full and not args.no_cpu_baseline:
         secs = args.cpu_secs or 0.2
         line["cpu_baseline"] = cpu_baseline("cfft_f32_1024", 1024, secs, secs)
     parallel.barrier(world, sync_device=False)

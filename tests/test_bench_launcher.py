@@ -39,7 +39,7 @@ def test_gpus2_scatter_leg_and_cpu_baseline():
     """N > 1 lines carry rank 0's cpu_baseline, and --scatter moves each rank its contiguous
     slice of the global batch from rank 0 (point-to-point; gloo on CPU here)."""
     r = _run(["--gpus", "2", "--dry-run", "--scaling", "strong", "--global-batch", "1000", "--scatter",
-              "--cpu-secs", "0.2"])
+              "--full", "--cpu-secs", "0.2"])
     assert r.returncode == 0, r.stderr[-2000:]
     line = _line(r.stdout)
     assert line["scatter"] == {"rows": 1000, "slices_verified": True, "ranks": 2}

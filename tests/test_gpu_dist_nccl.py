@@ -28,7 +28,7 @@ def test_bench_one_rank_rccl_group(torch_gpu):
     env.update({"CMSISDSP_DIST_SINGLE": "1", "RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "1",
                 "LOCAL_WORLD_SIZE": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(_free_port())})
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--batch", "65536", "--global-batch", "65536", "--scatter", "--no-cpu-baseline"],
+                        "--batch", "65536", "--global-batch", "65536", "--full", "--scatter", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=110, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = r.stdout.splitlines()
