@@ -251,15 +251,16 @@ __global__ __launch_bounds__(256, MI355X_FIR_Q15_MFMA_WG) void fir_q15_mfma_kern
   const int32_t sumc = info[0];                          // |sum c| <= 160 * 2^15
   for (int u = tid; u < 2 * KS * 3 * 64; u += 256) imgl[u] = image[u];   // visible after the loop's first barrier
 
-  // window word u (samples 2u, 2u + 1 of w) of item `it`, w[m] = s[n0 - d + m], d = parity of the
-  // block-input offset so that the words of the block input are 4-byte aligned
+  // window word u (samples 2u, 2u + 1 of w) of item `it`, w[m] = s[n0 - d + m], d = bit 1 of the
+  // ADDRESS of the block-input sample under w[d] (src's own 2-mod-4 offset included), so that the
+  // words of the block input are 4-byte aligned for any int16-aligned src
   struct Item { uint32_t f; int n0, count, d; };
   auto item_of = [&](uint32_t it) {
     Item x;
     x.f = it / nchunks;
     x.n0 = (int)(it - x.f * nchunks) * kFmChunk;
     x.count = min((int)B - x.n0, kFmChunk);
-    x.d = ALN ? d_base : (int)(((uint64_t)x.f * B + (uint32_t)x.n0 - (uint32_t)T1) & 1u);   // s index n0 - d + m -> src f B + n0 - d + m - T1
+    x.d = ALN ? d_base : (int)((((uint64_t)(uintptr_t)src >> 1) + (uint64_t)x.f * B + (uint32_t)x.n0 - (uint32_t)T1) & 1u);   // s index n0 - d + m -> src f B + n0 - d + m - T1
     return x;
   };
   // Window words in PAIRS: thread tid takes words 2 (tid + 256 q) and + 1 (4 samples, one 4-byte
@@ -287,7 +288,7 @@ __global__ __launch_bounds__(256, MI355X_FIR_Q15_MFMA_WG) void fir_q15_mfma_kern
   };
   auto load_window = [&](const Item& x) {
     const Win w = win_of(x);
-    const int64_t base = (int64_t)x.f * B + x.n0 - x.d - T1;               // src index of w[0] (even)
+    const int64_t base = (int64_t)x.f * B + x.n0 - x.d - T1;               // src index of w[0] (its address 4-byte aligned)
     if constexpr (ALN) {
       int m_lo, m_hi;
       aln_bounds(x, m_lo, m_hi);
@@ -835,7 +836,9 @@ __global__ __launch_bounds__(256) void fir_q7_mfma_kernel(int T, int d_base, con
     x.f = it / nchunks;
     x.n0 = (int)(it - x.f * nchunks) * kFmChunk;
     x.count = min((int)B - x.n0, kFmChunk);
-    x.d = ALN ? d_base : (int)(((uint64_t)x.f * B + (uint32_t)x.n0 - (uint32_t)T1) & 3u);   // w[m] = s[n0 - d + m]
+    // w[m] = s[n0 - d + m]; d = the low address bits of the block-input sample under w[d], so blk
+    // below is 4-byte aligned for ANY src (an offset view, the drop-in's state + numTaps - 1)
+    x.d = ALN ? d_base : (int)(((uint64_t)(uintptr_t)src + (uint64_t)x.f * B + (uint32_t)x.n0 - (uint32_t)T1) & 3u);
     return x;
   };
   // Window words (4 samples) from CLAMPED aligned block-input words, no branch; the words not wholly
