@@ -65,6 +65,8 @@ for _t in ("f32", "q31", "q15"):
                                                             _abi.arm_fir_interpolate_instance)
 for _t in ("f32", "q31", "q15"):
     globals()[f"arm_fir_lattice_instance_{_t}"] = _make(f"arm_fir_lattice_instance_{_t}", _abi.arm_fir_lattice_instance)
+for _t in {v[0].__name__: v[0] for v in _abi.BIQUAD_FUNCS.values()}.values():
+    globals()[_t.__name__] = _make(_t.__name__, _t)
 for _t in ("f32", "q31", "q15", "q7"):
     globals()[f"arm_fir_sparse_instance_{_t}"] = _make(f"arm_fir_sparse_instance_{_t}", _abi.arm_fir_sparse_instance)
 del _t
@@ -297,6 +299,54 @@ for _k in ("f32", "q31", "q15"):
     globals()[f"arm_fir_lattice_init_{_k}"] = _lattice_init(_k)
     globals()[f"arm_fir_lattice_{_k}"] = _lattice(_k)
 del _k
+
+
+# cmsisdsp_filtering.c cmsis_arm_biquad_cascade_*_init_* ("OiOO" / "OiOOi": S, numStages, pCoeffs, pState
+# [, postShift], :3672-3880, :5232-5400) and the processing functions ("OO": S, pSrc; returns len(pSrc)
+# words).  The module keeps its own zeroed state of the length the function needs.  Stereo: pSrc holds
+# interleaved L,R words and blockSize is len(pSrc) / 2 (the extension passes len(pSrc) and overruns
+# its own output buffer).
+_BQ_STATE = {"arm_biquad_cascade_df1_init_f32": (4, _np.float32, _np.float32, 5),
+             "arm_biquad_cascade_df1_init_q31": (4, _np.int32, _np.int32, 5),
+             "arm_biquad_cascade_df1_init_q15": (4, _np.int16, _np.int16, 6),
+             "arm_biquad_cas_df1_32x64_init_q31": (4, _np.int64, _np.int32, 5),
+             "arm_biquad_cascade_df2T_init_f32": (2, _np.float32, _np.float32, 5),
+             "arm_biquad_cascade_stereo_df2T_init_f32": (4, _np.float32, _np.float32, 5)}
+
+
+def _biquad_init(name, with_shift):
+    ks, sdt, cdt, nc = _BQ_STATE[name]
+
+    def init(inst, numStages, pCoeffs, pState, *postShift):
+        if len(postShift) != (1 if with_shift else 0):
+            raise TypeError(f"{name}: takes {5 if with_shift else 4} arguments")
+        c = _arr(pCoeffs, cdt)
+        if len(c) < nc * int(numStages):
+            raise ValueError(f"{name}: {nc} coefficients per stage")
+        state = _np.zeros(max(len(_np.asarray(pState)), ks * int(numStages)), dtype=sdt)
+        inst._keep = [c, state]
+        getattr(_lib, name)(_C.byref(inst._s), int(numStages), c.ctypes.data, state.ctypes.data,
+                            *[int(v) for v in postShift])
+        _check(name)
+    init.__name__ = name
+    return init
+
+
+def _biquad(name, dt, ch):
+    def run(inst, pSrc):
+        x = _arr(pSrc, dt)
+        y = _np.zeros(len(x), dtype=dt)
+        getattr(_lib, name)(_C.byref(inst._s), x.ctypes.data, y.ctypes.data, len(x) // ch)
+        _check(name)
+        return y
+    run.__name__ = name
+    return run
+
+
+for _f, (_i, _init, _ps) in _abi.BIQUAD_FUNCS.items():
+    globals()[_init] = _biquad_init(_init, _ps is not None)
+    globals()[_f] = _biquad(_f, _BQ_STATE[_init][2], 2 if "stereo" in _f else 1)
+del _f, _i, _init, _ps
 
 
 # cmsisdsp_filtering.c cmsis_arm_fir_sparse_init_* ("OhOOOh": S, numTaps, pCoeffs, pState,

@@ -71,6 +71,31 @@ class arm_fir_lattice_instance(C.Structure):
     _fields_ = [("numStages", C.c_uint16), ("pState", C.c_void_p), ("pCoeffs", C.c_void_p)]
 
 
+# Biquad cascade instances (filtering_functions.h:285-312, :1148-1203)
+class arm_biquad_casd_df1_inst_q15(C.Structure):
+    _fields_ = [("numStages", C.c_int8), ("pState", C.c_void_p), ("pCoeffs", C.c_void_p), ("postShift", C.c_int8)]
+
+
+class arm_biquad_casd_df1_inst_q31(C.Structure):
+    _fields_ = [("numStages", C.c_uint32), ("pState", C.c_void_p), ("pCoeffs", C.c_void_p), ("postShift", C.c_uint8)]
+
+
+class arm_biquad_casd_df1_inst_f32(C.Structure):
+    _fields_ = [("numStages", C.c_uint32), ("pState", C.c_void_p), ("pCoeffs", C.c_void_p)]
+
+
+class arm_biquad_cas_df1_32x64_ins_q31(C.Structure):
+    _fields_ = [("numStages", C.c_uint8), ("pState", C.c_void_p), ("pCoeffs", C.c_void_p), ("postShift", C.c_uint8)]
+
+
+class arm_biquad_cascade_df2T_instance_f32(C.Structure):
+    _fields_ = [("numStages", C.c_uint8), ("pState", C.c_void_p), ("pCoeffs", C.c_void_p)]
+
+
+class arm_biquad_cascade_stereo_df2T_instance_f32(C.Structure):
+    _fields_ = [("numStages", C.c_uint8), ("pState", C.c_void_p), ("pCoeffs", C.c_void_p)]
+
+
 # arm_fir_sparse_instance_{f32,q31,q15,q7} (filtering_functions.h:2033-2091), one layout
 class arm_fir_sparse_instance(C.Structure):
     _fields_ = [("numTaps", C.c_uint16), ("stateIndex", C.c_uint16), ("pState", C.c_void_p), ("pCoeffs", C.c_void_p),
@@ -234,6 +259,24 @@ for _t in ("f32", "q31", "q15"):
 for _n in RFFT_SIZES:
     DROPIN[f"arm_rfft_fast_init_{_n}_f32"] = (C.c_int, [P(arm_rfft_fast_instance_f32)])
 
+# Biquad cascades: processing function -> (instance, init function, init takes postShift).  The product
+# only: neither CPU checker builds them (tests/golden/biquad.npz holds the reference's outputs).
+BIQUAD_FUNCS = {
+    "arm_biquad_cascade_df1_f32": (arm_biquad_casd_df1_inst_f32, "arm_biquad_cascade_df1_init_f32", None),
+    "arm_biquad_cascade_df1_q31": (arm_biquad_casd_df1_inst_q31, "arm_biquad_cascade_df1_init_q31", C.c_int8),
+    "arm_biquad_cascade_df1_fast_q31": (arm_biquad_casd_df1_inst_q31, "arm_biquad_cascade_df1_init_q31", C.c_int8),
+    "arm_biquad_cascade_df1_q15": (arm_biquad_casd_df1_inst_q15, "arm_biquad_cascade_df1_init_q15", C.c_int8),
+    "arm_biquad_cascade_df1_fast_q15": (arm_biquad_casd_df1_inst_q15, "arm_biquad_cascade_df1_init_q15", C.c_int8),
+    "arm_biquad_cas_df1_32x64_q31": (arm_biquad_cas_df1_32x64_ins_q31, "arm_biquad_cas_df1_32x64_init_q31", C.c_uint8),
+    "arm_biquad_cascade_df2T_f32": (arm_biquad_cascade_df2T_instance_f32, "arm_biquad_cascade_df2T_init_f32", None),
+    "arm_biquad_cascade_stereo_df2T_f32": (arm_biquad_cascade_stereo_df2T_instance_f32,
+                                           "arm_biquad_cascade_stereo_df2T_init_f32", None),
+}
+BIQUAD = {}
+for _f, (_inst, _init, _ps) in BIQUAD_FUNCS.items():
+    BIQUAD[_f] = (None, [P(_inst), C.c_void_p, C.c_void_p, C.c_uint32])
+    BIQUAD[_init] = (None, [P(_inst), C.c_uint8, C.c_void_p, C.c_void_p] + ([_ps] if _ps else []))
+
 # per-length MFCC init functions (the product and the reference build; the oracle has the
 # generic init only)
 MFCC_LEN = {f"arm_mfcc_init_{n}_f32": (C.c_int, [P(arm_mfcc_instance_f32), C.c_uint32, C.c_uint32, C.c_void_p,
@@ -292,6 +335,8 @@ BATCHED = {
        for k in ("interpolate_f32", "interpolate_q15", "interpolate_q31")},
     **{f"arm_fir_lattice_{t}_batch": (C.c_int, [P(arm_fir_lattice_instance), C.c_void_p, C.c_void_p, C.c_uint32,
                                                 C.c_uint32, C.c_void_p, C.c_void_p]) for t in ("f32", "q31", "q15")},
+    **{f"{f}_batch": (C.c_int, [P(inst), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p])
+       for f, (inst, _, _) in BIQUAD_FUNCS.items()},
     **{f"arm_fir_sparse_{t}_batch": (C.c_int, [P(arm_fir_sparse_instance), C.c_void_p, C.c_void_p, C.c_uint32,
                                                C.c_uint32, C.c_void_p, C.c_void_p]) for t in ("f32", "q31", "q15", "q7")},
     "arm_mat_mult_f32_batch": (C.c_int, [P(arm_matrix_instance_f32), P(arm_matrix_instance_f32),

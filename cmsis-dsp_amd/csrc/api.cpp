@@ -944,6 +944,59 @@ arm_status lattice_batch(const Inst* S, const T* d_src, T* d_dst, uint32_t B, ui
   return ARM_MATH_SUCCESS;
 }
 
+// ---- biquad cascades ------------------------------------------------------------------------
+// ks state words (of ST) and nc coefficients per stage, ch interleaved channels (biquad.hip).  Drop-in:
+// state (host or device) in, filter, state out, as lattice_sync; the inits zero the state as
+// arm_biquad_cascade_*_init_*.c do.
+template <typename ST, typename Inst, typename CT>
+void biquad_init(Inst* S, uint8_t numStages, const CT* pCoeffs, ST* pState, int ks, const char* what) {
+  if (!S) return;
+  S->numStages = numStages; S->pCoeffs = pCoeffs; S->pState = pState;
+  if (pState && numStages) zero_words(pState, sizeof(ST) * (size_t)ks * numStages, what);
+}
+
+template <typename T, typename ST, typename Inst>
+void biquad_sync(const Inst* S, int ps, const T* pSrc, T* pDst, uint32_t B, int op, int ch, int ks, int nc,
+                 const char* what) {
+  if (!S || !S->pState || !S->pCoeffs || !pSrc || !pDst || S->numStages <= 0 || B == 0) return;
+  const uint32_t M = (uint32_t)S->numStages;
+  hipStream_t st = sync_stream();
+  BlobScope hold(st);
+  bool ok = true;
+  const T* dc = device_coeffs<T>(S->pCoeffs, (int)(M * nc), &ok);
+  if (!ok) { set_error(hipErrorOutOfMemory, what); return; }
+  const bool dstate = is_device_ptr(S->pState), dsrc = is_device_ptr(pSrc), ddst = is_device_ptr(pDst);
+  const size_t sb = sizeof(T) * (size_t)B * ch, hb = sizeof(ST) * (size_t)M * ks;
+  ST* dhist = dstate ? S->pState : (ST*)scratch(hb + 16, 2);
+  const T* dsr = dsrc ? pSrc : (const T*)scratch(sb, 3);
+  T* dds = ddst ? pDst : (T*)scratch(sb + 16, 4);
+  if (!dhist || !dsr || !dds) { set_error(hipErrorOutOfMemory, what); return; }
+  HostIO io(st);
+  hipError_t e = hipSuccess;
+  if (!dstate) e = io.in(dhist, S->pState, hb);
+  if (e == hipSuccess && !dsrc) e = io.in((void*)dsr, pSrc, sb);
+  if (e == hipSuccess) e = biquad_run(op, dc, M, ps, dsr, dds, B, 1, dhist, st);
+  if (e == hipSuccess && !ddst) e = io.out(pDst, dds, sb);
+  if (e == hipSuccess && !dstate) e = io.out(S->pState, dhist, hb);
+  if (e == hipSuccess) e = io.finish();
+  if (e != hipSuccess) set_error(e, what);
+}
+
+template <typename T, typename ST, typename Inst>
+arm_status biquad_batch(const Inst* S, int ps, const T* d_src, T* d_dst, uint32_t B, uint32_t batch, ST* d_state,
+                        void* stream, int op, int nc, const char* what) {
+  if (!S || !S->pCoeffs || S->numStages <= 0 || !d_src || !d_dst || !d_state) return ARM_MATH_ARGUMENT_ERROR;
+  if (!batch || !B) return ARM_MATH_SUCCESS;
+  const uint32_t M = (uint32_t)S->numStages;
+  BlobScope hold((hipStream_t)stream);
+  bool ok = true;
+  const T* dc = device_coeffs<T>(S->pCoeffs, (int)(M * nc), &ok);
+  if (!ok) { set_error(hipErrorOutOfMemory, what); return ARM_MATH_ARGUMENT_ERROR; }
+  hipError_t e = biquad_run(op, dc, M, ps, d_src, d_dst, B, batch, d_state, (hipStream_t)stream);
+  if (e != hipSuccess) { set_error(e, what); return ARM_MATH_ARGUMENT_ERROR; }
+  return ARM_MATH_SUCCESS;
+}
+
 // ---- convolution / correlation family ------------------------------------------------
 // How each reference function maps onto one ConvJob (conv.hip):
 //   conv (exact):      x = pSrcA, h = pSrcB, all srcALen + srcBLen - 1 outputs forward;
@@ -1721,6 +1774,57 @@ MI355X_LATTICE(f32, float32_t, kLatF32)
 MI355X_LATTICE(q31, q31_t, kLatQ31)
 MI355X_LATTICE(q15, q15_t, kLatQ15)
 #undef MI355X_LATTICE
+// biquad cascades: NAME the processing function, INST its instance, PS the postShift expression
+#define MI355X_BIQUAD(NAME, INST, CT, ST, OP, CH, KS, NC, PS)                                           \
+  void NAME(const INST* S, const CT* pSrc, CT* pDst, uint32_t blockSize) {                              \
+    biquad_sync<CT, ST>(S, S ? (int)(PS) : 0, pSrc, pDst, blockSize, OP, CH, KS, NC, #NAME);            \
+  }                                                                                                     \
+  arm_status NAME##_batch(const INST* S, const CT* d_src, CT* d_dst, uint32_t blockSize, uint32_t batch, \
+                          ST* d_state, void* stream) {                                                  \
+    return biquad_batch<CT, ST>(S, S ? (int)(PS) : 0, d_src, d_dst, blockSize, batch, d_state, stream, OP, NC, \
+                                #NAME "_batch");                                                        \
+  }
+MI355X_BIQUAD(arm_biquad_cascade_df1_f32, arm_biquad_casd_df1_inst_f32, float32_t, float32_t, kBqDf1F32, 1, 4, 5, 0)
+MI355X_BIQUAD(arm_biquad_cascade_df1_q31, arm_biquad_casd_df1_inst_q31, q31_t, q31_t, kBqDf1Q31, 1, 4, 5, S->postShift)
+MI355X_BIQUAD(arm_biquad_cascade_df1_fast_q31, arm_biquad_casd_df1_inst_q31, q31_t, q31_t, kBqDf1FastQ31, 1, 4, 5,
+              S->postShift)
+MI355X_BIQUAD(arm_biquad_cascade_df1_q15, arm_biquad_casd_df1_inst_q15, q15_t, q15_t, kBqDf1Q15, 1, 4, 6, S->postShift)
+MI355X_BIQUAD(arm_biquad_cascade_df1_fast_q15, arm_biquad_casd_df1_inst_q15, q15_t, q15_t, kBqDf1FastQ15, 1, 4, 6,
+              S->postShift)
+MI355X_BIQUAD(arm_biquad_cas_df1_32x64_q31, arm_biquad_cas_df1_32x64_ins_q31, q31_t, q63_t, kBq32x64, 1, 4, 5,
+              S->postShift)
+MI355X_BIQUAD(arm_biquad_cascade_df2T_f32, arm_biquad_cascade_df2T_instance_f32, float32_t, float32_t, kBqDf2TF32, 1, 2,
+              5, 0)
+MI355X_BIQUAD(arm_biquad_cascade_stereo_df2T_f32, arm_biquad_cascade_stereo_df2T_instance_f32, float32_t, float32_t,
+              kBqStereoDf2TF32, 2, 4, 5, 0)
+#undef MI355X_BIQUAD
+void arm_biquad_cascade_df1_init_f32(arm_biquad_casd_df1_inst_f32* S, uint8_t numStages, const float32_t* pCoeffs,
+                                     float32_t* pState) {
+  biquad_init(S, numStages, pCoeffs, pState, 4, "arm_biquad_cascade_df1_init_f32");
+}
+void arm_biquad_cascade_df1_init_q31(arm_biquad_casd_df1_inst_q31* S, uint8_t numStages, const q31_t* pCoeffs,
+                                     q31_t* pState, int8_t postShift) {
+  biquad_init(S, numStages, pCoeffs, pState, 4, "arm_biquad_cascade_df1_init_q31");
+  if (S) S->postShift = (uint8_t)postShift;
+}
+void arm_biquad_cascade_df1_init_q15(arm_biquad_casd_df1_inst_q15* S, uint8_t numStages, const q15_t* pCoeffs,
+                                     q15_t* pState, int8_t postShift) {
+  biquad_init(S, numStages, pCoeffs, pState, 4, "arm_biquad_cascade_df1_init_q15");
+  if (S) S->postShift = postShift;
+}
+void arm_biquad_cas_df1_32x64_init_q31(arm_biquad_cas_df1_32x64_ins_q31* S, uint8_t numStages, const q31_t* pCoeffs,
+                                       q63_t* pState, uint8_t postShift) {
+  biquad_init(S, numStages, pCoeffs, pState, 4, "arm_biquad_cas_df1_32x64_init_q31");
+  if (S) S->postShift = postShift;
+}
+void arm_biquad_cascade_df2T_init_f32(arm_biquad_cascade_df2T_instance_f32* S, uint8_t numStages,
+                                      const float32_t* pCoeffs, float32_t* pState) {
+  biquad_init(S, numStages, pCoeffs, pState, 2, "arm_biquad_cascade_df2T_init_f32");
+}
+void arm_biquad_cascade_stereo_df2T_init_f32(arm_biquad_cascade_stereo_df2T_instance_f32* S, uint8_t numStages,
+                                             const float32_t* pCoeffs, float32_t* pState) {
+  biquad_init(S, numStages, pCoeffs, pState, 4, "arm_biquad_cascade_stereo_df2T_init_f32");
+}
 void arm_fir_sparse_f32(arm_fir_sparse_instance_f32* S, const float32_t* pSrc, float32_t* pDst, float32_t* pScratchIn,
                         uint32_t blockSize) {
   (void)pScratchIn;

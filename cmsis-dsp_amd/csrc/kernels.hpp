@@ -149,6 +149,13 @@ hipError_t fir_sparse_run(int op, const void* coeffs, const int32_t* delays, int
 enum LatOp { kLatF32 = 0, kLatQ31 = 1, kLatQ15 = 2 };
 hipError_t fir_lattice_run(int op, const void* coeffs, int num_stages, const void* src, void* dst,
                            uint32_t block_size, uint32_t batch, void* state, hipStream_t st);
+// Biquad cascades (biquad.hip): `batch` streams sharing numStages sections; coeffs 5 words per stage
+// (q15: 6, {b0, 0, b1, b2, a1, a2}); state [batch][K numStages] in the reference's layout (K = 4, DF2T
+// mono 2; 32x64: int64 words), updated in place.  Stereo: src / dst [batch][2 block_size] interleaved.
+enum BqOp { kBqDf1F32 = 0, kBqDf1Q31 = 1, kBqDf1FastQ31 = 2, kBqDf1Q15 = 3, kBqDf1FastQ15 = 4, kBq32x64 = 5,
+            kBqDf2TF32 = 6, kBqStereoDf2TF32 = 7 };
+hipError_t biquad_run(int op, const void* coeffs, uint32_t num_stages, int post_shift, const void* src, void* dst,
+                      uint32_t block_size, uint32_t batch, void* state, hipStream_t st);
 
 // MFCC f32 around the batched RFFT (mfcc_f32.hip): frame normalisation + window, then the
 // spectrum -> Mel -> log -> DCT tail.  post needs mfcc_f32_post_lds(n, nb_mel) bytes of LDS.

@@ -123,6 +123,24 @@
 #define MI355X_LAT_IPW 1   // 2 / 4 measured slower (f32 211 / 220 vs 221 Gsamples/s, q31 138 / 147 vs 172)
 #endif
 
+// ---- biquad.hip
+#ifndef MI355X_BQ_T
+#define MI355X_BQ_T 16     // words per tile: a lane's registers, handed to the next stage by DPP
+                           // (df1_f32 32 stages: T 8 | 16 | 32 = 72 | 83 | 72 Gsamples/s, one stream per lane)
+#endif
+#ifndef MI355X_BQ_G
+#define MI355X_BQ_G 2      // tiles per coalesced I/O group (T G = 32 words: one 128-B row per f32 stream)
+#endif
+// Stages per pass from which a lane runs two streams (65 = never).  Gsamples/s at 2^16 streams, two | one:
+// df1_f32 4 stages 393 | 474, 6: 336 | 314, 16: 186 | 158, 32: 98 | 82; df1_q31 8: 263 | 299, 12: 177 | 192,
+// 16: 164 | 164, 32: 89 | 86; df1_q15 12: 126 | 132, 16: 112 | 109, 32: 58 | 54.
+#ifndef MI355X_BQ_NS2_F32
+#define MI355X_BQ_NS2_F32 6
+#endif
+#ifndef MI355X_BQ_NS2_FX
+#define MI355X_BQ_NS2_FX 16
+#endif
+
 // ---- mat_mult_fixed.hip
 #ifndef MI355X_I8_SCHED
 #define MI355X_I8_SCHED 10

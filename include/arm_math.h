@@ -268,6 +268,43 @@ MI355X_LATTICE_INST(q31, q31_t)
 MI355X_LATTICE_INST(f32, float32_t)
 #undef MI355X_LATTICE_INST
 
+/* Biquad cascade instances (Include/dsp/filtering_functions.h:285-312, :1148-1203).  State words per
+ * stage: DF1 4 {x1, x2, y1, y2} (32x64: q63 words), DF2T 2 {d1, d2}, stereo DF2T 4 {d1a, d2a, d1b, d2b};
+ * coefficients per stage 5 {b0, b1, b2, a1, a2}, q15 6 {b0, 0, b1, b2, a1, a2}. */
+typedef struct {
+        int8_t  numStages;
+        q15_t  *pState;      /* 4*numStages */
+  const q15_t  *pCoeffs;     /* 6*numStages */
+        int8_t  postShift;
+} arm_biquad_casd_df1_inst_q15;
+typedef struct {
+        uint32_t numStages;
+        q31_t   *pState;     /* 4*numStages */
+  const q31_t   *pCoeffs;    /* 5*numStages */
+        uint8_t  postShift;
+} arm_biquad_casd_df1_inst_q31;
+typedef struct {
+        uint32_t   numStages;
+        float32_t *pState;   /* 4*numStages */
+  const float32_t *pCoeffs;  /* 5*numStages */
+} arm_biquad_casd_df1_inst_f32;
+typedef struct {
+        uint8_t  numStages;
+        q63_t   *pState;     /* 4*numStages */
+  const q31_t   *pCoeffs;    /* 5*numStages */
+        uint8_t  postShift;
+} arm_biquad_cas_df1_32x64_ins_q31;
+typedef struct {
+        uint8_t    numStages;
+        float32_t *pState;   /* 2*numStages */
+  const float32_t *pCoeffs;  /* 5*numStages */
+} arm_biquad_cascade_df2T_instance_f32;
+typedef struct {
+        uint8_t    numStages;
+        float32_t *pState;   /* 4*numStages */
+  const float32_t *pCoeffs;  /* 5*numStages */
+} arm_biquad_cascade_stereo_df2T_instance_f32;
+
 /* ---- matrix instances: Include/dsp/matrix_functions.h:118-123 (f32), :139-143 (q7),
  * :139-144 (q15), :149-154 (q31) */
 typedef struct {
@@ -615,6 +652,43 @@ void arm_fir_lattice_f32(const arm_fir_lattice_instance_f32 *S, const float32_t 
                          uint32_t blockSize);
 void arm_fir_lattice_q31(const arm_fir_lattice_instance_q31 *S, const q31_t *pSrc, q31_t *pDst, uint32_t blockSize);
 void arm_fir_lattice_q15(const arm_fir_lattice_instance_q15 *S, const q15_t *pSrc, q15_t *pDst, uint32_t blockSize);
+
+/* ===================================================================================
+ * Biquad cascades.  Prototypes: Include/dsp/filtering_functions.h:331-441, :1163-1182, :1223-1295.
+ * Reference bodies: Source/FilteringFunctions/arm_biquad_cascade_df1_{f32,q31,fast_q31,q15,fast_q15}.c,
+ * arm_biquad_cascade_df1_32x64_q31.c, arm_biquad_cascade_df2T_f32.c, arm_biquad_cascade_stereo_df2T_f32.c
+ * (scalar path); the inits set the fields and zero the state.  Stages run in order, the first from
+ * pSrc and the rest in place over pDst (pSrc == pDst is allowed); the state is read before the
+ * block and written after it.  Stereo: pSrc / pDst hold 2*blockSize interleaved words.
+ * =================================================================================== */
+void arm_biquad_cascade_df1_init_f32(arm_biquad_casd_df1_inst_f32 *S, uint8_t numStages, const float32_t *pCoeffs,
+                                     float32_t *pState);
+void arm_biquad_cascade_df1_f32(const arm_biquad_casd_df1_inst_f32 *S, const float32_t *pSrc, float32_t *pDst,
+                                uint32_t blockSize);
+void arm_biquad_cascade_df1_init_q31(arm_biquad_casd_df1_inst_q31 *S, uint8_t numStages, const q31_t *pCoeffs,
+                                     q31_t *pState, int8_t postShift);
+void arm_biquad_cascade_df1_q31(const arm_biquad_casd_df1_inst_q31 *S, const q31_t *pSrc, q31_t *pDst,
+                                uint32_t blockSize);
+void arm_biquad_cascade_df1_fast_q31(const arm_biquad_casd_df1_inst_q31 *S, const q31_t *pSrc, q31_t *pDst,
+                                     uint32_t blockSize);
+void arm_biquad_cascade_df1_init_q15(arm_biquad_casd_df1_inst_q15 *S, uint8_t numStages, const q15_t *pCoeffs,
+                                     q15_t *pState, int8_t postShift);
+void arm_biquad_cascade_df1_q15(const arm_biquad_casd_df1_inst_q15 *S, const q15_t *pSrc, q15_t *pDst,
+                                uint32_t blockSize);
+void arm_biquad_cascade_df1_fast_q15(const arm_biquad_casd_df1_inst_q15 *S, const q15_t *pSrc, q15_t *pDst,
+                                     uint32_t blockSize);
+void arm_biquad_cas_df1_32x64_init_q31(arm_biquad_cas_df1_32x64_ins_q31 *S, uint8_t numStages, const q31_t *pCoeffs,
+                                       q63_t *pState, uint8_t postShift);
+void arm_biquad_cas_df1_32x64_q31(const arm_biquad_cas_df1_32x64_ins_q31 *S, const q31_t *pSrc, q31_t *pDst,
+                                  uint32_t blockSize);
+void arm_biquad_cascade_df2T_init_f32(arm_biquad_cascade_df2T_instance_f32 *S, uint8_t numStages,
+                                      const float32_t *pCoeffs, float32_t *pState);
+void arm_biquad_cascade_df2T_f32(const arm_biquad_cascade_df2T_instance_f32 *S, const float32_t *pSrc,
+                                 float32_t *pDst, uint32_t blockSize);
+void arm_biquad_cascade_stereo_df2T_init_f32(arm_biquad_cascade_stereo_df2T_instance_f32 *S, uint8_t numStages,
+                                             const float32_t *pCoeffs, float32_t *pState);
+void arm_biquad_cascade_stereo_df2T_f32(const arm_biquad_cascade_stereo_df2T_instance_f32 *S, const float32_t *pSrc,
+                                        float32_t *pDst, uint32_t blockSize);
 
 /* ===================================================================================
  * Convolution.  Prototypes: Include/dsp/filtering_functions.h

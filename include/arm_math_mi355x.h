@@ -156,6 +156,36 @@ arm_status arm_fir_lattice_q31_batch(const arm_fir_lattice_instance_q31 *S, cons
 arm_status arm_fir_lattice_q15_batch(const arm_fir_lattice_instance_q15 *S, const q15_t *d_src, q15_t *d_dst,
                                      uint32_t blockSize, uint32_t batch, q15_t *d_state, void *stream);
 
+/* Biquad cascades over `batch` independent streams sharing S's coefficients (host pointer, content-
+ * cached, or device pointer) and postShift: d_src / d_dst [batch][blockSize] (stereo: [batch][2*blockSize]
+ * interleaved L,R), d_state [batch][K*numStages] with each stream's state in the reference's own
+ * layout (K = 4; DF2T mono 2; 32x64: q63 words), zero-initialise to start a stream; updated in place, so
+ * consecutive calls equal one long call.  S->pState is unused.  d_src == d_dst is allowed.
+ * numStages == 0 or a NULL pointer: ARM_MATH_ARGUMENT_ERROR; blockSize == 0 or batch == 0: success,
+ * nothing touched.  Per-stream semantics: the drop-in functions of arm_math.h. */
+arm_status arm_biquad_cascade_df1_f32_batch(const arm_biquad_casd_df1_inst_f32 *S, const float32_t *d_src,
+                                            float32_t *d_dst, uint32_t blockSize, uint32_t batch, float32_t *d_state,
+                                            void *stream);
+arm_status arm_biquad_cascade_df1_q31_batch(const arm_biquad_casd_df1_inst_q31 *S, const q31_t *d_src, q31_t *d_dst,
+                                            uint32_t blockSize, uint32_t batch, q31_t *d_state, void *stream);
+arm_status arm_biquad_cascade_df1_fast_q31_batch(const arm_biquad_casd_df1_inst_q31 *S, const q31_t *d_src,
+                                                 q31_t *d_dst, uint32_t blockSize, uint32_t batch, q31_t *d_state,
+                                                 void *stream);
+arm_status arm_biquad_cascade_df1_q15_batch(const arm_biquad_casd_df1_inst_q15 *S, const q15_t *d_src, q15_t *d_dst,
+                                            uint32_t blockSize, uint32_t batch, q15_t *d_state, void *stream);
+arm_status arm_biquad_cascade_df1_fast_q15_batch(const arm_biquad_casd_df1_inst_q15 *S, const q15_t *d_src,
+                                                 q15_t *d_dst, uint32_t blockSize, uint32_t batch, q15_t *d_state,
+                                                 void *stream);
+arm_status arm_biquad_cas_df1_32x64_q31_batch(const arm_biquad_cas_df1_32x64_ins_q31 *S, const q31_t *d_src,
+                                              q31_t *d_dst, uint32_t blockSize, uint32_t batch, q63_t *d_state,
+                                              void *stream);
+arm_status arm_biquad_cascade_df2T_f32_batch(const arm_biquad_cascade_df2T_instance_f32 *S, const float32_t *d_src,
+                                             float32_t *d_dst, uint32_t blockSize, uint32_t batch, float32_t *d_state,
+                                             void *stream);
+arm_status arm_biquad_cascade_stereo_df2T_f32_batch(const arm_biquad_cascade_stereo_df2T_instance_f32 *S,
+                                                    const float32_t *d_src, float32_t *d_dst, uint32_t blockSize,
+                                                    uint32_t batch, float32_t *d_state, void *stream);
+
 /* Convolution of `batch` pairs: item i convolves d_a + i*strideA (srcALen samples) with
  * d_b + i*strideB (srcBLen samples; strideB = 0 shares one kernel) into
  * d_dst + i*(srcALen + srcBLen - 1).  Per-item semantics: arm_conv_f32 / _q15 / _q31. */

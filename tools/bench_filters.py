@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Throughput of the filtering functions outside bench.py's workloads (round 2 additions):
-arm_fir_q7, arm_fir_decimate_*, arm_fir_interpolate_*, arm_fir_sparse_*, arm_fir_lattice_* through the batched device API on one
-GPU, HIP-event timed on the launch stream after a clock-settle phase, each with a bit-exact
-check of 2 streams against the CPU checker (the reference build when present).
+arm_fir_q7, arm_fir_decimate_*, arm_fir_interpolate_*, arm_fir_sparse_*, arm_fir_lattice_* and the biquad cascades through the
+batched device API on one GPU, HIP-event timed on the launch stream after a clock-settle phase, each with a bit-exact
+check of 2 streams against the CPU checker (the reference build when present; the biquad rows
+against tests/biquad_ref.py, the numpy restatement that equals the committed reference fixtures).
 Usage: python tools/bench_filters.py [name ...]  -> one JSON line per workload."""
 import ctypes as C
 import json
@@ -18,6 +19,7 @@ import torch  # noqa: E402
 
 import cmsisdsp_amd as dsp  # noqa: E402
 from cmsisdsp_amd import _abi  # noqa: E402
+import biquad_ref  # noqa: E402
 import refs  # noqa: E402
 
 BATCH, BLOCK, TAPS = 1 << 16, 4096, 128
@@ -40,6 +42,19 @@ CASES = {
     "fir_lattice_q31": ("lattice_q31", 1, "q31"),
     "fir_lattice_q15": ("lattice_q15", 1, "q15"),
 }
+# biquad rows: one JSON line per (numStages, batch) of BQ_SHAPES
+BIQUAD = {
+    "biquad_df1_f32": "arm_biquad_cascade_df1_f32",
+    "biquad_df1_q31": "arm_biquad_cascade_df1_q31",
+    "biquad_df1_q15": "arm_biquad_cascade_df1_q15",
+    "biquad_df1_fast_q31": "arm_biquad_cascade_df1_fast_q31",
+    "biquad_df1_fast_q15": "arm_biquad_cascade_df1_fast_q15",
+    "biquad_df2T_f32": "arm_biquad_cascade_df2T_f32",
+    "biquad_stereo_df2T_f32": "arm_biquad_cascade_stereo_df2T_f32",
+    "biquad_32x64_q31": "arm_biquad_cas_df1_32x64_q31",
+}
+BQ_SHAPES = [(4, BATCH), (32, BATCH), (4, 256), (32, 256)]
+HBM_PEAK = 8e12                         # bytes/s
 TDT = {"f32": torch.float32, "q15": torch.int16, "q31": torch.int32, "q7": torch.int8}
 
 
@@ -152,7 +167,56 @@ def run(name):
             "bit_exact": bool(ok), "checker": hk}
 
 
+def run_biquad(name, stages, batch):
+    func = BIQUAD[name]
+    dt, sdt, ks, nc, ch = biquad_ref.FUNCS[func]
+    ps = 1 if func in biquad_ref.HAS_SHIFT else 0
+    c = biquad_ref.stable_coeffs(func, stages, ps, 7)
+    tdt = {np.float32: torch.float32, np.int32: torch.int32, np.int16: torch.int16, np.int64: torch.int64}
+    g = torch.Generator(device="cuda")
+    g.manual_seed(11)
+    if dt == np.float32:
+        src = torch.rand((batch, BLOCK * ch), generator=g, device="cuda") - 0.5
+    else:
+        info = np.iinfo(dt)
+        src = torch.randint(int(info.min) // 2, int(info.max) // 2, (batch, BLOCK * ch), generator=g, device="cuda",
+                            dtype=torch.int64).to(tdt[dt])
+    dc = torch.from_numpy(c.copy()).cuda()
+    inst = _abi.BIQUAD_FUNCS[func][0]
+    kw = {"postShift": ps} if any(f == "postShift" for f, _ in inst._fields_) else {}
+    S = inst(numStages=stages, pState=None, pCoeffs=dc.data_ptr(), **kw)
+    f = getattr(dsp.lib, func + "_batch")
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    dst = torch.empty_like(src)
+    state = torch.zeros((batch, ks * stages), dtype=tdt[sdt], device="cuda")
+
+    def launch(d=dst, h=state, s=src, b=batch):
+        rc = f(C.byref(S), C.c_void_p(s.data_ptr()), C.c_void_p(d.data_ptr()), BLOCK, b, C.c_void_p(h.data_ptr()),
+               stream)
+        assert rc == 0, dsp.last_error()
+
+    ms = timed(launch)
+    state.zero_()                          # parity: the first and the last stream from a zero state
+    launch()
+    torch.cuda.synchronize()
+    rows = [0, batch - 1]
+    want, wstate = biquad_ref.run(func, c, ps, src[rows].cpu().numpy(), np.zeros((2, ks * stages), dtype=sdt))
+    ok = dst[rows].cpu().numpy().tobytes() == want.tobytes() and state[rows].cpu().numpy().tobytes() == wstate.tobytes()
+    esz = np.dtype(dt).itemsize
+    rate = batch * BLOCK * ch / (ms * 1e-3)      # words per second
+    return {"workload": name, "function": func, "numStages": stages, "blockSize": BLOCK, "batch": batch,
+            "avg_kernel_ms": round(ms, 4), "gsamples_per_s": round(rate * 1e-9, 2),
+            "gstage_samples_per_s": round(rate * stages * 1e-9, 1),
+            "hbm_gbs": round(rate * 2 * esz * 1e-9, 1), "hbm_fraction": round(rate * 2 * esz / HBM_PEAK, 3),
+            "bit_exact": bool(ok), "checker": "biquad_ref"}
+
+
 if __name__ == "__main__":
-    for name in sys.argv[1:] or list(CASES):
+    for name in sys.argv[1:] or list(CASES) + list(BIQUAD):
+        if name in BIQUAD:
+            for stages, batch in BQ_SHAPES:
+                print(json.dumps(run_biquad(name, stages, batch)), flush=True)
+                torch.cuda.empty_cache()
+            continue
         print(json.dumps(run(name)), flush=True)
         torch.cuda.empty_cache()
