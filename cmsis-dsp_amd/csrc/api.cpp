@@ -27,6 +27,13 @@ bool cfft_len_ok(uint32_t n) {
     if (e_ != hipSuccess) { set_error(e_, where); return false; } \
   } while (0)
 
+// status of a batched entry point whose last step returned e; a failure is recorded under `what`
+arm_status batch_status(hipError_t e, const char* what) {
+  if (e == hipSuccess) return ARM_MATH_SUCCESS;
+  set_error(e, what);
+  return ARM_MATH_ARGUMENT_ERROR;
+}
+
 struct CfftPrep {
   const void* tw = nullptr;
   const uint16_t* perm = nullptr;
@@ -112,9 +119,7 @@ arm_status cfft_batch(const Inst* S, void* d_p1, uint32_t batch, uint8_t ifftFla
   CfftPrep pr;
   if (!cfft_prepare(S->fftLen, S->pTwiddle, S->pBitRevTable, S->bitRevLength, kind, ifftFlag, bitReverseFlag, pr))
     return ARM_MATH_ARGUMENT_ERROR;
-  hipError_t e = cfft_launch(kind, S->fftLen, d_p1, batch, pr, (hipStream_t)stream);
-  if (e != hipSuccess) { set_error(e, "arm_cfft_batch"); return ARM_MATH_ARGUMENT_ERROR; }
-  return ARM_MATH_SUCCESS;
+  return batch_status(cfft_launch(kind, S->fftLen, d_p1, batch, pr, (hipStream_t)stream), "arm_cfft_batch");
 }
 
 // multi-GPU: validate every shard, launch each on its device's internal stream (one BlobScope per
@@ -322,11 +327,13 @@ arm_status rfft_fixed_batch(const RInst* S, T* d_src, T* d_dst, uint32_t batch, 
 
 // ---- MFCC (arm_mfcc_f32.c:83-160): the instance's user tables packed into one
 // content-cached device blob: [dct | filter coefs | window | pos | len | coef offsets]
+// (T words: f32, or q31 / q15 for the fixed-point instances, which append to it)
+template <typename T>
 struct MfccDev {
   int total = 0;                   // Mel coefficients (sum of filterLengths)
-  const float* dct = nullptr;
-  const float* coefs = nullptr;
-  const float* win = nullptr;
+  const T* dct = nullptr;
+  const T* coefs = nullptr;
+  const T* win = nullptr;
   const uint32_t* pos = nullptr;
   const uint32_t* len = nullptr;
   const uint32_t* off = nullptr;
@@ -342,11 +349,21 @@ bool host_copy(const T* p, size_t count, std::vector<T>& out) {
   return true;
 }
 
-bool mfcc_prepare(const arm_mfcc_instance_f32* S, MfccDev& d) {
+size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// byte offsets of the blob's parts (dct at 0), each padded to 16 B; end: where a caller may append
+struct MfccLayout {
+  size_t coefs, win, pos, len, off, end;
+  uint64_t total;
+};
+
+// Packs the blob above from the instance's (host or device) tables: blob gets lay.end bytes, pos / len
+// the filter tables.  bound: the bins a Mel filter may read (pos + len <= bound), `beyond` the error
+// a filter past it is reported under.
+template <typename T, typename Inst>
+bool mfcc_pack(const Inst* S, uint32_t bound, const char* beyond, std::vector<uint8_t>& blob,
+               std::vector<uint32_t>& pos, std::vector<uint32_t>& len, MfccLayout& lay) {
   const uint32_t n = S->fftLen, nm = S->nbMelFilters, nd = S->nbDctOutputs;
-  if (!rfft_len_ok(n) || S->rfft.fftLenRFFT != n) { set_error(hipErrorInvalidValue, "mfcc instance"); return false; }
-  if (mfcc_f32_post_lds((int)n, (int)nm) > 65536) { set_error(hipErrorInvalidValue, "mfcc: too many Mel filters"); return false; }
-  std::vector<uint32_t> pos, len;
   if (!host_copy(S->filterPos, nm, pos) || !host_copy(S->filterLengths, nm, len)) {
     set_error(hipErrorInvalidValue, "mfcc filter tables");
     return false;
@@ -354,34 +371,56 @@ bool mfcc_prepare(const arm_mfcc_instance_f32* S, MfccDev& d) {
   std::vector<uint32_t> off(nm);
   uint64_t total = 0;
   for (uint32_t i = 0; i < nm; ++i) {
-    if ((uint64_t)pos[i] + len[i] > n) { set_error(hipErrorInvalidValue, "mfcc filter beyond fftLen"); return false; }
+    if ((uint64_t)pos[i] + len[i] > bound) { set_error(hipErrorInvalidValue, beyond); return false; }
     off[i] = (uint32_t)total;
     total += len[i];
   }
-  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  const size_t b_dct = up16(sizeof(float) * nm * nd), b_cf = up16(sizeof(float) * total), b_win = up16(sizeof(float) * n);
   const size_t b_u = up16(sizeof(uint32_t) * nm);
-  std::vector<uint8_t> blob(b_dct + b_cf + b_win + 3 * b_u + 16, 0);
-  std::vector<float> tmp;
+  lay.total = total;
+  lay.coefs = up16(sizeof(T) * nm * nd);
+  lay.win = lay.coefs + up16(sizeof(T) * total);
+  lay.pos = lay.win + up16(sizeof(T) * n);
+  lay.len = lay.pos + b_u;
+  lay.off = lay.len + b_u;
+  lay.end = lay.off + b_u;
+  blob.assign(lay.end, 0);
+  std::vector<T> tmp;
   if (!host_copy(S->dctCoefs, (size_t)nm * nd, tmp)) { set_error(hipErrorInvalidValue, "mfcc dct"); return false; }
-  memcpy(blob.data(), tmp.data(), sizeof(float) * tmp.size());
+  memcpy(blob.data(), tmp.data(), sizeof(T) * tmp.size());
   if (!host_copy(S->filterCoefs, (size_t)total, tmp)) { set_error(hipErrorInvalidValue, "mfcc coefs"); return false; }
-  memcpy(blob.data() + b_dct, tmp.data(), sizeof(float) * tmp.size());
+  memcpy(blob.data() + lay.coefs, tmp.data(), sizeof(T) * tmp.size());
   if (!host_copy(S->windowCoefs, (size_t)n, tmp)) { set_error(hipErrorInvalidValue, "mfcc window"); return false; }
-  memcpy(blob.data() + b_dct + b_cf, tmp.data(), sizeof(float) * tmp.size());
-  uint8_t* u = blob.data() + b_dct + b_cf + b_win;
-  memcpy(u, pos.data(), sizeof(uint32_t) * nm);
-  memcpy(u + b_u, len.data(), sizeof(uint32_t) * nm);
-  memcpy(u + 2 * b_u, off.data(), sizeof(uint32_t) * nm);
+  memcpy(blob.data() + lay.win, tmp.data(), sizeof(T) * tmp.size());
+  memcpy(blob.data() + lay.pos, pos.data(), sizeof(uint32_t) * nm);
+  memcpy(blob.data() + lay.len, len.data(), sizeof(uint32_t) * nm);
+  memcpy(blob.data() + lay.off, off.data(), sizeof(uint32_t) * nm);
+  return true;
+}
+
+// the device views of the packed parts, dev the blob's device copy
+template <typename T>
+void mfcc_bind(MfccDev<T>& d, const uint8_t* dev, const MfccLayout& lay) {
+  d.total = (int)lay.total;
+  d.dct = (const T*)dev;
+  d.coefs = (const T*)(dev + lay.coefs);
+  d.win = (const T*)(dev + lay.win);
+  d.pos = (const uint32_t*)(dev + lay.pos);
+  d.len = (const uint32_t*)(dev + lay.len);
+  d.off = (const uint32_t*)(dev + lay.off);
+}
+
+bool mfcc_prepare(const arm_mfcc_instance_f32* S, MfccDev<float>& d) {
+  const uint32_t n = S->fftLen, nm = S->nbMelFilters;
+  if (!rfft_len_ok(n) || S->rfft.fftLenRFFT != n) { set_error(hipErrorInvalidValue, "mfcc instance"); return false; }
+  if (mfcc_f32_post_lds((int)n, (int)nm) > 65536) { set_error(hipErrorInvalidValue, "mfcc: too many Mel filters"); return false; }
+  std::vector<uint8_t> blob;
+  std::vector<uint32_t> pos, len;
+  MfccLayout lay;
+  if (!mfcc_pack<float>(S, n, "mfcc filter beyond fftLen", blob, pos, len, lay)) return false;
+  blob.resize(lay.end + 16, 0);
   const uint8_t* dev = (const uint8_t*)device_blob(blob.data(), blob.size());
   if (!dev) return false;
-  d.total = (int)total;
-  d.dct = (const float*)dev;
-  d.coefs = (const float*)(dev + b_dct);
-  d.win = (const float*)(dev + b_dct + b_cf);
-  d.pos = (const uint32_t*)(dev + b_dct + b_cf + b_win);
-  d.len = (const uint32_t*)(dev + b_dct + b_cf + b_win + b_u);
-  d.off = (const uint32_t*)(dev + b_dct + b_cf + b_win + 2 * b_u);
+  mfcc_bind(d, dev, lay);
   return true;
 }
 
@@ -389,7 +428,7 @@ bool mfcc_prepare(const arm_mfcc_instance_f32* S, MfccDev& d) {
 // (canonical) CFFT tables take the fused single-launch kernel (x read once, y unused);
 // otherwise three launches, x overwritten and the frame maxima carried in dst[frame][0]
 // between the passes (read before the row is written).
-bool mfcc_run(const arm_mfcc_instance_f32* S, const MfccDev& d, float* x, float* y, float* dst, uint32_t batch,
+bool mfcc_run(const arm_mfcc_instance_f32* S, const MfccDev<float>& d, float* x, float* y, float* dst, uint32_t batch,
               hipStream_t st) {
   const int n = (int)S->fftLen, nd = (int)S->nbDctOutputs, nm = (int)S->nbMelFilters;
   const arm_cfft_instance_f32& in = S->rfft.Sint;
@@ -417,40 +456,28 @@ bool mfcc_run(const arm_mfcc_instance_f32* S, const MfccDev& d, float* x, float*
 // fixed-point RFFT.  Mel filters must
 // stay within the fftLen/2 + 1 magnitudes (the reference would read its CFFT's leftovers).
 template <typename T>
-struct MfccFxDev {
-  const T* dct = nullptr;
-  const T* coefs = nullptr;
-  const T* win = nullptr;
-  const uint32_t* pos = nullptr;
-  const uint32_t* len = nullptr;
-  const uint32_t* off = nullptr;
+struct MfccFxDev : MfccDev<T> {
   const uint32_t* bf = nullptr;    // flat Mel coefficient g -> bin << 16 | filter
-  int total = 0;
   int kmin = 0, kcnt = 0;          // the bins some Mel filter reads: kmin .. kmin + kcnt - 1
   const int4* tw = nullptr;        // split twiddles per bin k <= fftLen/2: {A[2mk], A[2mk+1], B[2mk], B[2mk+1]}
   const int32_t* lut = nullptr;
 };
 
+// the blob: mfcc_pack's parts, then [bf | split twiddle records] (the records' packing is what
+// mfcc_fixed_post.hpp reads)
 template <typename T, typename Inst>
-bool mfcc_fx_prepare(const Inst* S, MfccFxDev<T>& d) {
-  const uint32_t n = S->fftLen, nm = S->nbMelFilters, nd = S->nbDctOutputs;
+bool mfcc_prepare(const Inst* S, MfccFxDev<T>& d) {
+  const uint32_t n = S->fftLen, nm = S->nbMelFilters;
   if (!rfft_len_ok(n) || S->rfft.fftLenReal != n || S->rfft.ifftFlagR != 0) {
     set_error(hipErrorInvalidValue, "mfcc q31 instance");
     return false;
   }
   if (mfcc_q31_post_lds((int)n, (int)nm) > 65536) { set_error(hipErrorInvalidValue, "mfcc q31: too many Mel filters"); return false; }
+  std::vector<uint8_t> blob;
   std::vector<uint32_t> pos, len;
-  if (!host_copy(S->filterPos, nm, pos) || !host_copy(S->filterLengths, nm, len)) {
-    set_error(hipErrorInvalidValue, "mfcc q31 filter tables");
-    return false;
-  }
-  std::vector<uint32_t> off(nm);
-  uint64_t total = 0;
-  for (uint32_t i = 0; i < nm; ++i) {
-    if ((uint64_t)pos[i] + len[i] > n / 2 + 1) { set_error(hipErrorInvalidValue, "mfcc q31 filter beyond fftLen/2"); return false; }
-    off[i] = (uint32_t)total;
-    total += len[i];
-  }
+  MfccLayout lay;
+  if (!mfcc_pack<T>(S, n / 2 + 1, "mfcc q31 filter beyond fftLen/2", blob, pos, len, lay)) return false;
+  const uint64_t total = lay.total;
   if (nm > 0xFFFFu || total > 0x7FFFFFFFull) { set_error(hipErrorInvalidValue, "mfcc: too many Mel coefficients"); return false; }
   {
     uint32_t lo = n, hi = 0;
@@ -459,23 +486,9 @@ bool mfcc_fx_prepare(const Inst* S, MfccFxDev<T>& d) {
     d.kmin = lo < hi ? (int)lo : 0;
     d.kcnt = lo < hi ? (int)(hi - lo) : 0;
   }
-  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  const size_t b_dct = up16(sizeof(T) * nm * nd), b_cf = up16(sizeof(T) * total), b_win = up16(sizeof(T) * n);
-  const size_t b_u = up16(sizeof(uint32_t) * nm), b_bf = up16(sizeof(uint32_t) * total);
-  const size_t b_tw = up16(sizeof(int4) * (n / 2 + 1));
-  std::vector<uint8_t> blob(b_dct + b_cf + b_win + 3 * b_u + b_bf + b_tw + 16, 0);
-  std::vector<T> tmp;
-  if (!host_copy(S->dctCoefs, (size_t)nm * nd, tmp)) { set_error(hipErrorInvalidValue, "mfcc dct"); return false; }
-  memcpy(blob.data(), tmp.data(), sizeof(T) * tmp.size());
-  if (!host_copy(S->filterCoefs, (size_t)total, tmp)) { set_error(hipErrorInvalidValue, "mfcc coefs"); return false; }
-  memcpy(blob.data() + b_dct, tmp.data(), sizeof(T) * tmp.size());
-  if (!host_copy(S->windowCoefs, (size_t)n, tmp)) { set_error(hipErrorInvalidValue, "mfcc window"); return false; }
-  memcpy(blob.data() + b_dct + b_cf, tmp.data(), sizeof(T) * tmp.size());
-  uint8_t* u = blob.data() + b_dct + b_cf + b_win;
-  memcpy(u, pos.data(), sizeof(uint32_t) * nm);
-  memcpy(u + b_u, len.data(), sizeof(uint32_t) * nm);
-  memcpy(u + 2 * b_u, off.data(), sizeof(uint32_t) * nm);
-  uint32_t* bfh = reinterpret_cast<uint32_t*>(u + 3 * b_u);
+  const size_t b_bf = up16(sizeof(uint32_t) * total), b_tw = up16(sizeof(int4) * (n / 2 + 1));
+  blob.resize(lay.end + b_bf + b_tw + 16, 0);
+  uint32_t* bfh = reinterpret_cast<uint32_t*>(blob.data() + lay.end);
   for (uint32_t i = 0, g = 0; i < nm; ++i)
     for (uint32_t j = 0; j < len[i]; ++j) bfh[g++] = ((pos[i] + j) << 16) | i;
   {   // the split's twiddle records (arm_rfft_q31.c:293-326 index 2 * modifier * k)
@@ -485,7 +498,7 @@ bool mfcc_fx_prepare(const Inst* S, MfccFxDev<T>& d) {
       set_error(hipErrorInvalidValue, "mfcc rfft tables");
       return false;
     }
-    int4* twh = reinterpret_cast<int4*>(u + 3 * b_u + b_bf);
+    int4* twh = reinterpret_cast<int4*>(blob.data() + lay.end + b_bf);
     for (uint32_t k = 1; k < n / 2; ++k) {
       const uint32_t c = 2 * mod * k;
       if constexpr (sizeof(T) == 2) {   // q15: packed pairs for v_dot2 (mfcc_fixed_post.hpp mq_split_q15)
@@ -500,15 +513,9 @@ bool mfcc_fx_prepare(const Inst* S, MfccFxDev<T>& d) {
   const uint8_t* dev = (const uint8_t*)device_blob(blob.data(), blob.size());
   d.lut = (const int32_t*)device_table(sqrt_initial_lut_q31, sizeof(int32_t) * 32);
   if (!dev || !d.lut) return false;
-  d.dct = (const T*)dev;
-  d.coefs = (const T*)(dev + b_dct);
-  d.win = (const T*)(dev + b_dct + b_cf);
-  d.pos = (const uint32_t*)(dev + b_dct + b_cf + b_win);
-  d.len = (const uint32_t*)(dev + b_dct + b_cf + b_win + b_u);
-  d.off = (const uint32_t*)(dev + b_dct + b_cf + b_win + 2 * b_u);
-  d.bf = (const uint32_t*)(dev + b_dct + b_cf + b_win + 3 * b_u);
-  d.total = (int)total;
-  d.tw = (const int4*)(dev + b_dct + b_cf + b_win + 3 * b_u + b_bf);
+  mfcc_bind(d, dev, lay);
+  d.bf = (const uint32_t*)(dev + lay.end);
+  d.tw = (const int4*)(dev + lay.end + b_bf);
   return true;
 }
 
@@ -522,7 +529,7 @@ bool mfcc_fx_prepare(const Inst* S, MfccFxDev<T>& d) {
 // workgroups per CU), 0 = three launches (pre, CFFT, post: also every other length
 // and custom bit-reversal tables).
 template <typename T, typename Inst>
-bool mfcc_fx_run(const Inst* S, const MfccFxDev<T>& d, T* x, T* y, T* dst, uint32_t batch, hipStream_t st) {
+bool mfcc_run(const Inst* S, const MfccFxDev<T>& d, T* x, T* y, T* dst, uint32_t batch, hipStream_t st) {
   const int n = (int)S->fftLen, nd = (int)S->nbDctOutputs, nm = (int)S->nbMelFilters;
   // the forward RFFT's inner CFFT (arm_rfft_q31.c:148-183: cfft(L, fwd, bitReverseFlagR), then
   // arm_split_rfft): its tables and bit-reversal mode
@@ -578,13 +585,14 @@ bool mfcc_fx_run(const Inst* S, const MfccFxDev<T>& d, T* x, T* y, T* dst, uint3
   return true;
 }
 
-// FIR coefficients: device pointers in place, host sets through the content-keyed cache
+// Filter coefficients: device pointers in place, host sets through the content-keyed cache
 // (uploaded synchronously once per distinct set, so an asynchronous batch call never
-// shares a staging buffer with a later call on another stream)
+// shares a staging buffer with a later call on another stream).  nullptr: the upload failed,
+// recorded as hipErrorOutOfMemory under `what`.
 template <typename T>
-const T* device_coeffs(const T* c, int n, bool* ok) {
+const T* device_coeffs(const T* c, int n, const char* what) {
   const T* d = (const T*)device_table(c, sizeof(T) * (size_t)n);
-  *ok = d != nullptr;
+  if (!d) set_error(hipErrorOutOfMemory, what);
   return d;
 }
 
@@ -593,25 +601,81 @@ bool ranges_overlap(const void* a, const void* b, size_t bytes) {
   return bytes && x < y + bytes && y < x + bytes;
 }
 
+// ---- drop-in staging of the stateful filters (FIR, multirate, lattice, biquad) ---------------
+// One synchronous call: the thread's stream, the scope that holds the coefficient blob, the
+// coefficients on the device (nullptr: see device_coeffs) and which of the caller's three buffers
+// are device memory.
+template <typename T>
+struct FilterCall {
+  hipStream_t st;
+  BlobScope hold;
+  const T* dc;
+  bool dstate, dsrc, ddst;
+  FilterCall(const T* pCoeffs, int ncoef, const void* pState, const void* pSrc, const void* pDst, const char* what)
+      : st(sync_stream()), hold(st), dc(device_coeffs(pCoeffs, ncoef, what)), dstate(is_device_ptr(pState)),
+        dsrc(is_device_ptr(pSrc)), ddst(is_device_ptr(pDst)) {}
+};
+
+// The call's DMA path.  pState (hb bytes of ST words), pSrc (sb bytes) and pDst (ob bytes) lie each
+// on the host or the device; host ones are staged through scratch slots 2, 3 and 4: state in, src
+// in, run(dc, src, dst, state, st), dst out, state out.
+// in_state: the block input is part of the state, [history (hb) ; block (sb)] (FIR, decimator,
+// interpolator).  The reference copies each input into pState before it writes pDst
+// (arm_fir_f32.c:947-975), so after the call the state holds [new history ; block input], and a
+// device pSrc overlapping pDst is filtered from a copy of the input, which also feeds the new
+// history and that tail.
+// what_scratch: arm_fir names its scratch failure apart from its other errors.
+template <typename T, typename ST, typename Run>
+void filter_sync(FilterCall<T>& c, ST* pState, size_t hb, const T* pSrc, size_t sb, T* pDst, size_t ob, bool in_state,
+                 const char* what, Run&& run, const char* what_scratch = nullptr) {
+  hipStream_t st = c.st;
+  const bool alias = in_state && c.dsrc && c.ddst && ranges_overlap(pSrc, pDst, std::max(sb, ob));
+  ST* dhist = c.dstate ? pState : (ST*)scratch(hb + 16, 2);
+  const T* dsr = (c.dsrc && !alias) ? pSrc : (const T*)scratch(sb + 16, 3);
+  T* dds = c.ddst ? pDst : (T*)scratch(ob + 16, 4);
+  if (!dhist || !dsr || !dds) { set_error(hipErrorOutOfMemory, what_scratch ? what_scratch : what); return; }
+  HostIO io(st);
+  hipError_t e = hipSuccess;
+  if (!c.dstate && hb > 0) e = io.in(dhist, pState, hb);
+  if (e == hipSuccess && alias) e = hipMemcpyAsync((void*)dsr, pSrc, sb, hipMemcpyDeviceToDevice, st);
+  else if (e == hipSuccess && !c.dsrc) e = io.in((void*)dsr, pSrc, sb);
+  if (e == hipSuccess) e = run(c.dc, dsr, dds, dhist, st);
+  if (e == hipSuccess && !c.ddst && ob) e = io.out(pDst, dds, ob);
+  if (e == hipSuccess && !c.dstate && hb > 0) e = io.out(pState, dhist, hb);
+  if (e == hipSuccess && in_state) {
+    void* tail = (uint8_t*)pState + hb;
+    if (c.dstate) e = hipMemcpyAsync(tail, dsr, sb, hipMemcpyDeviceToDevice, st);
+    else if (c.dsrc) e = io.out(tail, dsr, sb);
+    else memcpy(tail, pSrc, sb);               // host input, host state: the caller's words
+  }
+  if (e == hipSuccess) e = io.finish();
+  if (e == hipSuccess) c.hold.synced();
+  if (e != hipSuccess) set_error(e, what);
+}
+
+// the whole call, for the families with no path in front of the DMA one
+template <typename T, typename ST, typename Run>
+void filter_sync(const T* pCoeffs, int ncoef, ST* pState, size_t hb, const T* pSrc, size_t sb, T* pDst, size_t ob,
+                 bool in_state, const char* what, Run&& run) {
+  FilterCall<T> c(pCoeffs, ncoef, pState, pSrc, pDst, what);
+  if (c.dc) filter_sync(c, pState, hb, pSrc, sb, pDst, ob, in_state, what, run);
+}
+
 // drop-in FIR: state = [history(T-1) ; block(B)] on host or device (arm_fir_f32.c:911-1280).
 // After the call the state holds [new history ; block input], as the reference leaves it.
 template <typename T, typename Inst>
 void fir_sync(const Inst* S, const T* pSrc, T* pDst, uint32_t B, int kind) {
   if (!S || !S->pState || !S->pCoeffs || S->numTaps == 0 || B == 0) return;
   const int taps = S->numTaps, T1 = taps - 1;
-  hipStream_t st = sync_stream();
-  BlobScope hold(st);
-  bool ok = true;
-  const T* dc = device_coeffs<T>(S->pCoeffs, taps, &ok);
-  if (!ok) { set_error(hipErrorOutOfMemory, "arm_fir coeffs"); return; }
-  const bool dstate = is_device_ptr(S->pState), dsrc = is_device_ptr(pSrc), ddst = is_device_ptr(pDst);
+  FilterCall<T> c(S->pCoeffs, taps, S->pState, pSrc, pDst, "arm_fir coeffs");
+  if (!c.dc) return;
   const size_t sb = sizeof(T) * (size_t)B, hb = sizeof(T) * (size_t)T1;
-  if (!dstate && !dsrc && !ddst && hb + sb <= kZeroCopyMax) {
+  if (!c.dstate && !c.dsrc && !c.ddst && hb + sb <= kZeroCopyMax) {
     // all host, small: the caller's state buffer itself, [history ; block], staged as one
     // coherent pinned copy the kernels use in place (the filter reads it, the history kernel
     // rewrites its head), so after finish() it holds [new history ; block input] exactly as the
     // reference leaves pState; outputs likewise -- two launches, no DMA
-    HostIO io(st);
+    HostIO io(c.st);
     T* zs = (T*)io.zinout(S->pState, hb + sb);
     T* zd = (T*)io.zout(pDst, sb);
     if (!zs || !zd) { set_error(hipErrorOutOfMemory, "arm_fir staging"); return; }
@@ -620,37 +684,17 @@ void fir_sync(const Inst* S, const T* pSrc, T* pDst, uint32_t B, int kind) {
     uint32_t seq = 0;
     bool flagged = false;                         // the filter's workgroup wrote the completion word
     if (!done_slot(&done, &seq)) done = nullptr;
-    hipError_t e = fir_run(kind, dc, taps, zs + T1, zd, B, 1, zs, st, done, seq, &flagged);
+    hipError_t e = fir_run(kind, c.dc, taps, zs + T1, zd, B, 1, zs, c.st, done, seq, &flagged);
     if (e == hipSuccess) e = io.finish(flagged ? seq : 0);
-    if (e == hipSuccess) hold.synced();
+    if (e == hipSuccess) c.hold.synced();
     if (e != hipSuccess) set_error(e, "arm_fir");
     return;
   }
-  // in place on the device (pSrc overlapping pDst): filter from a copy of the input, which
-  // also feeds the new history and the state tail (the reference copies each input into
-  // pState before writing pDst, arm_fir_f32.c:947-975)
-  const bool alias = dsrc && ddst && ranges_overlap(pSrc, pDst, sb);
-  T* dhist = dstate ? S->pState : (T*)scratch(hb + 16, 2);
-  const T* dsr = (dsrc && !alias) ? pSrc : (const T*)scratch(sb, 3);
-  T* dds = ddst ? pDst : (T*)scratch(sb, 4);
-  if (!dhist || !dsr || !dds) { set_error(hipErrorOutOfMemory, "arm_fir scratch"); return; }
-  HostIO io(st);
-  hipError_t e = hipSuccess;
-  if (!dstate && T1 > 0) e = io.in(dhist, S->pState, hb);
-  if (e == hipSuccess && alias) e = hipMemcpyAsync((void*)dsr, pSrc, sb, hipMemcpyDeviceToDevice, st);
-  else if (e == hipSuccess && !dsrc) e = io.in((void*)dsr, pSrc, sb);
-  if (e == hipSuccess) e = fir_run(kind, dc, taps, dsr, dds, B, 1, dhist, st);
-  if (e == hipSuccess && !ddst) e = io.out(pDst, dds, sb);
-  if (e == hipSuccess && !dstate && T1 > 0) e = io.out(S->pState, dhist, hb);
-  // state tail keeps the block input (the reference copies it there, :947-975)
-  if (e == hipSuccess) {
-    if (dstate) e = hipMemcpyAsync(S->pState + T1, dsr, sb, hipMemcpyDeviceToDevice, st);
-    else if (dsrc) e = io.out(S->pState + T1, dsr, sb);
-    else memcpy(S->pState + T1, pSrc, sb);     // host input, host state: the caller's words
-  }
-  if (e == hipSuccess) e = io.finish();
-  if (e == hipSuccess) hold.synced();
-  if (e != hipSuccess) set_error(e, "arm_fir");
+  filter_sync(c, S->pState, hb, pSrc, sb, pDst, sb, true, "arm_fir",
+              [&](const T* dc, const T* src, T* dst, T* hist, hipStream_t st) {
+                return fir_run(kind, dc, taps, src, dst, B, 1, hist, st);
+              },
+              "arm_fir scratch");
 }
 
 template <typename T, typename Inst>
@@ -660,12 +704,9 @@ arm_status fir_batch(const Inst* S, const T* d_src, T* d_dst, uint32_t B, uint32
   if (S->numTaps > 1 && batch && !d_hist) return ARM_MATH_ARGUMENT_ERROR;
   hipStream_t st = (hipStream_t)stream;
   BlobScope hold(st);
-  bool ok = true;
-  const T* dc = device_coeffs<T>(S->pCoeffs, S->numTaps, &ok);
-  if (!ok) { set_error(hipErrorOutOfMemory, "arm_fir_batch coeffs"); return ARM_MATH_ARGUMENT_ERROR; }
-  hipError_t e = fir_run(kind, dc, S->numTaps, d_src, d_dst, B, batch, d_hist, st);
-  if (e != hipSuccess) { set_error(e, "arm_fir_batch"); return ARM_MATH_ARGUMENT_ERROR; }
-  return ARM_MATH_SUCCESS;
+  const T* dc = device_coeffs<T>(S->pCoeffs, S->numTaps, "arm_fir_batch coeffs");
+  if (!dc) return ARM_MATH_ARGUMENT_ERROR;
+  return batch_status(fir_run(kind, dc, S->numTaps, d_src, d_dst, B, batch, d_hist, st), "arm_fir_batch");
 }
 
 // multi-GPU FIR (the batch is sliced by filter, each shard's history rows stay on
@@ -678,9 +719,8 @@ arm_status fir_batch_multi(const Inst* S, uint32_t nshards, const int* devices, 
   for (uint32_t s = 0; s < nshards; ++s)
     if (batch[s] && ((B && (!d_src[s] || !d_dst[s])) || (S->numTaps > 1 && !d_hist[s]))) return ARM_MATH_ARGUMENT_ERROR;
   return run_multi(nshards, devices, batch, "arm_fir_batch_multi", [&](uint32_t s, hipStream_t st) {
-    bool ok = true;
-    const T* dc = device_coeffs<T>(S->pCoeffs, S->numTaps, &ok);   // uploaded once per device
-    if (!ok) return false;
+    const T* dc = device_coeffs<T>(S->pCoeffs, S->numTaps, "arm_fir_batch_multi");   // uploaded once per device
+    if (!dc) return false;
     hipError_t e = fir_run(kind, dc, S->numTaps, d_src[s], d_dst[s], B, batch[s], d_hist[s], st);
     if (e != hipSuccess) { set_error(e, "arm_fir_batch_multi"); return false; }
     return true;
@@ -700,41 +740,7 @@ void zero_words(void* p, size_t bytes, const char* what) {
 // ---- multirate FIR (decimator / interpolator) ----------------------------------------
 // Drop-in: state = [history (H) ; block (B)] on host or device; after the call it holds
 // [new history ; block input], as the reference leaves it (the block is copied into pState
-// before the pass, arm_fir_decimate_f32.c / arm_fir_interpolate_f32.c).  run(dc, src, dst,
-// hist, st) launches the batched pass for one stream.
-template <typename T, typename Run>
-void mr_sync(T* pState, const T* pCoeffs, int ncoef, int H, const T* pSrc, T* pDst, uint32_t B, size_t out_words,
-             const char* what, Run&& run) {
-  if (!pState || !pCoeffs || ncoef <= 0 || B == 0) return;
-  hipStream_t st = sync_stream();
-  BlobScope hold(st);
-  bool ok = true;
-  const T* dc = device_coeffs<T>(pCoeffs, ncoef, &ok);
-  if (!ok) { set_error(hipErrorOutOfMemory, what); return; }
-  const bool dstate = is_device_ptr(pState), dsrc = is_device_ptr(pSrc), ddst = is_device_ptr(pDst);
-  const size_t sb = sizeof(T) * (size_t)B, hb = sizeof(T) * (size_t)H, ob = sizeof(T) * out_words;
-  const bool alias = dsrc && ddst && ranges_overlap(pSrc, pDst, sb > ob ? sb : ob);
-  T* dhist = dstate ? pState : (T*)scratch(hb + 16, 2);
-  const T* dsr = (dsrc && !alias) ? pSrc : (const T*)scratch(sb, 3);
-  T* dds = ddst ? pDst : (T*)scratch(ob + 16, 4);
-  if (!dhist || !dsr || !dds) { set_error(hipErrorOutOfMemory, what); return; }
-  HostIO io(st);
-  hipError_t e = hipSuccess;
-  if (!dstate && H > 0) e = io.in(dhist, pState, hb);
-  if (e == hipSuccess && alias) e = hipMemcpyAsync((void*)dsr, pSrc, sb, hipMemcpyDeviceToDevice, st);
-  else if (e == hipSuccess && !dsrc) e = io.in((void*)dsr, pSrc, sb);
-  if (e == hipSuccess) e = run(dc, dsr, dds, dhist, st);
-  if (e == hipSuccess && !ddst && ob) e = io.out(pDst, dds, ob);
-  if (e == hipSuccess && !dstate && H > 0) e = io.out(pState, dhist, hb);
-  if (e == hipSuccess) {
-    if (dstate) e = hipMemcpyAsync(pState + H, dsr, sb, hipMemcpyDeviceToDevice, st);
-    else if (dsrc) e = io.out(pState + H, dsr, sb);
-    else memcpy(pState + H, pSrc, sb);
-  }
-  if (e == hipSuccess) e = io.finish();
-  if (e != hipSuccess) set_error(e, what);
-}
-
+// before the pass, arm_fir_decimate_f32.c / arm_fir_interpolate_f32.c): filter_sync's in_state.
 template <typename T, typename Inst>
 arm_status decimate_init(Inst* S, uint16_t numTaps, uint8_t M, const T* pCoeffs, T* pState, uint32_t blockSize) {
   if (!S) return ARM_MATH_ARGUMENT_ERROR;
@@ -753,21 +759,23 @@ arm_status interpolate_init(Inst* S, uint8_t L, uint16_t numTaps, const T* pCoef
 }
 template <typename T, typename Inst>
 void decimate_sync(const Inst* S, const T* pSrc, T* pDst, uint32_t B, int op, const char* what) {
-  if (!S || S->M == 0 || S->numTaps == 0) return;
+  if (!S || S->M == 0 || S->numTaps == 0 || !S->pState || !S->pCoeffs || B == 0) return;
   const int M = S->M, taps = S->numTaps;
-  mr_sync<T>(S->pState, S->pCoeffs, taps, taps - 1, pSrc, pDst, B, B / M, what,
-             [&](const T* dc, const T* src, T* dst, T* hist, hipStream_t st) {
-               return fir_decimate_run(op, dc, taps, M, src, dst, B, 1, hist, st);
-             });
+  filter_sync(S->pCoeffs, taps, S->pState, sizeof(T) * (size_t)(taps - 1), pSrc, sizeof(T) * (size_t)B, pDst,
+              sizeof(T) * (size_t)(B / M), true, what,
+              [&](const T* dc, const T* src, T* dst, T* hist, hipStream_t st) {
+                return fir_decimate_run(op, dc, taps, M, src, dst, B, 1, hist, st);
+              });
 }
 template <typename T, typename Inst>
 void interpolate_sync(const Inst* S, const T* pSrc, T* pDst, uint32_t B, int op, const char* what) {
-  if (!S || S->L == 0 || S->phaseLength == 0) return;
+  if (!S || S->L == 0 || S->phaseLength == 0 || !S->pState || !S->pCoeffs || B == 0) return;
   const int L = S->L, P = S->phaseLength;
-  mr_sync<T>(S->pState, S->pCoeffs, L * P, P - 1, pSrc, pDst, B, (size_t)B * L, what,
-             [&](const T* dc, const T* src, T* dst, T* hist, hipStream_t st) {
-               return fir_interpolate_run(op, dc, L, P, src, dst, B, 1, hist, st);
-             });
+  filter_sync(S->pCoeffs, L * P, S->pState, sizeof(T) * (size_t)(P - 1), pSrc, sizeof(T) * (size_t)B, pDst,
+              sizeof(T) * (size_t)B * L, true, what,
+              [&](const T* dc, const T* src, T* dst, T* hist, hipStream_t st) {
+                return fir_interpolate_run(op, dc, L, P, src, dst, B, 1, hist, st);
+              });
 }
 template <typename T, typename Inst>
 arm_status decimate_batch(const Inst* S, const T* d_src, T* d_dst, uint32_t B, uint32_t batch, T* d_hist,
@@ -775,12 +783,10 @@ arm_status decimate_batch(const Inst* S, const T* d_src, T* d_dst, uint32_t B, u
   if (!S || !S->pCoeffs || S->numTaps == 0 || S->M == 0) return ARM_MATH_ARGUMENT_ERROR;
   if (batch && B && (!d_src || (B >= S->M && !d_dst) || (S->numTaps > 1 && !d_hist))) return ARM_MATH_ARGUMENT_ERROR;
   BlobScope hold((hipStream_t)stream);
-  bool ok = true;
-  const T* dc = device_coeffs<T>(S->pCoeffs, S->numTaps, &ok);
-  if (!ok) { set_error(hipErrorOutOfMemory, what); return ARM_MATH_ARGUMENT_ERROR; }
-  hipError_t e = fir_decimate_run(op, dc, S->numTaps, S->M, d_src, d_dst, B, batch, d_hist, (hipStream_t)stream);
-  if (e != hipSuccess) { set_error(e, what); return ARM_MATH_ARGUMENT_ERROR; }
-  return ARM_MATH_SUCCESS;
+  const T* dc = device_coeffs<T>(S->pCoeffs, S->numTaps, what);
+  if (!dc) return ARM_MATH_ARGUMENT_ERROR;
+  return batch_status(fir_decimate_run(op, dc, S->numTaps, S->M, d_src, d_dst, B, batch, d_hist, (hipStream_t)stream),
+                      what);
 }
 template <typename T, typename Inst>
 arm_status interpolate_batch(const Inst* S, const T* d_src, T* d_dst, uint32_t B, uint32_t batch, T* d_hist,
@@ -788,13 +794,11 @@ arm_status interpolate_batch(const Inst* S, const T* d_src, T* d_dst, uint32_t B
   if (!S || !S->pCoeffs || S->phaseLength == 0 || S->L == 0) return ARM_MATH_ARGUMENT_ERROR;
   if (batch && B && (!d_src || !d_dst || (S->phaseLength > 1 && !d_hist))) return ARM_MATH_ARGUMENT_ERROR;
   BlobScope hold((hipStream_t)stream);
-  bool ok = true;
-  const T* dc = device_coeffs<T>(S->pCoeffs, (int)S->L * S->phaseLength, &ok);
-  if (!ok) { set_error(hipErrorOutOfMemory, what); return ARM_MATH_ARGUMENT_ERROR; }
-  hipError_t e = fir_interpolate_run(op, dc, S->L, S->phaseLength, d_src, d_dst, B, batch, d_hist,
-                                     (hipStream_t)stream);
-  if (e != hipSuccess) { set_error(e, what); return ARM_MATH_ARGUMENT_ERROR; }
-  return ARM_MATH_SUCCESS;
+  const T* dc = device_coeffs<T>(S->pCoeffs, (int)S->L * S->phaseLength, what);
+  if (!dc) return ARM_MATH_ARGUMENT_ERROR;
+  return batch_status(fir_interpolate_run(op, dc, S->L, S->phaseLength, d_src, d_dst, B, batch, d_hist,
+                                          (hipStream_t)stream),
+                      what);
 }
 
 // ---- sparse FIR ---------------------------------------------------------------------------
@@ -820,10 +824,9 @@ void sparse_sync(Inst* S, const T* pSrc, T* pDst, uint32_t B, int op, const char
   const uint32_t L = (uint32_t)S->maxDelay + B;
   hipStream_t st = sync_stream();
   BlobScope hold(st);
-  bool ok = true, okd = true;
-  const T* dc = device_coeffs<T>(S->pCoeffs, taps, &ok);
-  const int32_t* dd = device_coeffs<int32_t>(S->pTapDelay, taps, &okd);
-  if (!ok || !okd) { set_error(hipErrorOutOfMemory, what); return; }
+  const T* dc = device_coeffs<T>(S->pCoeffs, taps, what);
+  const int32_t* dd = device_coeffs<int32_t>(S->pTapDelay, taps, what);
+  if (!dc || !dd) return;
   const bool dstate = is_device_ptr(S->pState), dsrc = is_device_ptr(pSrc), ddst = is_device_ptr(pDst);
   // words moved: the circular length, or up to a stateIndex a larger earlier block left past it
   const size_t es = sizeof(T), sb = es * B, lb = es * std::max<size_t>(L, (size_t)S->stateIndex + 1);
@@ -884,14 +887,12 @@ arm_status sparse_batch(const Inst* S, const T* d_src, T* d_dst, uint32_t B, uin
   if (!S || !S->pCoeffs || !S->pTapDelay || S->numTaps == 0) return ARM_MATH_ARGUMENT_ERROR;
   if (batch && B && (!d_src || !d_dst || (S->maxDelay > 0 && !d_hist))) return ARM_MATH_ARGUMENT_ERROR;
   BlobScope hold((hipStream_t)stream);
-  bool ok = true, okd = true;
-  const T* dc = device_coeffs<T>(S->pCoeffs, S->numTaps, &ok);
-  const int32_t* dd = device_coeffs<int32_t>(S->pTapDelay, S->numTaps, &okd);
-  if (!ok || !okd) { set_error(hipErrorOutOfMemory, what); return ARM_MATH_ARGUMENT_ERROR; }
-  hipError_t e = fir_sparse_run(op, dc, dd, S->numTaps, S->maxDelay, d_src, d_dst, B, batch, d_hist, 0, 0,
-                                (hipStream_t)stream);
-  if (e != hipSuccess) { set_error(e, what); return ARM_MATH_ARGUMENT_ERROR; }
-  return ARM_MATH_SUCCESS;
+  const T* dc = device_coeffs<T>(S->pCoeffs, S->numTaps, what);
+  const int32_t* dd = device_coeffs<int32_t>(S->pTapDelay, S->numTaps, what);
+  if (!dc || !dd) return ARM_MATH_ARGUMENT_ERROR;
+  return batch_status(fir_sparse_run(op, dc, dd, S->numTaps, S->maxDelay, d_src, d_dst, B, batch, d_hist, 0, 0,
+                                     (hipStream_t)stream),
+                      what);
 }
 
 // ---- FIR lattice ----------------------------------------------------------------------------
@@ -908,26 +909,11 @@ template <typename T, typename Inst>
 void lattice_sync(const Inst* S, const T* pSrc, T* pDst, uint32_t B, int op, const char* what) {
   if (!S || !S->pState || !S->pCoeffs || S->numStages == 0 || B == 0) return;
   const int M = S->numStages;
-  hipStream_t st = sync_stream();
-  BlobScope hold(st);
-  bool ok = true;
-  const T* dc = device_coeffs<T>(S->pCoeffs, M, &ok);
-  if (!ok) { set_error(hipErrorOutOfMemory, what); return; }
-  const bool dstate = is_device_ptr(S->pState), dsrc = is_device_ptr(pSrc), ddst = is_device_ptr(pDst);
-  const size_t sb = sizeof(T) * (size_t)B, hb = sizeof(T) * (size_t)M;
-  T* dhist = dstate ? S->pState : (T*)scratch(hb + 16, 2);
-  const T* dsr = dsrc ? pSrc : (const T*)scratch(sb, 3);
-  T* dds = ddst ? pDst : (T*)scratch(sb + 16, 4);
-  if (!dhist || !dsr || !dds) { set_error(hipErrorOutOfMemory, what); return; }
-  HostIO io(st);
-  hipError_t e = hipSuccess;
-  if (!dstate) e = io.in(dhist, S->pState, hb);
-  if (e == hipSuccess && !dsrc) e = io.in((void*)dsr, pSrc, sb);
-  if (e == hipSuccess) e = fir_lattice_run(op, dc, M, dsr, dds, B, 1, dhist, st);
-  if (e == hipSuccess && !ddst) e = io.out(pDst, dds, sb);
-  if (e == hipSuccess && !dstate) e = io.out(S->pState, dhist, hb);
-  if (e == hipSuccess) e = io.finish();
-  if (e != hipSuccess) set_error(e, what);
+  const size_t sb = sizeof(T) * (size_t)B;
+  filter_sync(S->pCoeffs, M, S->pState, sizeof(T) * (size_t)M, pSrc, sb, pDst, sb, false, what,
+              [&](const T* dc, const T* src, T* dst, T* state, hipStream_t st) {
+                return fir_lattice_run(op, dc, M, src, dst, B, 1, state, st);
+              });
 }
 
 template <typename T, typename Inst>
@@ -936,12 +922,9 @@ arm_status lattice_batch(const Inst* S, const T* d_src, T* d_dst, uint32_t B, ui
   if (!S || !S->pCoeffs || S->numStages == 0) return ARM_MATH_ARGUMENT_ERROR;
   if (batch && B && (!d_src || !d_dst || !d_state)) return ARM_MATH_ARGUMENT_ERROR;
   BlobScope hold((hipStream_t)stream);
-  bool ok = true;
-  const T* dc = device_coeffs<T>(S->pCoeffs, S->numStages, &ok);
-  if (!ok) { set_error(hipErrorOutOfMemory, what); return ARM_MATH_ARGUMENT_ERROR; }
-  hipError_t e = fir_lattice_run(op, dc, S->numStages, d_src, d_dst, B, batch, d_state, (hipStream_t)stream);
-  if (e != hipSuccess) { set_error(e, what); return ARM_MATH_ARGUMENT_ERROR; }
-  return ARM_MATH_SUCCESS;
+  const T* dc = device_coeffs<T>(S->pCoeffs, S->numStages, what);
+  if (!dc) return ARM_MATH_ARGUMENT_ERROR;
+  return batch_status(fir_lattice_run(op, dc, S->numStages, d_src, d_dst, B, batch, d_state, (hipStream_t)stream), what);
 }
 
 // ---- biquad cascades ------------------------------------------------------------------------
@@ -960,26 +943,11 @@ void biquad_sync(const Inst* S, int ps, const T* pSrc, T* pDst, uint32_t B, int 
                  const char* what) {
   if (!S || !S->pState || !S->pCoeffs || !pSrc || !pDst || S->numStages <= 0 || B == 0) return;
   const uint32_t M = (uint32_t)S->numStages;
-  hipStream_t st = sync_stream();
-  BlobScope hold(st);
-  bool ok = true;
-  const T* dc = device_coeffs<T>(S->pCoeffs, (int)(M * nc), &ok);
-  if (!ok) { set_error(hipErrorOutOfMemory, what); return; }
-  const bool dstate = is_device_ptr(S->pState), dsrc = is_device_ptr(pSrc), ddst = is_device_ptr(pDst);
-  const size_t sb = sizeof(T) * (size_t)B * ch, hb = sizeof(ST) * (size_t)M * ks;
-  ST* dhist = dstate ? S->pState : (ST*)scratch(hb + 16, 2);
-  const T* dsr = dsrc ? pSrc : (const T*)scratch(sb, 3);
-  T* dds = ddst ? pDst : (T*)scratch(sb + 16, 4);
-  if (!dhist || !dsr || !dds) { set_error(hipErrorOutOfMemory, what); return; }
-  HostIO io(st);
-  hipError_t e = hipSuccess;
-  if (!dstate) e = io.in(dhist, S->pState, hb);
-  if (e == hipSuccess && !dsrc) e = io.in((void*)dsr, pSrc, sb);
-  if (e == hipSuccess) e = biquad_run(op, dc, M, ps, dsr, dds, B, 1, dhist, st);
-  if (e == hipSuccess && !ddst) e = io.out(pDst, dds, sb);
-  if (e == hipSuccess && !dstate) e = io.out(S->pState, dhist, hb);
-  if (e == hipSuccess) e = io.finish();
-  if (e != hipSuccess) set_error(e, what);
+  const size_t sb = sizeof(T) * (size_t)B * ch;
+  filter_sync(S->pCoeffs, (int)(M * nc), S->pState, sizeof(ST) * (size_t)M * ks, pSrc, sb, pDst, sb, false, what,
+              [&](const T* dc, const T* src, T* dst, ST* state, hipStream_t st) {
+                return biquad_run(op, dc, M, ps, src, dst, B, 1, state, st);
+              });
 }
 
 template <typename T, typename ST, typename Inst>
@@ -989,12 +957,9 @@ arm_status biquad_batch(const Inst* S, int ps, const T* d_src, T* d_dst, uint32_
   if (!batch || !B) return ARM_MATH_SUCCESS;
   const uint32_t M = (uint32_t)S->numStages;
   BlobScope hold((hipStream_t)stream);
-  bool ok = true;
-  const T* dc = device_coeffs<T>(S->pCoeffs, (int)(M * nc), &ok);
-  if (!ok) { set_error(hipErrorOutOfMemory, what); return ARM_MATH_ARGUMENT_ERROR; }
-  hipError_t e = biquad_run(op, dc, M, ps, d_src, d_dst, B, batch, d_state, (hipStream_t)stream);
-  if (e != hipSuccess) { set_error(e, what); return ARM_MATH_ARGUMENT_ERROR; }
-  return ARM_MATH_SUCCESS;
+  const T* dc = device_coeffs<T>(S->pCoeffs, (int)(M * nc), what);
+  if (!dc) return ARM_MATH_ARGUMENT_ERROR;
+  return batch_status(biquad_run(op, dc, M, ps, d_src, d_dst, B, batch, d_state, (hipStream_t)stream), what);
 }
 
 // ---- convolution / correlation family ------------------------------------------------
@@ -1076,9 +1041,7 @@ arm_status conv_family_batch(int op, int variant, const T* a, uint32_t alen, uin
   if (variant == kVarPartial) { j.sy = num; j.yoff = -(int64_t)first; }
   else if (variant == kVarCorr) j.sy = 2ull * (alen > blen ? alen : blen) - 1;
   else j.sy = (uint64_t)alen + blen - 1;
-  hipError_t e = conv_family_run(j, (hipStream_t)stream);
-  if (e != hipSuccess) { set_error(e, what); return ARM_MATH_ARGUMENT_ERROR; }
-  return ARM_MATH_SUCCESS;
+  return batch_status(conv_family_run(j, (hipStream_t)stream), what);
 }
 
 bool partial_range_ok(uint32_t alen, uint32_t blen, uint32_t first, uint32_t num) {
@@ -1108,9 +1071,9 @@ arm_status mat_batch_multi(const M* pSrcA, const M* pSrcB, M* pDst, uint32_t nsh
   });
 }
 
-// drop-in fixed-point matrix multiply (host or device operands), synchronous
-template <typename T, typename M>
-arm_status mat_mult_fixed_sync(const M* pSrcA, const M* pSrcB, M* pDst, bool fast = false) {
+// drop-in matrix multiply (host or device operands), synchronous; launch as for mat_batch_multi
+template <typename T, typename M, typename Launch>
+arm_status mat_mult_sync(const M* pSrcA, const M* pSrcB, M* pDst, const char* what, Launch&& launch) {
   if (!pSrcA || !pSrcB || !pDst) return ARM_MATH_ARGUMENT_ERROR;
   if (!mat_shapes_ok(pSrcA, pSrcB, pDst)) return ARM_MATH_SIZE_MISMATCH;
   const int m = pSrcA->numRows, k = pSrcA->numCols, n = pSrcB->numCols;
@@ -1125,18 +1088,21 @@ arm_status mat_mult_fixed_sync(const M* pSrcA, const M* pSrcB, M* pDst, bool fas
   hipError_t e = hipSuccess;
   if (!da) e = io.in(A, pSrcA->pData, ab);
   if (e == hipSuccess && !db) e = io.in(B, pSrcB->pData, bb);
-  if (e == hipSuccess) {
-    if constexpr (sizeof(T) == 1)
-      e = mat_mult_q7_launch(m, k, n, A, B, Cd, 1, st);
-    else if constexpr (sizeof(T) == 2)
-      e = fast ? mat_mult_fast_q15_launch(m, k, n, A, B, Cd, 1, st) : mat_mult_q15_launch(m, k, n, A, B, Cd, 1, st);
-    else
-      e = fast ? mat_mult_fast_q31_launch(m, k, n, A, B, Cd, 1, st) : mat_mult_q31_launch(m, k, n, A, B, Cd, 1, st);
-  }
+  if (e == hipSuccess) e = launch(m, k, n, A, B, Cd, 1, st);
   if (e == hipSuccess && !dc) e = io.out(pDst->pData, Cd, cb);
   if (e == hipSuccess) e = io.finish();
-  if (e != hipSuccess) { set_error(e, "arm_mat_mult"); return ARM_MATH_ARGUMENT_ERROR; }
-  return ARM_MATH_SUCCESS;
+  return batch_status(e, what);
+}
+
+// batched device API: `batch` contiguous matrices at the instances' pData
+template <typename M, typename Launch>
+arm_status mat_batch(const M* pSrcA, const M* pSrcB, M* pDst, uint32_t batch, void* stream, const char* what,
+                     Launch&& launch) {
+  if (!pSrcA || !pSrcB || !pDst) return ARM_MATH_ARGUMENT_ERROR;
+  if (!mat_shapes_ok(pSrcA, pSrcB, pDst)) return ARM_MATH_SIZE_MISMATCH;
+  return batch_status(launch(pSrcA->numRows, pSrcA->numCols, pSrcB->numCols, pSrcA->pData, pSrcB->pData, pDst->pData,
+                             batch, (hipStream_t)stream),
+                      what);
 }
 
 // FIR init: zero numTaps + blockSize - 1 state words (arm_fir_init_f32.c:74-95,
@@ -1147,14 +1113,44 @@ void fir_init(Inst* S, uint16_t numTaps, const T* pCoeffs, T* pState, uint32_t b
   S->numTaps = numTaps;
   S->pCoeffs = pCoeffs;
   S->pState = pState;
-  if (!pState) return;
-  const size_t bytes = sizeof(T) * ((size_t)numTaps + blockSize - 1);
-  if (is_device_ptr(pState)) {
-    hipError_t e = hipMemset(pState, 0, bytes);
-    if (e != hipSuccess) set_error(e, "arm_fir_init");
-  } else {
-    memset(pState, 0, bytes);
-  }
+  if (pState) zero_words(pState, sizeof(T) * ((size_t)numTaps + blockSize - 1), "arm_fir_init");
+}
+
+// ---- MFCC drop-in and batched calls, f32 (Dev = MfccDev<float>) and q31 / q15 (MfccFxDev<T>) ----
+// Drop-in: work space lives on the device; the reference's pSrc / pTmp work contents are not
+// reproduced.
+template <typename Dev, typename T, typename Inst>
+arm_status mfcc_sync(const Inst* S, T* pSrc, T* pDst, const char* what) {
+  if (!S || !pSrc || !pDst) return ARM_MATH_ARGUMENT_ERROR;
+  if (S->nbDctOutputs == 0) return ARM_MATH_SUCCESS;
+  hipStream_t st = sync_stream();
+  BlobScope hold(st);
+  Dev d;
+  if (!mfcc_prepare(S, d)) return ARM_MATH_ARGUMENT_ERROR;
+  const uint32_t n = S->fftLen, nd = S->nbDctOutputs;
+  T* x = (T*)scratch(sizeof(T) * n, 0);
+  T* y = (T*)scratch(sizeof(T) * 2 * n, 1);
+  const bool ddst = is_device_ptr(pDst);
+  T* o = ddst ? pDst : (T*)scratch(sizeof(T) * nd, 2);
+  if (!x || !y || !o) { set_error(hipErrorOutOfMemory, what); return ARM_MATH_ARGUMENT_ERROR; }
+  HostIO io(st);
+  hipError_t e = is_device_ptr(pSrc) ? hipMemcpyAsync(x, pSrc, sizeof(T) * n, hipMemcpyDeviceToDevice, st)
+                                     : io.in(x, pSrc, sizeof(T) * n);
+  if (e != hipSuccess) { set_error(e, what); return ARM_MATH_ARGUMENT_ERROR; }
+  if (!mfcc_run(S, d, x, y, o, 1, st)) { (void)hipStreamSynchronize(st); return ARM_MATH_ARGUMENT_ERROR; }
+  if (!ddst) e = io.out(pDst, o, sizeof(T) * nd);
+  if (e == hipSuccess) e = io.finish();
+  return batch_status(e, what);
+}
+
+template <typename Dev, typename T, typename Inst>
+arm_status mfcc_batch(const Inst* S, T* d_src, T* d_dst, T* d_tmp, uint32_t batch, void* stream) {
+  if (!S || (batch && (!d_src || !d_dst || !d_tmp))) return ARM_MATH_ARGUMENT_ERROR;
+  if (batch == 0 || S->nbDctOutputs == 0) return ARM_MATH_SUCCESS;
+  BlobScope hold((hipStream_t)stream);
+  Dev d;
+  if (!mfcc_prepare(S, d)) return ARM_MATH_ARGUMENT_ERROR;
+  return mfcc_run(S, d, d_src, d_tmp, d_dst, batch, (hipStream_t)stream) ? ARM_MATH_SUCCESS : ARM_MATH_ARGUMENT_ERROR;
 }
 }  // namespace
 
@@ -1376,126 +1372,37 @@ arm_status arm_mat_mult_q31_batch_multi(const arm_matrix_instance_q31* pSrcA, co
 
 arm_status arm_mat_mult_f32(const arm_matrix_instance_f32* pSrcA, const arm_matrix_instance_f32* pSrcB,
                             arm_matrix_instance_f32* pDst) {
-  if (!pSrcA || !pSrcB || !pDst) return ARM_MATH_ARGUMENT_ERROR;
-  if (!mat_shapes_ok(pSrcA, pSrcB, pDst)) return ARM_MATH_SIZE_MISMATCH;
-  const int m = pSrcA->numRows, k = pSrcA->numCols, n = pSrcB->numCols;
-  const size_t ab = sizeof(float) * (size_t)m * k, bb = sizeof(float) * (size_t)k * n, cb = sizeof(float) * (size_t)m * n;
-  hipStream_t st = sync_stream();
-  const bool da = is_device_ptr(pSrcA->pData), db = is_device_ptr(pSrcB->pData), dc = is_device_ptr(pDst->pData);
-  float* A = da ? pSrcA->pData : (float*)scratch(ab + 16, 0);
-  float* B = db ? pSrcB->pData : (float*)scratch(bb + 16, 1);
-  float* C = dc ? pDst->pData : (float*)scratch(cb + 16, 2);
-  if (!A || !B || !C) { set_error(hipErrorOutOfMemory, "arm_mat_mult scratch"); return ARM_MATH_ARGUMENT_ERROR; }
-  HostIO io(st);
-  hipError_t e = hipSuccess;
-  if (!da) e = io.in(A, pSrcA->pData, ab);
-  if (e == hipSuccess && !db) e = io.in(B, pSrcB->pData, bb);
-  if (e == hipSuccess) e = mat_mult_f32_launch(m, k, n, A, B, C, 1, st);
-  if (e == hipSuccess && !dc) e = io.out(pDst->pData, C, cb);
-  if (e == hipSuccess) e = io.finish();
-  if (e != hipSuccess) { set_error(e, "arm_mat_mult_f32"); return ARM_MATH_ARGUMENT_ERROR; }
-  return ARM_MATH_SUCCESS;
+  return mat_mult_sync<float>(pSrcA, pSrcB, pDst, "arm_mat_mult_f32", mat_mult_f32_launch);
 }
-
 arm_status arm_mat_mult_f32_batch(const arm_matrix_instance_f32* pSrcA, const arm_matrix_instance_f32* pSrcB,
                                   arm_matrix_instance_f32* pDst, uint32_t batch, void* stream) {
-  if (!pSrcA || !pSrcB || !pDst) return ARM_MATH_ARGUMENT_ERROR;
-  if (!mat_shapes_ok(pSrcA, pSrcB, pDst)) return ARM_MATH_SIZE_MISMATCH;
-  hipError_t e = mat_mult_f32_launch(pSrcA->numRows, pSrcA->numCols, pSrcB->numCols, pSrcA->pData, pSrcB->pData,
-                                     pDst->pData, batch, (hipStream_t)stream);
-  if (e != hipSuccess) { set_error(e, "arm_mat_mult_f32_batch"); return ARM_MATH_ARGUMENT_ERROR; }
-  return ARM_MATH_SUCCESS;
+  return mat_batch(pSrcA, pSrcB, pDst, batch, stream, "arm_mat_mult_f32_batch", mat_mult_f32_launch);
 }
 
-// ---- MFCC f32 (drop-in + batched) ------------------------------------------------
+// ---- MFCC (drop-in + batched) ------------------------------------------------------
 void arm_mfcc_f32(const arm_mfcc_instance_f32* S, float32_t* pSrc, float32_t* pDst, float32_t* pTmp) {
-  (void)pTmp;   // work space lives on the device; the reference's pTmp contents are not reproduced
-  if (!S || !pSrc || !pDst || S->nbDctOutputs == 0) return;
-  hipStream_t st = sync_stream();
-  BlobScope hold(st);
-  MfccDev d;
-  if (!mfcc_prepare(S, d)) return;
-  const uint32_t n = S->fftLen, nd = S->nbDctOutputs;
-  float* x = (float*)scratch(sizeof(float) * n, 0);
-  float* y = (float*)scratch(sizeof(float) * n, 1);
-  const bool ddst = is_device_ptr(pDst);
-  float* o = ddst ? pDst : (float*)scratch(sizeof(float) * nd, 2);
-  if (!x || !y || !o) { set_error(hipErrorOutOfMemory, "arm_mfcc scratch"); return; }
-  HostIO io(st);
-  hipError_t e = is_device_ptr(pSrc) ? hipMemcpyAsync(x, pSrc, sizeof(float) * n, hipMemcpyDeviceToDevice, st)
-                                     : io.in(x, pSrc, sizeof(float) * n);
-  if (e != hipSuccess) { set_error(e, "arm_mfcc_f32"); return; }
-  if (!mfcc_run(S, d, x, y, o, 1, st)) { (void)hipStreamSynchronize(st); return; }
-  if (!ddst) e = io.out(pDst, o, sizeof(float) * nd);
-  if (e == hipSuccess) e = io.finish();
-  if (e != hipSuccess) set_error(e, "arm_mfcc_f32");
+  (void)pTmp;
+  (void)mfcc_sync<MfccDev<float>>(S, pSrc, pDst, "arm_mfcc_f32");
 }
-
 arm_status arm_mfcc_f32_batch(const arm_mfcc_instance_f32* S, float32_t* d_src, float32_t* d_dst, float32_t* d_tmp,
                               uint32_t batch, void* stream) {
-  if (!S || (batch && (!d_src || !d_dst || !d_tmp))) return ARM_MATH_ARGUMENT_ERROR;
-  if (batch == 0 || S->nbDctOutputs == 0) return ARM_MATH_SUCCESS;
-  BlobScope hold((hipStream_t)stream);
-  MfccDev d;
-  if (!mfcc_prepare(S, d)) return ARM_MATH_ARGUMENT_ERROR;
-  return mfcc_run(S, d, d_src, d_tmp, d_dst, batch, (hipStream_t)stream) ? ARM_MATH_SUCCESS : ARM_MATH_ARGUMENT_ERROR;
+  return mfcc_batch<MfccDev<float>>(S, d_src, d_dst, d_tmp, batch, stream);
 }
-
-// ---- MFCC q31 / q15 (drop-in + batched) -----------------------------------------
-// Drop-in: the reference's pSrc / pTmp work contents are not reproduced (device scratch).
-}  // extern "C"
-template <typename T, typename Inst>
-static arm_status mfcc_fx_dropin(const Inst* S, T* pSrc, T* pDst, const char* what) {
-  if (!S || !pSrc || !pDst) return ARM_MATH_ARGUMENT_ERROR;
-  if (S->nbDctOutputs == 0) return ARM_MATH_SUCCESS;
-  hipStream_t st = sync_stream();
-  BlobScope hold(st);
-  MfccFxDev<T> d;
-  if (!mfcc_fx_prepare<T>(S, d)) return ARM_MATH_ARGUMENT_ERROR;
-  const uint32_t n = S->fftLen, nd = S->nbDctOutputs;
-  T* x = (T*)scratch(sizeof(T) * n, 0);
-  T* y = (T*)scratch(sizeof(T) * 2 * n, 1);
-  const bool ddst = is_device_ptr(pDst);
-  T* o = ddst ? pDst : (T*)scratch(sizeof(T) * nd, 2);
-  if (!x || !y || !o) { set_error(hipErrorOutOfMemory, what); return ARM_MATH_ARGUMENT_ERROR; }
-  HostIO io(st);
-  hipError_t e = is_device_ptr(pSrc) ? hipMemcpyAsync(x, pSrc, sizeof(T) * n, hipMemcpyDeviceToDevice, st)
-                                     : io.in(x, pSrc, sizeof(T) * n);
-  if (e != hipSuccess) { set_error(e, what); return ARM_MATH_ARGUMENT_ERROR; }
-  if (!mfcc_fx_run<T>(S, d, x, y, o, 1, st)) { (void)hipStreamSynchronize(st); return ARM_MATH_ARGUMENT_ERROR; }
-  if (!ddst) e = io.out(pDst, o, sizeof(T) * nd);
-  if (e == hipSuccess) e = io.finish();
-  if (e != hipSuccess) { set_error(e, what); return ARM_MATH_ARGUMENT_ERROR; }
-  return ARM_MATH_SUCCESS;
-}
-
-template <typename T, typename Inst>
-static arm_status mfcc_fx_batch(const Inst* S, T* d_src, T* d_dst, T* d_tmp, uint32_t batch, void* stream) {
-  if (!S || (batch && (!d_src || !d_dst || !d_tmp))) return ARM_MATH_ARGUMENT_ERROR;
-  if (batch == 0 || S->nbDctOutputs == 0) return ARM_MATH_SUCCESS;
-  BlobScope hold((hipStream_t)stream);
-  MfccFxDev<T> d;
-  if (!mfcc_fx_prepare<T>(S, d)) return ARM_MATH_ARGUMENT_ERROR;
-  return mfcc_fx_run<T>(S, d, d_src, d_tmp, d_dst, batch, (hipStream_t)stream) ? ARM_MATH_SUCCESS
-                                                                                : ARM_MATH_ARGUMENT_ERROR;
-}
-extern "C" {
-
 arm_status arm_mfcc_q31(const arm_mfcc_instance_q31* S, q31_t* pSrc, q31_t* pDst, q31_t* pTmp) {
   (void)pTmp;
-  return mfcc_fx_dropin<int32_t>(S, pSrc, pDst, "arm_mfcc_q31");
+  return mfcc_sync<MfccFxDev<int32_t>>(S, pSrc, pDst, "arm_mfcc_q31");
 }
 arm_status arm_mfcc_q31_batch(const arm_mfcc_instance_q31* S, q31_t* d_src, q31_t* d_dst, q31_t* d_tmp,
                               uint32_t batch, void* stream) {
-  return mfcc_fx_batch<int32_t>(S, d_src, d_dst, d_tmp, batch, stream);
+  return mfcc_batch<MfccFxDev<int32_t>>(S, d_src, d_dst, d_tmp, batch, stream);
 }
 arm_status arm_mfcc_q15(const arm_mfcc_instance_q15* S, q15_t* pSrc, q15_t* pDst, q31_t* pTmp) {
   (void)pTmp;
-  return mfcc_fx_dropin<int16_t>(S, pSrc, pDst, "arm_mfcc_q15");
+  return mfcc_sync<MfccFxDev<int16_t>>(S, pSrc, pDst, "arm_mfcc_q15");
 }
 arm_status arm_mfcc_q15_batch(const arm_mfcc_instance_q15* S, q15_t* d_src, q15_t* d_dst, q15_t* d_tmp,
                               uint32_t batch, void* stream) {
-  return mfcc_fx_batch<int16_t>(S, d_src, d_dst, d_tmp, batch, stream);
+  return mfcc_batch<MfccFxDev<int16_t>>(S, d_src, d_dst, d_tmp, batch, stream);
 }
 
 // ---- matrix multiply q7 / q15 / q31 ---------------------------------------------
@@ -1504,32 +1411,23 @@ arm_status arm_mfcc_q15_batch(const arm_mfcc_instance_q15* S, q15_t* d_src, q15_
 arm_status arm_mat_mult_q7(const arm_matrix_instance_q7* pSrcA, const arm_matrix_instance_q7* pSrcB,
                            arm_matrix_instance_q7* pDst, q7_t* pState) {
   (void)pState;
-  return mat_mult_fixed_sync<int8_t>(pSrcA, pSrcB, pDst);
-}
-arm_status arm_mat_mult_q7_batch(const arm_matrix_instance_q7* pSrcA, const arm_matrix_instance_q7* pSrcB,
-                                 arm_matrix_instance_q7* pDst, uint32_t batch, void* stream) {
-  if (!pSrcA || !pSrcB || !pDst) return ARM_MATH_ARGUMENT_ERROR;
-  if (!mat_shapes_ok(pSrcA, pSrcB, pDst)) return ARM_MATH_SIZE_MISMATCH;
-  hipError_t e = mat_mult_q7_launch(pSrcA->numRows, pSrcA->numCols, pSrcB->numCols, pSrcA->pData, pSrcB->pData,
-                                    pDst->pData, batch, (hipStream_t)stream);
-  if (e != hipSuccess) { set_error(e, "arm_mat_mult_q7_batch"); return ARM_MATH_ARGUMENT_ERROR; }
-  return ARM_MATH_SUCCESS;
+  return mat_mult_sync<int8_t>(pSrcA, pSrcB, pDst, "arm_mat_mult", mat_mult_q7_launch);
 }
 arm_status arm_mat_mult_q15(const arm_matrix_instance_q15* pSrcA, const arm_matrix_instance_q15* pSrcB,
                             arm_matrix_instance_q15* pDst, q15_t* pState) {
   (void)pState;   // the reference's transpose buffer (ARM_MATH_DSP branch only)
-  return mat_mult_fixed_sync<int16_t>(pSrcA, pSrcB, pDst);
+  return mat_mult_sync<int16_t>(pSrcA, pSrcB, pDst, "arm_mat_mult", mat_mult_q15_launch);
 }
 arm_status arm_mat_mult_q31(const arm_matrix_instance_q31* pSrcA, const arm_matrix_instance_q31* pSrcB,
                             arm_matrix_instance_q31* pDst) {
-  return mat_mult_fixed_sync<int32_t>(pSrcA, pSrcB, pDst);
+  return mat_mult_sync<int32_t>(pSrcA, pSrcB, pDst, "arm_mat_mult", mat_mult_q31_launch);
 }
 // arm_mat_mult_opt_q31.c:648-780 (the host build's scalar branch): the q31 product above; pState
 // (the Helium branch's transpose buffer) is unused there too.
 arm_status arm_mat_mult_opt_q31(const arm_matrix_instance_q31* pSrcA, const arm_matrix_instance_q31* pSrcB,
                                 arm_matrix_instance_q31* pDst, q31_t* pState) {
   (void)pState;
-  return mat_mult_fixed_sync<int32_t>(pSrcA, pSrcB, pDst);
+  return arm_mat_mult_q31(pSrcA, pSrcB, pDst);
 }
 // arm_mat_mult_fast_q15.c:351-401 (!ARM_MATH_DSP: q31_t modular sum, (q15)(sum >> 15)),
 // arm_mat_mult_fast_q31.c:152-166 (per-product high word, sum << 1); pState unused (the
@@ -1537,48 +1435,22 @@ arm_status arm_mat_mult_opt_q31(const arm_matrix_instance_q31* pSrcA, const arm_
 arm_status arm_mat_mult_fast_q15(const arm_matrix_instance_q15* pSrcA, const arm_matrix_instance_q15* pSrcB,
                                  arm_matrix_instance_q15* pDst, q15_t* pState) {
   (void)pState;
-  return mat_mult_fixed_sync<int16_t>(pSrcA, pSrcB, pDst, true);
+  return mat_mult_sync<int16_t>(pSrcA, pSrcB, pDst, "arm_mat_mult", mat_mult_fast_q15_launch);
 }
 arm_status arm_mat_mult_fast_q31(const arm_matrix_instance_q31* pSrcA, const arm_matrix_instance_q31* pSrcB,
                                  arm_matrix_instance_q31* pDst) {
-  return mat_mult_fixed_sync<int32_t>(pSrcA, pSrcB, pDst, true);
+  return mat_mult_sync<int32_t>(pSrcA, pSrcB, pDst, "arm_mat_mult", mat_mult_fast_q31_launch);
 }
-arm_status arm_mat_mult_fast_q15_batch(const arm_matrix_instance_q15* pSrcA, const arm_matrix_instance_q15* pSrcB,
-                                       arm_matrix_instance_q15* pDst, uint32_t batch, void* stream) {
-  if (!pSrcA || !pSrcB || !pDst) return ARM_MATH_ARGUMENT_ERROR;
-  if (!mat_shapes_ok(pSrcA, pSrcB, pDst)) return ARM_MATH_SIZE_MISMATCH;
-  hipError_t e = mat_mult_fast_q15_launch(pSrcA->numRows, pSrcA->numCols, pSrcB->numCols, pSrcA->pData,
-                                          pSrcB->pData, pDst->pData, batch, (hipStream_t)stream);
-  if (e != hipSuccess) { set_error(e, "arm_mat_mult_fast_q15_batch"); return ARM_MATH_ARGUMENT_ERROR; }
-  return ARM_MATH_SUCCESS;
-}
-arm_status arm_mat_mult_fast_q31_batch(const arm_matrix_instance_q31* pSrcA, const arm_matrix_instance_q31* pSrcB,
-                                       arm_matrix_instance_q31* pDst, uint32_t batch, void* stream) {
-  if (!pSrcA || !pSrcB || !pDst) return ARM_MATH_ARGUMENT_ERROR;
-  if (!mat_shapes_ok(pSrcA, pSrcB, pDst)) return ARM_MATH_SIZE_MISMATCH;
-  hipError_t e = mat_mult_fast_q31_launch(pSrcA->numRows, pSrcA->numCols, pSrcB->numCols, pSrcA->pData,
-                                          pSrcB->pData, pDst->pData, batch, (hipStream_t)stream);
-  if (e != hipSuccess) { set_error(e, "arm_mat_mult_fast_q31_batch"); return ARM_MATH_ARGUMENT_ERROR; }
-  return ARM_MATH_SUCCESS;
-}
-arm_status arm_mat_mult_q15_batch(const arm_matrix_instance_q15* pSrcA, const arm_matrix_instance_q15* pSrcB,
-                                  arm_matrix_instance_q15* pDst, uint32_t batch, void* stream) {
-  if (!pSrcA || !pSrcB || !pDst) return ARM_MATH_ARGUMENT_ERROR;
-  if (!mat_shapes_ok(pSrcA, pSrcB, pDst)) return ARM_MATH_SIZE_MISMATCH;
-  hipError_t e = mat_mult_q15_launch(pSrcA->numRows, pSrcA->numCols, pSrcB->numCols, pSrcA->pData, pSrcB->pData,
-                                     pDst->pData, batch, (hipStream_t)stream);
-  if (e != hipSuccess) { set_error(e, "arm_mat_mult_q15_batch"); return ARM_MATH_ARGUMENT_ERROR; }
-  return ARM_MATH_SUCCESS;
-}
-arm_status arm_mat_mult_q31_batch(const arm_matrix_instance_q31* pSrcA, const arm_matrix_instance_q31* pSrcB,
-                                  arm_matrix_instance_q31* pDst, uint32_t batch, void* stream) {
-  if (!pSrcA || !pSrcB || !pDst) return ARM_MATH_ARGUMENT_ERROR;
-  if (!mat_shapes_ok(pSrcA, pSrcB, pDst)) return ARM_MATH_SIZE_MISMATCH;
-  hipError_t e = mat_mult_q31_launch(pSrcA->numRows, pSrcA->numCols, pSrcB->numCols, pSrcA->pData, pSrcB->pData,
-                                     pDst->pData, batch, (hipStream_t)stream);
-  if (e != hipSuccess) { set_error(e, "arm_mat_mult_q31_batch"); return ARM_MATH_ARGUMENT_ERROR; }
-  return ARM_MATH_SUCCESS;
-}
+#define MI355X_MAT_BATCH(NAME, INST, LAUNCH)                                                                \
+  arm_status NAME(const INST* pSrcA, const INST* pSrcB, INST* pDst, uint32_t batch, void* stream) {        \
+    return mat_batch(pSrcA, pSrcB, pDst, batch, stream, #NAME, LAUNCH);                                    \
+  }
+MI355X_MAT_BATCH(arm_mat_mult_q7_batch, arm_matrix_instance_q7, mat_mult_q7_launch)
+MI355X_MAT_BATCH(arm_mat_mult_q15_batch, arm_matrix_instance_q15, mat_mult_q15_launch)
+MI355X_MAT_BATCH(arm_mat_mult_q31_batch, arm_matrix_instance_q31, mat_mult_q31_launch)
+MI355X_MAT_BATCH(arm_mat_mult_fast_q15_batch, arm_matrix_instance_q15, mat_mult_fast_q15_launch)
+MI355X_MAT_BATCH(arm_mat_mult_fast_q31_batch, arm_matrix_instance_q31, mat_mult_fast_q31_launch)
+#undef MI355X_MAT_BATCH
 
 // ---- convolution ------------------------------------------------------------------
 #define MI355X_CONV_FULL(NAME, T, CT, OP, VAR)                                                                  \

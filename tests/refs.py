@@ -135,30 +135,49 @@ class Host:
             f(C.byref(S), src.ctypes.data, out[r].ctypes.data, tmp.ctypes.data)
         return out
 
-    def fir(self, kind, coeffs, blocks):
+    @staticmethod
+    def _state(n, dt, state_mem):
+        """The state buffer of a filter as (pointer, reader): host words, or state_mem(n, dtype)."""
+        if state_mem is not None:
+            return state_mem(n, dt)
+        state = np.zeros(n, dtype=dt)
+        return state.ctypes.data, state.copy
+
+    @staticmethod
+    def _stream(f, inst, blocks, dt, nout, src_mem, dst_mem):
+        """Call f(inst, src, dst, len) per block.  src_mem(block) may supply the input's pointer and
+        dst_mem(n, dtype) the output buffer as (pointer, reader), e.g. device memory."""
+        outs = []
+        for b in blocks:
+            b = np.ascontiguousarray(b, dtype=dt)
+            y = np.zeros(nout(len(b)), dtype=dt)
+            sptr = b.ctypes.data if src_mem is None else src_mem(b)
+            dptr, dread = (y.ctypes.data, lambda: y) if dst_mem is None else dst_mem(len(y), dt)
+            f(C.byref(inst), sptr, dptr, len(b))
+            outs.append(dread())
+        return outs
+
+    def fir(self, kind, coeffs, blocks, state_mem=None, src_mem=None, dst_mem=None):
         """Stream `blocks` (list of 1-D arrays, each <= the block size) through one filter;
-        returns (outputs, final state buffer).  kind: f32, q15, q31, fast_q15, fast_q31."""
+        returns (outputs, final state buffer).  kind: f32, q15, q31, fast_q15, fast_q31.
+        state_mem / src_mem / dst_mem may supply the buffers (_state, _stream)."""
         base = kind.split("_")[-1]
         dt = DTYPE[base]
         inst = {"f32": _abi.arm_fir_instance_f32, "q15": _abi.arm_fir_instance_q15,
                 "q31": _abi.arm_fir_instance_q31, "q7": _abi.arm_fir_instance_q7}[base]()
         c = np.ascontiguousarray(coeffs, dtype=dt)
         bs = max(len(b) for b in blocks)
-        state = np.zeros(len(c) + bs - 1, dtype=dt)
-        self.fn(f"arm_fir_init_{base}")(C.byref(inst), len(c), c.ctypes.data, state.ctypes.data, bs)
-        outs = []
-        for b in blocks:
-            b = np.ascontiguousarray(b, dtype=dt)
-            y = np.zeros_like(b)
-            self.fn(f"arm_fir_{kind}")(C.byref(inst), b.ctypes.data, y.ctypes.data, len(b))
-            outs.append(y)
-        self._keep = (c, state)
-        return outs, state.copy()
+        sptr, sread = self._state(len(c) + bs - 1, dt, state_mem)
+        self.fn(f"arm_fir_init_{base}")(C.byref(inst), len(c), c.ctypes.data, sptr, bs)
+        outs = self._stream(self.fn(f"arm_fir_{kind}"), inst, blocks, dt, lambda n: n, src_mem, dst_mem)
+        self._keep = (c, sread)
+        return outs, sread()
 
-    def multirate(self, fn, factor, coeffs, blocks, block_size=None):
+    def multirate(self, fn, factor, coeffs, blocks, block_size=None, state_mem=None, src_mem=None, dst_mem=None):
         """Stream `blocks` through one arm_fir_decimate_* / arm_fir_interpolate_* instance
         (fn e.g. "decimate_fast_q15", "interpolate_f32"; factor = M or L): returns
-        (init status, outputs, final state buffer)."""
+        (init status, outputs, final state buffer).  state_mem / src_mem / dst_mem may supply
+        the buffers (_state, _stream)."""
         base = fn.split("_")[-1]
         dt = DTYPE[base]
         decim = fn.startswith("decimate")
@@ -166,25 +185,18 @@ class Host:
         bs = block_size or max(len(b) for b in blocks)
         if decim:
             inst = _abi.arm_fir_decimate_instance()
-            state = np.zeros(len(c) + bs - 1, dtype=dt)
-            st = self.fn(f"arm_fir_decimate_init_{base}")(C.byref(inst), len(c), factor, c.ctypes.data,
-                                                            state.ctypes.data, bs)
+            sptr, sread = self._state(len(c) + bs - 1, dt, state_mem)
+            st = self.fn(f"arm_fir_decimate_init_{base}")(C.byref(inst), len(c), factor, c.ctypes.data, sptr, bs)
         else:
             inst = _abi.arm_fir_interpolate_instance()
-            state = np.zeros(bs + max(len(c) // max(factor, 1), 1) - 1, dtype=dt)
-            st = self.fn(f"arm_fir_interpolate_init_{base}")(C.byref(inst), factor, len(c), c.ctypes.data,
-                                                               state.ctypes.data, bs)
+            sptr, sread = self._state(bs + max(len(c) // max(factor, 1), 1) - 1, dt, state_mem)
+            st = self.fn(f"arm_fir_interpolate_init_{base}")(C.byref(inst), factor, len(c), c.ctypes.data, sptr, bs)
         if st != 0:
-            return st, [], state
-        outs = []
-        f = self.fn(f"arm_fir_{fn}")
-        for b in blocks:
-            b = np.ascontiguousarray(b, dtype=dt)
-            y = np.zeros(len(b) // factor if decim else len(b) * factor, dtype=dt)
-            f(C.byref(inst), b.ctypes.data, y.ctypes.data, len(b))
-            outs.append(y)
-        self._keep = (c, state)
-        return st, outs, state.copy()
+            return st, [], sread()
+        outs = self._stream(self.fn(f"arm_fir_{fn}"), inst, blocks, dt,
+                            (lambda n: n // factor) if decim else (lambda n: n * factor), src_mem, dst_mem)
+        self._keep = (c, sread)
+        return st, outs, sread()
 
     def lattice(self, kind, coeffs, blocks, state_mem=None):
         """Stream `blocks` through one arm_fir_lattice_<kind> instance: returns (outputs,
@@ -310,6 +322,47 @@ class Host:
         init(C.byref(Cm), c.shape[0], c.shape[1], c.ctypes.data)
         st = self.fn("arm_mat_mult_f32")(C.byref(A), C.byref(B), C.byref(Cm))
         return st, c
+
+
+def in_place_host():
+    """src_mem / dst_mem hooks of Host.fir / Host.multirate: each block is filtered in place on a
+    host copy of it (pDst == pSrc)."""
+    last = []
+
+    def src_mem(b):
+        last[:] = [b.copy()]
+        return last[0].ctypes.data
+
+    def dst_mem(n, dt):
+        buf = last[0]
+        return buf.ctypes.data, lambda: buf[:n].copy()
+
+    return {"src_mem": src_mem, "dst_mem": dst_mem}
+
+
+def device_placement(torch, on, in_place=False):
+    """state_mem / src_mem / dst_mem hooks of Host.fir / Host.multirate that put the buffers named
+    in `on` ("state", "src", "dst") into device memory, each in a tensor of its own; in_place: pDst is
+    the device input buffer itself.  A device state starts non-zero, so the init's zeroing shows."""
+    keep = []
+
+    def tensor(a):
+        keep.append(torch.from_numpy(a).cuda())
+        return keep[-1]
+
+    def state_mem(n, dt):
+        t = tensor(np.full(n, 3, dtype=dt))
+        return t.data_ptr(), lambda: t.cpu().numpy().copy()
+
+    def src_mem(b):
+        return tensor(b.copy()).data_ptr()
+
+    def dst_mem(n, dt):
+        t = keep[-1] if in_place else tensor(np.zeros(n, dtype=dt))
+        return t.data_ptr(), lambda: t[:n].cpu().numpy().copy()
+
+    hooks = {"state": ("state_mem", state_mem), "src": ("src_mem", src_mem), "dst": ("dst_mem", dst_mem)}
+    return dict(hooks[k] for k in on)
 
 
 _cache = {}

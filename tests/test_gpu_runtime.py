@@ -124,6 +124,54 @@ def test_fir_dropin_in_place_on_device(dsp, torch_gpu, ref):
     assert state.cpu().numpy().tobytes() == want_state.tobytes()
 
 
+def _fir_q31_case():
+    return refs.rand_input("q31", 29, seed=21), [refs.rand_input("q31", b, seed=22 + k) for k, b in enumerate((64, 37))]
+
+
+@pytest.mark.parametrize("on", [("state", "src", "dst"), ("state",), ("src",), ("dst",)], ids="+".join)
+def test_fir_dropin_placement(dsp, torch_gpu, ref, on):
+    """arm_fir_q31 with the named ones of pState / pSrc / pDst in device memory (distinct buffers,
+    the others host words): two calls' outputs and the final state buffer equal the reference's."""
+    c, blocks = _fir_q31_case()
+    want, want_state = ref.fir("q31", c, blocks)
+    got, state = refs.Host(dsp.lib, "").fir("q31", c, blocks, **refs.device_placement(torch_gpu, on))
+    dsp._check_void("arm_fir_q31")
+    for g, w in zip(got, want):
+        assert g.tobytes() == w.tobytes()
+    assert state.tobytes() == want_state.tobytes()
+
+
+def test_fir_q31_dropin_in_place_on_device(dsp, torch_gpu, ref):
+    """arm_fir_q31 with pSrc == pDst on the device: the reference's out-of-place bytes, which are
+    also what the reference itself gives in place (each input is copied into pState first)."""
+    c, blocks = _fir_q31_case()
+    want, want_state = ref.fir("q31", c, blocks)
+    in_place, in_place_state = ref.fir("q31", c, blocks, **refs.in_place_host())
+    hooks = refs.device_placement(torch_gpu, ("state", "src", "dst"), in_place=True)
+    got, state = refs.Host(dsp.lib, "").fir("q31", c, blocks, **hooks)
+    dsp._check_void("arm_fir_q31")
+    for g, w, r in zip(got, want, in_place):
+        assert g.tobytes() == w.tobytes() == r.tobytes()
+    assert state.tobytes() == want_state.tobytes() == in_place_state.tobytes()
+
+
+def test_mat_mult_dropin_device_operands(dsp, torch_gpu, ref, oracle):
+    """arm_mat_mult_f32 and arm_mat_mult_q15 on a 5x7x3 product with all three matrices in device
+    memory: f32 equals the stated fmaf chain, q15 the reference build."""
+    torch = torch_gpu
+    for kind, inst, state in (("f32", dsp.arm_matrix_instance_f32, ()), ("q15", dsp.arm_matrix_instance_q15, (None,))):
+        a, b = refs.rand_input(kind, 35, seed=31).reshape(5, 7), refs.rand_input(kind, 21, seed=32).reshape(7, 3)
+        want = oracle.mat_mult_fmaf(a, b)[1] if kind == "f32" else ref.mat_mult_fixed(kind, a, b)[1]
+        da, db = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
+        dc = torch.full((5, 3), 9, dtype=da.dtype, device="cuda")
+        A, B, Cm = inst(), inst(), inst()
+        for M, t in ((A, da), (B, db), (Cm, dc)):
+            getattr(dsp.lib, f"arm_mat_init_{kind}")(C.byref(M), t.shape[0], t.shape[1], C.c_void_p(t.data_ptr()))
+        assert getattr(dsp.lib, f"arm_mat_mult_{kind}")(C.byref(A), C.byref(B), C.byref(Cm), *state) == 0
+        dsp._check_void(f"arm_mat_mult_{kind}")
+        assert dc.cpu().numpy().tobytes() == want.tobytes()
+
+
 @pytest.mark.parametrize("kind", ["f32", "q15", "q31"])
 def test_fir_batch_in_place(dsp, torch_gpu, ref, kind):
     """arm_fir_*_batch with d_src == d_dst over two calls (several chunks per filter)."""

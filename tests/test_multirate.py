@@ -100,6 +100,37 @@ def test_multirate_dropin_bitexact(product, torch_gpu, ref, fn):
         same(product.multirate(fn, factor, c, xs), ref.multirate(fn, factor, c, xs))
 
 
+# Drop-in pointer placement: which of pState / pSrc / pDst lie in device memory, each in a buffer of
+# its own (the others are host words).  Two consecutive calls, outputs and the final state buffer.
+PLACED = [("decimate_f32", 29, 3, [33, 66]), ("decimate_fast_q15", 29, 3, [33, 66]), ("interpolate_q15", 30, 3, [33, 7])]
+PLACEMENTS = [("state", "src", "dst"), ("state",), ("src",), ("dst",)]
+
+
+@pytest.mark.parametrize("fn,taps,M,blocks", PLACED[:2])
+def test_decimate_reference_in_place_equals_out_of_place(ref, fn, taps, M, blocks):
+    """The reference run with pDst == pSrc gives its out-of-place bytes (every input is copied into
+    pState before an output is written), which is what the in-place GPU case below expects."""
+    c, xs = case(fn, taps, blocks, taps + M)
+    same(ref.multirate(fn, M, c, xs, **refs.in_place_host()), ref.multirate(fn, M, c, xs))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("on", PLACEMENTS, ids="+".join)
+@pytest.mark.parametrize("fn,taps,factor,blocks", PLACED)
+def test_multirate_dropin_placement(product, torch_gpu, ref, fn, taps, factor, blocks, on):
+    c, xs = case(fn, taps, blocks, taps + factor)
+    same(product.multirate(fn, factor, c, xs, **refs.device_placement(torch_gpu, on)), ref.multirate(fn, factor, c, xs))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fn,taps,M,blocks", PLACED[:2])
+def test_decimate_dropin_in_place_on_device(product, torch_gpu, ref, fn, taps, M, blocks):
+    """pSrc == pDst on the device (state on the device too): the reference's out-of-place bytes."""
+    c, xs = case(fn, taps, blocks, taps + M)
+    hooks = refs.device_placement(torch_gpu, ("state", "src", "dst"), in_place=True)
+    same(product.multirate(fn, M, c, xs, **hooks), ref.multirate(fn, M, c, xs))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("fn", DECIM + INTERP)
 @pytest.mark.parametrize("taps,factor,block", [(128, 4, 4096), (31, 3, 999), (256, 2, 2050)])
