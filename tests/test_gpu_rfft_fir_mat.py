@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import refs
+from f32_classes import f32_class_input
 
 pytestmark = pytest.mark.gpu
 
@@ -373,13 +374,7 @@ def _mat_inputs(rng, shape_a, shape_b, dist):
         f = lambda sh: (rng.uniform(0.5, 1.0, sh) * rng.choice([-1.0, 1.0], sh) * 2.0 ** -66).astype(np.float32)
         return f(shape_a), f(shape_b)
     if dist == "mixed":         # exponents over 2^-20 .. 2^20, exact zeros and negative zeros
-        def f(sh):
-            v = rng.uniform(0.5, 1.0, sh) * rng.choice([-1.0, 1.0], sh) * 2.0 ** rng.integers(-20, 21, sh)
-            z = rng.uniform(0, 1, sh)
-            v[z < 0.1] = 0.0
-            v[(z >= 0.1) & (z < 0.2)] = -0.0
-            return v.astype(np.float32)
-        return f(shape_a), f(shape_b)
+        return f32_class_input("mixed", shape_a, rng), f32_class_input("mixed", shape_b, rng)
     raise ValueError(dist)
 
 
