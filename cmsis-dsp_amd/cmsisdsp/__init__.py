@@ -67,6 +67,8 @@ for _t in ("f32", "q31", "q15"):
     globals()[f"arm_fir_lattice_instance_{_t}"] = _make(f"arm_fir_lattice_instance_{_t}", _abi.arm_fir_lattice_instance)
 for _t in {v[0].__name__: v[0] for v in _abi.BIQUAD_FUNCS.values()}.values():
     globals()[_t.__name__] = _make(_t.__name__, _t)
+for _t in (v[0] for v in _abi.ADAPTIVE_FUNCS.values()):
+    globals()[_t.__name__] = _make(_t.__name__, _t)
 for _t in ("f32", "q31", "q15", "q7"):
     globals()[f"arm_fir_sparse_instance_{_t}"] = _make(f"arm_fir_sparse_instance_{_t}", _abi.arm_fir_sparse_instance)
 del _t
@@ -347,6 +349,81 @@ for _f, (_i, _init, _ps) in _abi.BIQUAD_FUNCS.items():
     globals()[_init] = _biquad_init(_init, _ps is not None)
     globals()[_f] = _biquad(_f, _BQ_STATE[_init][2], 2 if "stereo" in _f else 1)
 del _f, _i, _init, _ps
+
+
+# cmsisdsp_filtering.c cmsis_arm_iir_lattice_init_* ("OhOOO": S, numStages, pkCoeffs, pvCoeffs, pState; the
+# extension passes blockSize = len(pkCoeffs), :5652-5812) and cmsis_arm_iir_lattice_* ("OO": S, pSrc; returns
+# len(pSrc) words, :5618-5780).  The module keeps its own zeroed state, at least the numStages +
+# len(pkCoeffs) words that init clears.
+def _iir_lattice_init(name, dt):
+    def init(inst, numStages, pkCoeffs, pvCoeffs, pState):
+        k, v = _arr(pkCoeffs, dt), _arr(pvCoeffs, dt)
+        if len(k) < int(numStages) or len(v) < int(numStages) + 1:
+            raise ValueError(f"{name}: numStages reflection and numStages + 1 ladder coefficients")
+        state = _np.zeros(max(len(_np.asarray(pState)), int(numStages) + len(k)), dtype=dt)
+        inst._keep = [k, v, state]
+        getattr(_lib, name)(_C.byref(inst._s), int(numStages), k.ctypes.data, v.ctypes.data, state.ctypes.data, len(k))
+        _check(name)
+    init.__name__ = name
+    return init
+
+
+def _iir_lattice(name, dt):
+    def run(inst, pSrc):
+        x = _arr(pSrc, dt)
+        y = _np.zeros(len(x), dtype=dt)
+        getattr(_lib, name)(_C.byref(inst._s), x.ctypes.data, y.ctypes.data, len(x))
+        _check(name)
+        return y
+    run.__name__ = name
+    return run
+
+
+# cmsis_arm_lms*_init_* ("OhOOf" / "OhOOhi" / "OhOOii": S, numTaps, pCoeffs, pState, mu[, postShift];
+# blockSize = len(pState) - len(pCoeffs) + 1, :5856-6240) and cmsis_arm_lms* ("OOOO": S, pSrc, pRef, pErr;
+# returns pOut, len(pSrc) words, :5814-6210).  The extension works on converted copies, so the error
+# signal and the adapted coefficients never reach its caller; here a numpy pErr of the function's dtype
+# and len(pSrc) words receives the error, and inst.coeffs() returns the instance's current coefficients.
+def _lms_init(name, dt, with_shift):
+    def init(inst, numTaps, pCoeffs, pState, mu, *postShift):
+        if len(postShift) != (1 if with_shift else 0):
+            raise TypeError(f"{name}: takes {7 if with_shift else 6} arguments")
+        c = _arr(pCoeffs, dt).copy()
+        if len(c) < int(numTaps) or int(numTaps) < 1:
+            raise ValueError(f"{name}: numTaps coefficients")
+        state = _np.zeros(max(len(_np.asarray(pState)), int(numTaps) - 1), dtype=dt)
+        inst._keep = [c, state]
+        inst.coeffs = lambda: c[:int(numTaps)].copy()
+        getattr(_lib, name)(_C.byref(inst._s), int(numTaps), c.ctypes.data, state.ctypes.data,
+                            float(mu) if dt == _np.float32 else int(mu), len(state) - len(c) + 1 if len(state) >= len(c) else 0,
+                            *[int(v) for v in postShift])
+        _check(name)
+    init.__name__ = name
+    return init
+
+
+def _lms(name, dt):
+    def run(inst, pSrc, pRef, pErr):
+        x, d = _arr(pSrc, dt), _arr(pRef, dt)
+        if len(d) < len(x):
+            raise ValueError(f"{name}: pRef shorter than pSrc")
+        y, e = _np.zeros(len(x), dtype=dt), _np.zeros(len(x), dtype=dt)
+        getattr(_lib, name)(_C.byref(inst._s), x.ctypes.data, d.ctypes.data, y.ctypes.data, e.ctypes.data, len(x))
+        _check(name)
+        if isinstance(pErr, _np.ndarray) and pErr.dtype == dt and pErr.shape == e.shape:
+            pErr[...] = e
+        return y
+    run.__name__ = name
+    return run
+
+
+for _f, (_i, _init, _extra) in _abi.ADAPTIVE_FUNCS.items():
+    _d = _DT[_f.rsplit("_", 1)[1]]
+    if "lattice" in _f:
+        globals()[_init], globals()[_f] = _iir_lattice_init(_init, _d), _iir_lattice(_f, _d)
+    else:
+        globals()[_init], globals()[_f] = _lms_init(_init, _d, len(_extra) == 2), _lms(_f, _d)
+del _f, _i, _init, _extra, _d
 
 
 # cmsisdsp_filtering.c cmsis_arm_fir_sparse_init_* ("OhOOOh": S, numTaps, pCoeffs, pState,

@@ -49,6 +49,7 @@ def _load():
     _abi.bind(lib, _abi.RFFTQ_LEN)
     _abi.bind(lib, _abi.PARTIAL_FAST)
     _abi.bind(lib, _abi.BIQUAD)
+    _abi.bind(lib, _abi.ADAPTIVE)
     _abi.bind(lib, _abi.BATCHED)
     return lib
 

@@ -96,6 +96,44 @@ class arm_biquad_cascade_stereo_df2T_instance_f32(C.Structure):
     _fields_ = [("numStages", C.c_uint8), ("pState", C.c_void_p), ("pCoeffs", C.c_void_p)]
 
 
+# IIR lattice instances (filtering_functions.h:1428-1458): one layout, a class per type
+class arm_iir_lattice_instance_f32(C.Structure):
+    _fields_ = [("numStages", C.c_uint16), ("pState", C.c_void_p), ("pkCoeffs", C.c_void_p), ("pvCoeffs", C.c_void_p)]
+
+
+class arm_iir_lattice_instance_q31(C.Structure):
+    _fields_ = arm_iir_lattice_instance_f32._fields_
+
+
+class arm_iir_lattice_instance_q15(C.Structure):
+    _fields_ = arm_iir_lattice_instance_f32._fields_
+
+
+# LMS / normalised LMS instances (filtering_functions.h:1560-1566, :1608-1615, :1659-1666, :1710-1718, :1813-1824)
+class arm_lms_instance_f32(C.Structure):
+    _fields_ = [("numTaps", C.c_uint16), ("pState", C.c_void_p), ("pCoeffs", C.c_void_p), ("mu", C.c_float)]
+
+
+class arm_lms_instance_q31(C.Structure):
+    _fields_ = [("numTaps", C.c_uint16), ("pState", C.c_void_p), ("pCoeffs", C.c_void_p), ("mu", C.c_int32),
+                ("postShift", C.c_uint32)]
+
+
+class arm_lms_instance_q15(C.Structure):
+    _fields_ = [("numTaps", C.c_uint16), ("pState", C.c_void_p), ("pCoeffs", C.c_void_p), ("mu", C.c_int16),
+                ("postShift", C.c_uint32)]
+
+
+class arm_lms_norm_instance_f32(C.Structure):
+    _fields_ = [("numTaps", C.c_uint16), ("pState", C.c_void_p), ("pCoeffs", C.c_void_p), ("mu", C.c_float),
+                ("energy", C.c_float), ("x0", C.c_float)]
+
+
+class arm_lms_norm_instance_q15(C.Structure):
+    _fields_ = [("numTaps", C.c_uint16), ("pState", C.c_void_p), ("pCoeffs", C.c_void_p), ("mu", C.c_int16),
+                ("postShift", C.c_uint8), ("recipTable", C.c_void_p), ("energy", C.c_int16), ("x0", C.c_int16)]
+
+
 # arm_fir_sparse_instance_{f32,q31,q15,q7} (filtering_functions.h:2033-2091), one layout
 class arm_fir_sparse_instance(C.Structure):
     _fields_ = [("numTaps", C.c_uint16), ("stateIndex", C.c_uint16), ("pState", C.c_void_p), ("pCoeffs", C.c_void_p),
@@ -277,6 +315,28 @@ for _f, (_inst, _init, _ps) in BIQUAD_FUNCS.items():
     BIQUAD[_f] = (None, [P(_inst), C.c_void_p, C.c_void_p, C.c_uint32])
     BIQUAD[_init] = (None, [P(_inst), C.c_uint8, C.c_void_p, C.c_void_p] + ([_ps] if _ps else []))
 
+# IIR lattice and LMS / normalised LMS: processing function -> (instance, init function, the init's
+# arguments after (S, n, coefficient pointers, pState): mu and postShift).  The product only, as BIQUAD
+# (tests/golden/adaptive.npz holds the reference's outputs).
+ADAPTIVE_FUNCS = {
+    "arm_iir_lattice_f32": (arm_iir_lattice_instance_f32, "arm_iir_lattice_init_f32", []),
+    "arm_iir_lattice_q31": (arm_iir_lattice_instance_q31, "arm_iir_lattice_init_q31", []),
+    "arm_iir_lattice_q15": (arm_iir_lattice_instance_q15, "arm_iir_lattice_init_q15", []),
+    "arm_lms_f32": (arm_lms_instance_f32, "arm_lms_init_f32", [C.c_float]),
+    "arm_lms_q31": (arm_lms_instance_q31, "arm_lms_init_q31", [C.c_int32, C.c_uint32]),
+    "arm_lms_q15": (arm_lms_instance_q15, "arm_lms_init_q15", [C.c_int16, C.c_uint32]),
+    "arm_lms_norm_f32": (arm_lms_norm_instance_f32, "arm_lms_norm_init_f32", [C.c_float]),
+    "arm_lms_norm_q15": (arm_lms_norm_instance_q15, "arm_lms_norm_init_q15", [C.c_int16, C.c_uint8]),
+}
+ADAPTIVE = {}
+for _f, (_inst, _init, _extra) in ADAPTIVE_FUNCS.items():
+    if "lattice" in _f:   # (S, pSrc, pDst, blockSize); init (S, numStages, pkCoeffs, pvCoeffs, pState, blockSize)
+        ADAPTIVE[_f] = (None, [P(_inst), C.c_void_p, C.c_void_p, C.c_uint32])
+        ADAPTIVE[_init] = (None, [P(_inst), C.c_uint16, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32])
+    else:                 # (S, pSrc, pRef, pOut, pErr, blockSize); init (S, numTaps, pCoeffs, pState, mu, blockSize[, postShift])
+        ADAPTIVE[_f] = (None, [P(_inst), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32])
+        ADAPTIVE[_init] = (None, [P(_inst), C.c_uint16, C.c_void_p, C.c_void_p, _extra[0], C.c_uint32] + _extra[1:])
+
 # per-length MFCC init functions (the product and the reference build; the oracle has the
 # generic init only)
 MFCC_LEN = {f"arm_mfcc_init_{n}_f32": (C.c_int, [P(arm_mfcc_instance_f32), C.c_uint32, C.c_uint32, C.c_void_p,
@@ -337,6 +397,12 @@ BATCHED = {
                                                 C.c_uint32, C.c_void_p, C.c_void_p]) for t in ("f32", "q31", "q15")},
     **{f"{f}_batch": (C.c_int, [P(inst), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p])
        for f, (inst, _, _) in BIQUAD_FUNCS.items()},
+    # (S, d_src, d_dst, blockSize, batch, d_state, stream)
+    **{f"{f}_batch": (C.c_int, [P(inst), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p])
+       for f, (inst, _, _) in ADAPTIVE_FUNCS.items() if "lattice" in f},
+    # (S, d_src, d_ref, d_out, d_err, blockSize, batch, d_coeffs, d_state[, d_energy_x0], stream)
+    **{f"{f}_batch": (C.c_int, [P(inst)] + [C.c_void_p] * 4 + [C.c_uint32] * 2 + [C.c_void_p] * (4 if "norm" in f else 3))
+       for f, (inst, _, _) in ADAPTIVE_FUNCS.items() if "lms" in f},
     **{f"arm_fir_sparse_{t}_batch": (C.c_int, [P(arm_fir_sparse_instance), C.c_void_p, C.c_void_p, C.c_uint32,
                                                C.c_uint32, C.c_void_p, C.c_void_p]) for t in ("f32", "q31", "q15", "q7")},
     "arm_mat_mult_f32_batch": (C.c_int, [P(arm_matrix_instance_f32), P(arm_matrix_instance_f32),

@@ -962,6 +962,153 @@ arm_status biquad_batch(const Inst* S, int ps, const T* d_src, T* d_dst, uint32_
   return batch_status(biquad_run(op, dc, M, ps, d_src, d_dst, B, batch, d_state, (hipStream_t)stream), what);
 }
 
+// ---- IIR lattice ----------------------------------------------------------------------------
+// Drop-in: the live state (the first numStages words of pState, host or device) in, filter, state out,
+// as lattice_sync, with a second coefficient set; the reference's blockSize scratch words that follow
+// are not touched.  The inits zero numStages + blockSize words (arm_iir_lattice_init_f32.c).
+template <typename T, typename Inst>
+void iir_lattice_init(Inst* S, uint16_t numStages, T* pkCoeffs, T* pvCoeffs, T* pState, uint32_t blockSize) {
+  if (!S) return;
+  S->numStages = numStages; S->pkCoeffs = pkCoeffs; S->pvCoeffs = pvCoeffs; S->pState = pState;
+  const size_t words = (size_t)numStages + blockSize;
+  if (pState && words) zero_words(pState, sizeof(T) * words, "arm_iir_lattice_init");
+}
+
+template <typename T, typename Inst>
+void iir_lattice_sync(const Inst* S, const T* pSrc, T* pDst, uint32_t B, int op, const char* what) {
+  if (!S || B == 0) return;
+  if (!S->pState || !S->pkCoeffs || !S->pvCoeffs || !pSrc || !pDst || S->numStages == 0) {
+    set_error(hipErrorInvalidValue, what);
+    return;
+  }
+  const int N = S->numStages;
+  const size_t sb = sizeof(T) * (size_t)B;
+  FilterCall<T> c(S->pkCoeffs, N, S->pState, pSrc, pDst, what);
+  const T* dv = c.dc ? device_coeffs<T>(S->pvCoeffs, N + 1, what) : nullptr;
+  if (!dv) return;
+  filter_sync(c, S->pState, sizeof(T) * (size_t)N, pSrc, sb, pDst, sb, false, what,
+              [&](const T* dk, const T* src, T* dst, T* state, hipStream_t st) {
+                return iir_lattice_run(op, dk, dv, N, src, dst, B, 1, state, st);
+              });
+}
+
+template <typename T, typename Inst>
+arm_status iir_lattice_batch(const Inst* S, const T* d_src, T* d_dst, uint32_t B, uint32_t batch, T* d_state,
+                             void* stream, int op, const char* what) {
+  if (!S || !S->pkCoeffs || !S->pvCoeffs || S->numStages == 0 || !d_src || !d_dst || !d_state)
+    return ARM_MATH_ARGUMENT_ERROR;
+  if (!batch || !B) return ARM_MATH_SUCCESS;
+  BlobScope hold((hipStream_t)stream);
+  const T* dk = device_coeffs<T>(S->pkCoeffs, S->numStages, what);
+  const T* dv = dk ? device_coeffs<T>(S->pvCoeffs, S->numStages + 1, what) : nullptr;
+  if (!dv) return ARM_MATH_ARGUMENT_ERROR;
+  return batch_status(iir_lattice_run(op, dk, dv, S->numStages, d_src, d_dst, B, batch, d_state, (hipStream_t)stream),
+                      what);
+}
+
+// ---- LMS / normalised LMS -----------------------------------------------------------------
+// What a call needs from its instance: the kernel's op, the scalars as the kernel takes them and, for
+// the q15 normalised kind, the reciprocal table.  ok: the reference's shift counts stay in 0...31.
+struct LmsParams {
+  int op;
+  bool norm;
+  int taps;
+  int32_t mu, post_shift;
+  const q15_t* recip;
+  bool ok;
+};
+int32_t f32_bits(float32_t v) { int32_t b; memcpy(&b, &v, 4); return b; }
+extern "C" const int16_t armRecipTableQ15[64];
+LmsParams lms_params(const arm_lms_instance_f32* S) { return {kLmsF32, false, S->numTaps, f32_bits(S->mu), 0, nullptr, true}; }
+LmsParams lms_params(const arm_lms_instance_q31* S) {
+  return {kLmsQ31, false, S->numTaps, S->mu, (int32_t)S->postShift, nullptr, S->postShift <= 30};
+}
+LmsParams lms_params(const arm_lms_instance_q15* S) {
+  return {kLmsQ15, false, S->numTaps, S->mu, (int32_t)S->postShift, nullptr, S->postShift <= 14};
+}
+LmsParams lms_params(const arm_lms_norm_instance_f32* S) {
+  return {kLmsF32, true, S->numTaps, f32_bits(S->mu), 0, nullptr, true};
+}
+LmsParams lms_params(const arm_lms_norm_instance_q15* S) {
+  return {kLmsQ15, true, S->numTaps, S->mu, S->postShift, S->recipTable ? S->recipTable : armRecipTableQ15,
+          S->postShift <= 14};
+}
+
+// The inits set the fields and zero numTaps + blockSize - 1 state words (arm_lms_init_f32.c).
+template <typename T, typename Inst>
+void lms_init(Inst* S, uint16_t numTaps, T* pCoeffs, T* pState, T mu, uint32_t blockSize) {
+  S->numTaps = numTaps; S->pCoeffs = pCoeffs; S->pState = pState; S->mu = mu;
+  const size_t words = (size_t)numTaps + blockSize - 1;      // numTaps = blockSize = 0: none
+  if (pState && (numTaps || blockSize) && words) zero_words(pState, sizeof(T) * words, "arm_lms_init");
+}
+
+// Drop-in staging of the adaptive shape: two inputs (pSrc, pRef), two outputs (pOut, pErr), and the
+// coefficients, the history (the first numTaps - 1 words of pState) and, normalised, {energy, x0} both
+// in and out.  Every buffer lies on the host or the device; host ones go through scratch slots 2...8.
+// ex: the instance's {energy, x0} words, or nullptr.
+template <typename T>
+void adaptive_sync(const LmsParams& p, T* pCoeffs, T* pState, const T* pSrc, const T* pRef, T* pOut, T* pErr, uint32_t B,
+                   T* ex, const char* what) {
+  if (B == 0) return;
+  if (!pCoeffs || !pSrc || !pRef || !pOut || !pErr || p.taps == 0 || (p.taps > 1 && !pState) || !p.ok) {
+    set_error(hipErrorInvalidValue, what);
+    return;
+  }
+  hipStream_t st = sync_stream();
+  BlobScope hold(st);
+  const int16_t* drecip = nullptr;
+  if (p.recip) {
+    drecip = device_coeffs<int16_t>(p.recip, 64, what);
+    if (!drecip) return;
+  }
+  const size_t sb = sizeof(T) * (size_t)B, cb = sizeof(T) * (size_t)p.taps, hb = cb - sizeof(T), eb = 2 * sizeof(T);
+  const bool dco = is_device_ptr(pCoeffs), dst8 = hb && is_device_ptr(pState), dsrc = is_device_ptr(pSrc),
+             dref = is_device_ptr(pRef), dout = is_device_ptr(pOut), derr = is_device_ptr(pErr);
+  T* dc = dco ? pCoeffs : (T*)scratch(cb + 16, 2);
+  T* dh = (dst8 || !hb) ? pState : (T*)scratch(hb + 16, 3);
+  const T* dx = dsrc ? pSrc : (const T*)scratch(sb + 16, 4);
+  const T* dr = dref ? pRef : (const T*)scratch(sb + 16, 5);
+  T* dy = dout ? pOut : (T*)scratch(sb + 16, 6);
+  T* de = derr ? pErr : (T*)scratch(sb + 16, 7);
+  T* dex = ex ? (T*)scratch(eb + 16, 8) : nullptr;
+  if (!dc || (hb && !dh) || !dx || !dr || !dy || !de || (ex && !dex)) { set_error(hipErrorOutOfMemory, what); return; }
+  HostIO io(st);
+  hipError_t e = hipSuccess;
+  if (!dco) e = io.in(dc, pCoeffs, cb);
+  if (e == hipSuccess && hb && !dst8) e = io.in(dh, pState, hb);
+  if (e == hipSuccess && !dsrc) e = io.in((void*)dx, pSrc, sb);
+  if (e == hipSuccess && !dref) e = io.in((void*)dr, pRef, sb);
+  if (e == hipSuccess && ex) e = io.in(dex, ex, eb);
+  if (e == hipSuccess)
+    e = lms_run(p.op, p.norm, dx, dr, dy, de, B, 1, p.taps, dc, hb ? dh : nullptr, dex, p.mu, p.post_shift, drecip, st);
+  if (e == hipSuccess && !dout) e = io.out(pOut, dy, sb);
+  if (e == hipSuccess && !derr) e = io.out(pErr, de, sb);
+  if (e == hipSuccess && !dco) e = io.out(pCoeffs, dc, cb);
+  if (e == hipSuccess && hb && !dst8) e = io.out(pState, dh, hb);
+  if (e == hipSuccess && ex) e = io.out(ex, dex, eb);
+  if (e == hipSuccess) e = io.finish();
+  if (e == hipSuccess) hold.synced();
+  if (e != hipSuccess) set_error(e, what);
+}
+
+template <typename T>
+arm_status adaptive_batch(const LmsParams& p, const T* d_src, const T* d_ref, T* d_out, T* d_err, uint32_t B,
+                          uint32_t batch, T* d_coeffs, T* d_state, T* d_ex, void* stream, const char* what) {
+  if (p.taps == 0 || !p.ok || !d_src || !d_ref || !d_out || !d_err || !d_coeffs || (p.taps > 1 && !d_state) ||
+      (p.norm && !d_ex))
+    return ARM_MATH_ARGUMENT_ERROR;
+  if (!batch || !B) return ARM_MATH_SUCCESS;
+  BlobScope hold((hipStream_t)stream);
+  const int16_t* drecip = nullptr;
+  if (p.recip) {
+    drecip = device_coeffs<int16_t>(p.recip, 64, what);
+    if (!drecip) return ARM_MATH_ARGUMENT_ERROR;
+  }
+  return batch_status(lms_run(p.op, p.norm, d_src, d_ref, d_out, d_err, B, batch, p.taps, d_coeffs, d_state, d_ex, p.mu,
+                              p.post_shift, drecip, (hipStream_t)stream),
+                      what);
+}
+
 // ---- convolution / correlation family ------------------------------------------------
 // How each reference function maps onto one ConvJob (conv.hip):
 //   conv (exact):      x = pSrcA, h = pSrcB, all srcALen + srcBLen - 1 outputs forward;
@@ -1696,6 +1843,109 @@ void arm_biquad_cascade_df2T_init_f32(arm_biquad_cascade_df2T_instance_f32* S, u
 void arm_biquad_cascade_stereo_df2T_init_f32(arm_biquad_cascade_stereo_df2T_instance_f32* S, uint8_t numStages,
                                              const float32_t* pCoeffs, float32_t* pState) {
   biquad_init(S, numStages, pCoeffs, pState, 4, "arm_biquad_cascade_stereo_df2T_init_f32");
+}
+// IIR lattice
+#define MI355X_IIR_LATTICE(T, CT, OP)                                                                    \
+  void arm_iir_lattice_init_##T(arm_iir_lattice_instance_##T* S, uint16_t numStages, CT* pkCoeffs,      \
+                                CT* pvCoeffs, CT* pState, uint32_t blockSize) {                         \
+    iir_lattice_init(S, numStages, pkCoeffs, pvCoeffs, pState, blockSize);                              \
+  }                                                                                                     \
+  void arm_iir_lattice_##T(const arm_iir_lattice_instance_##T* S, const CT* pSrc, CT* pDst, uint32_t blockSize) { \
+    iir_lattice_sync(S, pSrc, pDst, blockSize, OP, "arm_iir_lattice_" #T);                              \
+  }                                                                                                     \
+  arm_status arm_iir_lattice_##T##_batch(const arm_iir_lattice_instance_##T* S, const CT* d_src, CT* d_dst, \
+                                         uint32_t blockSize, uint32_t batch, CT* d_state, void* stream) { \
+    return iir_lattice_batch(S, d_src, d_dst, blockSize, batch, d_state, stream, OP, "arm_iir_lattice_" #T "_batch"); \
+  }
+MI355X_IIR_LATTICE(f32, float32_t, kIirF32)
+MI355X_IIR_LATTICE(q31, q31_t, kIirQ31)
+MI355X_IIR_LATTICE(q15, q15_t, kIirQ15)
+#undef MI355X_IIR_LATTICE
+// Initial values of arm_recip_q15: the mean of the reciprocals of the ends of [1 + i/64, 1 + (i+1)/64]
+// in q15 with one integer bit, floor(2^20 (129 + 2 i) / ((64 + i)(65 + i))).
+#define MI355X_R1(i) (int16_t)((1048576u * (129u + 2u * (i))) / ((64u + (i)) * (65u + (i))))
+#define MI355X_R4(i) MI355X_R1(i), MI355X_R1((i) + 1u), MI355X_R1((i) + 2u), MI355X_R1((i) + 3u)
+#define MI355X_R16(i) MI355X_R4(i), MI355X_R4((i) + 4u), MI355X_R4((i) + 8u), MI355X_R4((i) + 12u)
+const int16_t armRecipTableQ15[64] = {MI355X_R16(0u), MI355X_R16(16u), MI355X_R16(32u), MI355X_R16(48u)};
+#undef MI355X_R16
+#undef MI355X_R4
+#undef MI355X_R1
+// LMS: KIND lms | lms_norm, SC const for the plain kinds, EX the instance's {energy, x0} words
+#define MI355X_LMS(KIND, T, CT, SC, EXIN, EXOUT)                                                            \
+  void arm_##KIND##_##T(SC arm_##KIND##_instance_##T* S, const CT* pSrc, CT* pRef, CT* pOut, CT* pErr,     \
+                        uint32_t blockSize) {                                                               \
+    if (!S) return;                                                                                         \
+    CT ex[2] = {0, 0};                                                                                      \
+    CT* pex = nullptr;                                                                                      \
+    EXIN;                                                                                                   \
+    adaptive_sync<CT>(lms_params(S), S->pCoeffs, S->pState, pSrc, pRef, pOut, pErr, blockSize, pex,         \
+                      "arm_" #KIND "_" #T);                                                                 \
+    EXOUT;                                                                                                  \
+  }
+#define MI355X_EX_IN ex[0] = S->energy; ex[1] = S->x0; pex = ex
+#define MI355X_EX_OUT S->energy = ex[0]; S->x0 = ex[1]
+MI355X_LMS(lms, f32, float32_t, const, (void)ex, (void)pex)
+MI355X_LMS(lms, q31, q31_t, const, (void)ex, (void)pex)
+MI355X_LMS(lms, q15, q15_t, const, (void)ex, (void)pex)
+MI355X_LMS(lms_norm, f32, float32_t, , MI355X_EX_IN, MI355X_EX_OUT)
+MI355X_LMS(lms_norm, q15, q15_t, , MI355X_EX_IN, MI355X_EX_OUT)
+#undef MI355X_EX_OUT
+#undef MI355X_EX_IN
+#undef MI355X_LMS
+#define MI355X_LMS_BATCH(KIND, T, CT)                                                                       \
+  arm_status arm_##KIND##_##T##_batch(const arm_##KIND##_instance_##T* S, const CT* d_src, const CT* d_ref, \
+                                      CT* d_out, CT* d_err, uint32_t blockSize, uint32_t batch, CT* d_coeffs, \
+                                      CT* d_state, void* stream) {                                          \
+    if (!S) return ARM_MATH_ARGUMENT_ERROR;                                                                 \
+    return adaptive_batch<CT>(lms_params(S), d_src, d_ref, d_out, d_err, blockSize, batch, d_coeffs, d_state, \
+                              nullptr, stream, "arm_" #KIND "_" #T "_batch");                               \
+  }
+MI355X_LMS_BATCH(lms, f32, float32_t)
+MI355X_LMS_BATCH(lms, q31, q31_t)
+MI355X_LMS_BATCH(lms, q15, q15_t)
+#undef MI355X_LMS_BATCH
+#define MI355X_LMS_NORM_BATCH(T, CT)                                                                        \
+  arm_status arm_lms_norm_##T##_batch(const arm_lms_norm_instance_##T* S, const CT* d_src, const CT* d_ref, \
+                                      CT* d_out, CT* d_err, uint32_t blockSize, uint32_t batch, CT* d_coeffs, \
+                                      CT* d_state, CT* d_energy_x0, void* stream) {                         \
+    if (!S) return ARM_MATH_ARGUMENT_ERROR;                                                                 \
+    return adaptive_batch<CT>(lms_params(S), d_src, d_ref, d_out, d_err, blockSize, batch, d_coeffs, d_state, \
+                              d_energy_x0, stream, "arm_lms_norm_" #T "_batch");                            \
+  }
+MI355X_LMS_NORM_BATCH(f32, float32_t)
+MI355X_LMS_NORM_BATCH(q15, q15_t)
+#undef MI355X_LMS_NORM_BATCH
+void arm_lms_init_f32(arm_lms_instance_f32* S, uint16_t numTaps, float32_t* pCoeffs, float32_t* pState, float32_t mu,
+                      uint32_t blockSize) {
+  if (S) lms_init(S, numTaps, pCoeffs, pState, mu, blockSize);
+}
+void arm_lms_init_q31(arm_lms_instance_q31* S, uint16_t numTaps, q31_t* pCoeffs, q31_t* pState, q31_t mu,
+                      uint32_t blockSize, uint32_t postShift) {
+  if (!S) return;
+  lms_init(S, numTaps, pCoeffs, pState, mu, blockSize);
+  S->postShift = postShift;
+}
+void arm_lms_init_q15(arm_lms_instance_q15* S, uint16_t numTaps, q15_t* pCoeffs, q15_t* pState, q15_t mu,
+                      uint32_t blockSize, uint32_t postShift) {
+  if (!S) return;
+  lms_init(S, numTaps, pCoeffs, pState, mu, blockSize);
+  S->postShift = postShift;
+}
+void arm_lms_norm_init_f32(arm_lms_norm_instance_f32* S, uint16_t numTaps, float32_t* pCoeffs, float32_t* pState,
+                           float32_t mu, uint32_t blockSize) {
+  if (!S) return;
+  lms_init(S, numTaps, pCoeffs, pState, mu, blockSize);
+  S->energy = 0.0f;
+  S->x0 = 0.0f;
+}
+void arm_lms_norm_init_q15(arm_lms_norm_instance_q15* S, uint16_t numTaps, q15_t* pCoeffs, q15_t* pState, q15_t mu,
+                           uint32_t blockSize, uint8_t postShift) {
+  if (!S) return;
+  lms_init(S, numTaps, pCoeffs, pState, mu, blockSize);
+  S->postShift = postShift;
+  S->recipTable = armRecipTableQ15;
+  S->energy = 0;
+  S->x0 = 0;
 }
 void arm_fir_sparse_f32(arm_fir_sparse_instance_f32* S, const float32_t* pSrc, float32_t* pDst, float32_t* pScratchIn,
                         uint32_t blockSize) {

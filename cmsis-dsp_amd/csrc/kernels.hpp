@@ -156,6 +156,19 @@ enum BqOp { kBqDf1F32 = 0, kBqDf1Q31 = 1, kBqDf1FastQ31 = 2, kBqDf1Q15 = 3, kBqD
             kBqDf2TF32 = 6, kBqStereoDf2TF32 = 7 };
 hipError_t biquad_run(int op, const void* coeffs, uint32_t num_stages, int post_shift, const void* src, void* dst,
                       uint32_t block_size, uint32_t batch, void* state, hipStream_t st);
+// IIR lattice (iir_lattice.hip): `batch` streams sharing pk (num_stages reflection words) and pv
+// (num_stages + 1 ladder words); state [batch][num_stages], the reference's live words, updated in place.
+enum IirOp { kIirF32 = 0, kIirQ31 = 1, kIirQ15 = 2 };
+hipError_t iir_lattice_run(int op, const void* pk, const void* pv, int num_stages, const void* src, void* dst,
+                           uint32_t block_size, uint32_t batch, void* state, hipStream_t st);
+// LMS / normalised LMS (lms.hip): per stream coeffs [batch][num_taps] (time-reversed, updated), state
+// [batch][num_taps - 1] (oldest first, updated) and, normalised, energy_x0 [batch][2] words {energy, x0};
+// mu is the type's word (f32: its bits); recip_table: the 64 device words of armRecipTableQ15 (q15
+// normalised only).  kLmsQ31 has no normalised form here.
+enum LmsOp { kLmsF32 = 0, kLmsQ31 = 1, kLmsQ15 = 2 };
+hipError_t lms_run(int op, bool norm, const void* src, const void* ref, void* out, void* err, uint32_t block_size,
+                   uint32_t batch, int num_taps, void* coeffs, void* state, void* energy_x0, int32_t mu,
+                   int32_t post_shift, const int16_t* recip_table, hipStream_t st);
 
 // MFCC f32 around the batched RFFT (mfcc_f32.hip): frame normalisation + window, then the
 // spectrum -> Mel -> log -> DCT tail.  post needs mfcc_f32_post_lds(n, nb_mel) bytes of LDS.

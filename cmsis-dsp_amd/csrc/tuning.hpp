@@ -141,6 +141,26 @@
 #define MI355X_BQ_NS2_FX 16
 #endif
 
+// ---- iir_lattice.hip / lms.hip (one lane per stream, one wave per workgroup)
+#ifndef MI355X_IIR_TS
+#define MI355X_IIR_TS 32   // samples per I/O tile row (one 128-B row segment per f32 stream)
+#endif
+#ifndef MI355X_IIR_REG
+#define MI355X_IIR_REG 32  // most stages with state, k and v in registers (further instances serve <= 4, 8, 16)
+#endif
+#ifndef MI355X_IIR_LDS
+#define MI355X_IIR_LDS 128 // most stages with the state in LDS (256 B per stage and wave); beyond: d_state in place
+#endif
+#ifndef MI355X_LMS_TS
+#define MI355X_LMS_TS 32
+#endif
+#ifndef MI355X_LMS_REG
+#define MI355X_LMS_REG 32  // most taps with coefficients and window in registers (further instances serve <= 4, 8, 16)
+#endif
+#ifndef MI355X_LMS_LDS
+#define MI355X_LMS_LDS 64  // most taps with coefficients and ring in LDS (512 B per tap and wave); beyond: global
+#endif
+
 // ---- mat_mult_fixed.hip
 #ifndef MI355X_I8_SCHED
 #define MI355X_I8_SCHED 10

@@ -89,6 +89,10 @@ extern const uint16_t armBitRevIndexTable_fixed_1024[ARMBITREVINDEXTABLE_FIXED_1
 extern const uint16_t armBitRevIndexTable_fixed_2048[ARMBITREVINDEXTABLE_FIXED_2048_TABLE_LENGTH];
 extern const uint16_t armBitRevIndexTable_fixed_4096[ARMBITREVINDEXTABLE_FIXED_4096_TABLE_LENGTH];
 
+/* Initial values of arm_recip_q15 (Include/dsp/utils.h), the table arm_lms_norm_init_q15 points
+ * S->recipTable at: entry i = floor(2^20 (129 + 2 i) / ((64 + i)(65 + i))). */
+extern const int16_t armRecipTableQ15[64];   /* q15_t words */
+
 #ifdef __cplusplus
 }
 #endif

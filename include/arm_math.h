@@ -305,6 +305,63 @@ typedef struct {
   const float32_t *pCoeffs;  /* 5*numStages */
 } arm_biquad_cascade_stereo_df2T_instance_f32;
 
+/* IIR lattice instances (Include/dsp/filtering_functions.h:1428-1458).  pState: numStages + blockSize
+ * words, of which the first numStages are the live state between calls; pkCoeffs: numStages reflection
+ * words; pvCoeffs: numStages + 1 ladder words. */
+#define MI355X_IIR_LATTICE_INST(T, CT)                                        \
+  typedef struct {                                                            \
+    uint16_t numStages;                                                       \
+    CT *pState;                                                               \
+    CT *pkCoeffs;                                                             \
+    CT *pvCoeffs;                                                             \
+  } arm_iir_lattice_instance_##T;
+MI355X_IIR_LATTICE_INST(q15, q15_t)
+MI355X_IIR_LATTICE_INST(q31, q31_t)
+MI355X_IIR_LATTICE_INST(f32, float32_t)
+#undef MI355X_IIR_LATTICE_INST
+
+/* LMS / normalised LMS instances (filtering_functions.h:1560-1566, :1608-1615, :1659-1666, :1710-1718,
+ * :1813-1824).  pState: numTaps + blockSize - 1 words, of which the first numTaps - 1 are the live
+ * history (oldest first) between calls; pCoeffs: numTaps words, time-reversed, updated in place. */
+typedef struct {
+  uint16_t   numTaps;
+  float32_t *pState;
+  float32_t *pCoeffs;
+  float32_t  mu;
+} arm_lms_instance_f32;
+typedef struct {
+  uint16_t numTaps;
+  q15_t   *pState;
+  q15_t   *pCoeffs;
+  q15_t    mu;
+  uint32_t postShift;
+} arm_lms_instance_q15;
+typedef struct {
+  uint16_t numTaps;
+  q31_t   *pState;
+  q31_t   *pCoeffs;
+  q31_t    mu;
+  uint32_t postShift;
+} arm_lms_instance_q31;
+typedef struct {
+  uint16_t   numTaps;
+  float32_t *pState;
+  float32_t *pCoeffs;
+  float32_t  mu;
+  float32_t  energy;
+  float32_t  x0;
+} arm_lms_norm_instance_f32;
+typedef struct {
+        uint16_t numTaps;
+        q15_t   *pState;
+        q15_t   *pCoeffs;
+        q15_t    mu;
+        uint8_t  postShift;
+  const q15_t   *recipTable;   /* armRecipTableQ15 (arm_common_tables.h) */
+        q15_t    energy;
+        q15_t    x0;
+} arm_lms_norm_instance_q15;
+
 /* ---- matrix instances: Include/dsp/matrix_functions.h:118-123 (f32), :139-143 (q7),
  * :139-144 (q15), :149-154 (q31) */
 typedef struct {
@@ -689,6 +746,54 @@ void arm_biquad_cascade_stereo_df2T_init_f32(arm_biquad_cascade_stereo_df2T_inst
                                              const float32_t *pCoeffs, float32_t *pState);
 void arm_biquad_cascade_stereo_df2T_f32(const arm_biquad_cascade_stereo_df2T_instance_f32 *S, const float32_t *pSrc,
                                         float32_t *pDst, uint32_t blockSize);
+
+/* ===================================================================================
+ * IIR lattice.  Prototypes: Include/dsp/filtering_functions.h:1468-1554.  Reference bodies:
+ * Source/FilteringFunctions/arm_iir_lattice_{f32,q31,q15}.c (scalar path); the inits set the fields
+ * and zero numStages + blockSize state words.  pDst == pSrc is allowed.  After a call the first
+ * numStages state words are the reference's; the remaining blockSize words are its scratch and are
+ * left as they were.
+ * =================================================================================== */
+void arm_iir_lattice_init_f32(arm_iir_lattice_instance_f32 *S, uint16_t numStages, float32_t *pkCoeffs,
+                              float32_t *pvCoeffs, float32_t *pState, uint32_t blockSize);
+void arm_iir_lattice_f32(const arm_iir_lattice_instance_f32 *S, const float32_t *pSrc, float32_t *pDst,
+                         uint32_t blockSize);
+void arm_iir_lattice_init_q31(arm_iir_lattice_instance_q31 *S, uint16_t numStages, q31_t *pkCoeffs, q31_t *pvCoeffs,
+                              q31_t *pState, uint32_t blockSize);
+void arm_iir_lattice_q31(const arm_iir_lattice_instance_q31 *S, const q31_t *pSrc, q31_t *pDst, uint32_t blockSize);
+void arm_iir_lattice_init_q15(arm_iir_lattice_instance_q15 *S, uint16_t numStages, q15_t *pkCoeffs, q15_t *pvCoeffs,
+                              q15_t *pState, uint32_t blockSize);
+void arm_iir_lattice_q15(const arm_iir_lattice_instance_q15 *S, const q15_t *pSrc, q15_t *pDst, uint32_t blockSize);
+
+/* ===================================================================================
+ * LMS and normalised LMS adaptive filters.  Prototypes: filtering_functions.h:1578-1704, :1730-1762,
+ * :1836-1864.  Reference bodies: Source/FilteringFunctions/arm_lms_{f32,q31,q15}.c,
+ * arm_lms_norm_{f32,q15}.c (scalar path); the inits set the fields and zero numTaps + blockSize - 1
+ * state words.  S->pCoeffs is updated in place; the normalised kinds write S->energy and S->x0 back.
+ * pOut == pSrc and pErr == pRef are allowed.  A postShift for which the reference's shift counts leave
+ * 0...31 (q15: > 14, q31: > 30) is refused through arm_mi355x_last_error.  arm_lms_norm_q31 is not
+ * provided.
+ * =================================================================================== */
+void arm_lms_init_f32(arm_lms_instance_f32 *S, uint16_t numTaps, float32_t *pCoeffs, float32_t *pState, float32_t mu,
+                      uint32_t blockSize);
+void arm_lms_f32(const arm_lms_instance_f32 *S, const float32_t *pSrc, float32_t *pRef, float32_t *pOut,
+                 float32_t *pErr, uint32_t blockSize);
+void arm_lms_init_q31(arm_lms_instance_q31 *S, uint16_t numTaps, q31_t *pCoeffs, q31_t *pState, q31_t mu,
+                      uint32_t blockSize, uint32_t postShift);
+void arm_lms_q31(const arm_lms_instance_q31 *S, const q31_t *pSrc, q31_t *pRef, q31_t *pOut, q31_t *pErr,
+                 uint32_t blockSize);
+void arm_lms_init_q15(arm_lms_instance_q15 *S, uint16_t numTaps, q15_t *pCoeffs, q15_t *pState, q15_t mu,
+                      uint32_t blockSize, uint32_t postShift);
+void arm_lms_q15(const arm_lms_instance_q15 *S, const q15_t *pSrc, q15_t *pRef, q15_t *pOut, q15_t *pErr,
+                 uint32_t blockSize);
+void arm_lms_norm_init_f32(arm_lms_norm_instance_f32 *S, uint16_t numTaps, float32_t *pCoeffs, float32_t *pState,
+                           float32_t mu, uint32_t blockSize);
+void arm_lms_norm_f32(arm_lms_norm_instance_f32 *S, const float32_t *pSrc, float32_t *pRef, float32_t *pOut,
+                      float32_t *pErr, uint32_t blockSize);
+void arm_lms_norm_init_q15(arm_lms_norm_instance_q15 *S, uint16_t numTaps, q15_t *pCoeffs, q15_t *pState, q15_t mu,
+                           uint32_t blockSize, uint8_t postShift);
+void arm_lms_norm_q15(arm_lms_norm_instance_q15 *S, const q15_t *pSrc, q15_t *pRef, q15_t *pOut, q15_t *pErr,
+                      uint32_t blockSize);
 
 /* ===================================================================================
  * Convolution.  Prototypes: Include/dsp/filtering_functions.h

@@ -186,6 +186,43 @@ arm_status arm_biquad_cascade_stereo_df2T_f32_batch(const arm_biquad_cascade_ste
                                                     const float32_t *d_src, float32_t *d_dst, uint32_t blockSize,
                                                     uint32_t batch, float32_t *d_state, void *stream);
 
+/* IIR lattice over `batch` independent streams sharing S's pkCoeffs / pvCoeffs (host pointers, content-
+ * cached, or device pointers): d_src / d_dst [batch][blockSize], d_state [batch][numStages], each
+ * stream's live state words as the drop-in leaves them at the head of pState; zero-initialise to start
+ * a stream; updated in place, so consecutive calls equal one long call.  S->pState is unused.
+ * d_src == d_dst is allowed.  numStages == 0 or a NULL pointer: ARM_MATH_ARGUMENT_ERROR; blockSize == 0
+ * or batch == 0: success, nothing touched. */
+arm_status arm_iir_lattice_f32_batch(const arm_iir_lattice_instance_f32 *S, const float32_t *d_src, float32_t *d_dst,
+                                     uint32_t blockSize, uint32_t batch, float32_t *d_state, void *stream);
+arm_status arm_iir_lattice_q31_batch(const arm_iir_lattice_instance_q31 *S, const q31_t *d_src, q31_t *d_dst,
+                                     uint32_t blockSize, uint32_t batch, q31_t *d_state, void *stream);
+arm_status arm_iir_lattice_q15_batch(const arm_iir_lattice_instance_q15 *S, const q15_t *d_src, q15_t *d_dst,
+                                     uint32_t blockSize, uint32_t batch, q15_t *d_state, void *stream);
+
+/* LMS / normalised LMS over `batch` independent adaptive filters: d_src / d_ref / d_out / d_err
+ * [batch][blockSize]; d_coeffs [batch][numTaps], each stream's own taps (time-reversed), read and
+ * updated; d_state [batch][numTaps - 1], the previous samples, oldest first (may be NULL when
+ * numTaps == 1), updated; normalised: d_energy_x0 [batch][2] words {energy, x0}, updated.  numTaps, mu
+ * and postShift come from S (the q15 normalised kind reads S->recipTable, NULL = armRecipTableQ15);
+ * S->pCoeffs, S->pState, S->energy and S->x0 are unused.  d_out == d_src and d_err == d_ref are allowed.
+ * numTaps == 0, a NULL pointer or a postShift outside the reference's defined range:
+ * ARM_MATH_ARGUMENT_ERROR; blockSize == 0 or batch == 0: success, nothing touched. */
+arm_status arm_lms_f32_batch(const arm_lms_instance_f32 *S, const float32_t *d_src, const float32_t *d_ref,
+                             float32_t *d_out, float32_t *d_err, uint32_t blockSize, uint32_t batch,
+                             float32_t *d_coeffs, float32_t *d_state, void *stream);
+arm_status arm_lms_q31_batch(const arm_lms_instance_q31 *S, const q31_t *d_src, const q31_t *d_ref, q31_t *d_out,
+                             q31_t *d_err, uint32_t blockSize, uint32_t batch, q31_t *d_coeffs, q31_t *d_state,
+                             void *stream);
+arm_status arm_lms_q15_batch(const arm_lms_instance_q15 *S, const q15_t *d_src, const q15_t *d_ref, q15_t *d_out,
+                             q15_t *d_err, uint32_t blockSize, uint32_t batch, q15_t *d_coeffs, q15_t *d_state,
+                             void *stream);
+arm_status arm_lms_norm_f32_batch(const arm_lms_norm_instance_f32 *S, const float32_t *d_src, const float32_t *d_ref,
+                                  float32_t *d_out, float32_t *d_err, uint32_t blockSize, uint32_t batch,
+                                  float32_t *d_coeffs, float32_t *d_state, float32_t *d_energy_x0, void *stream);
+arm_status arm_lms_norm_q15_batch(const arm_lms_norm_instance_q15 *S, const q15_t *d_src, const q15_t *d_ref,
+                                  q15_t *d_out, q15_t *d_err, uint32_t blockSize, uint32_t batch, q15_t *d_coeffs,
+                                  q15_t *d_state, q15_t *d_energy_x0, void *stream);
+
 /* Convolution of `batch` pairs: item i convolves d_a + i*strideA (srcALen samples) with
  * d_b + i*strideB (srcBLen samples; strideB = 0 shares one kernel) into
  * d_dst + i*(srcALen + srcBLen - 1).  Per-item semantics: arm_conv_f32 / _q15 / _q31. */
