@@ -495,6 +495,25 @@ def arm_mat_mult_q15(pSrcA, pSrcB, pState=None):
     return _amd.arm_mat_mult_fixed("q15", _arr(pSrcA, _np.int16), _arr(pSrcB, _np.int16))
 
 
+def arm_mat_cmplx_mult_f32(pSrcA, pSrcB):
+    """cmsisdsp_matrix.c cmsis_arm_mat_cmplx_mult_f32 (:661-690): real arrays [M, 2K], [K, 2N] of
+    interleaved (re, im) words -> (status, C [M, 2N])."""
+    return _amd.arm_mat_cmplx_mult("f32", _arr(pSrcA, _np.float32), _arr(pSrcB, _np.float32))
+
+
+def arm_mat_cmplx_mult_q31(pSrcA, pSrcB):
+    """cmsisdsp_matrix.c cmsis_arm_mat_cmplx_mult_q31 (:729-760)."""
+    return _amd.arm_mat_cmplx_mult("q31", _arr(pSrcA, _np.int32), _arr(pSrcB, _np.int32))
+
+
+def arm_mat_cmplx_mult_q15(pSrcA, pSrcB, pScratch):
+    """cmsisdsp_matrix.c cmsis_arm_mat_cmplx_mult_q15 ("OOO" -> (status, C), :692-727).  The wrapper
+    converts pScratch to a private q15 buffer and frees it, so the caller's array is left as it is;
+    here the library writes B transposed into a buffer of the size it needs."""
+    b = _arr(pSrcB, _np.int16)
+    return _amd.arm_mat_cmplx_mult("q15", _arr(pSrcA, _np.int16), b, _np.zeros(max(b.size, 1), dtype=_np.int16))
+
+
 def arm_mat_mult_fast_q31(pSrcA, pSrcB):
     """cmsisdsp_matrix.c cmsis_arm_mat_mult_fast_q31: (status, C)."""
     return _amd.arm_mat_mult_fixed("fast_q31", _arr(pSrcA, _np.int32), _arr(pSrcB, _np.int32))

@@ -50,6 +50,7 @@ def _load():
     _abi.bind(lib, _abi.PARTIAL_FAST)
     _abi.bind(lib, _abi.BIQUAD)
     _abi.bind(lib, _abi.ADAPTIVE)
+    _abi.bind(lib, _abi.CMPLX_MAT)
     _abi.bind(lib, _abi.BATCHED)
     return lib
 
@@ -521,6 +522,28 @@ def mat_mult_batch_multi(shards):
         raise RuntimeError(f"{fn.__name__} -> {st}: {last_error()[1]}")
 
 
+def mat_cmplx_mult_batch_multi(shards):
+    """The complex product per shard through one arm_mat_cmplx_mult_*_batch_multi call (synchronous):
+    shards = [(a, b, c), ...] with [batch_s, M, 2K] x [batch_s, K, 2N] -> [batch_s, M, 2N] tensors of
+    interleaved (re, im) words on each shard's device (f32 / int16 / int32)."""
+    import torch
+    a0, b0, _ = shards[0]
+    m, k_, n = a0.shape[1], b0.shape[1], b0.shape[2] // 2
+    kind = {torch.float32: "f32", torch.int16: "q15", torch.int32: "q31"}[a0.dtype]
+    inst = _abi.CMPLX_MAT_INST[kind]
+    for d in sorted({t[0].device.index for t in shards}):
+        torch.cuda.synchronize(d)
+    k = len(shards)
+    A, B, Cm = inst(m, a0.shape[2] // 2, None), inst(k_, n, None), inst(m, n, None)
+    devs = (C.c_int * k)(*[t[0].device.index for t in shards])
+    pa, pb, pc = ((C.c_void_p * k)(*[t[i].data_ptr() for t in shards]) for i in range(3))
+    cnts = (C.c_uint32 * k)(*[t[0].shape[0] for t in shards])
+    fn = getattr(lib, f"arm_mat_cmplx_mult_{kind}_batch_multi")
+    st = fn(C.byref(A), C.byref(B), C.byref(Cm), k, devs, pa, pb, pc, cnts)
+    if st != ARM_MATH_SUCCESS:
+        raise RuntimeError(f"{fn.__name__} -> {st}: {last_error()[1]}")
+
+
 def arm_conv(kind, a, b):
     """arm_conv_f32 / _q15 / _q31 / _q7 (drop-in, numpy): len(a) + len(b) - 1 samples."""
     dt = {"f32": np.float32, "q15": np.int16, "q31": np.int32, "q7": np.int8}[kind]
@@ -599,6 +622,44 @@ def arm_mat_mult_fixed(kind, a, b):
         fn(C.byref(A), C.byref(B), C.byref(Cm))
     _check_void(f"arm_mat_mult_{kind}")
     return st, c
+
+
+def arm_mat_cmplx_mult(kind, a, b, scratch=None):
+    """(status, C) through arm_mat_cmplx_mult_f32 / _q31 / _q15 (kind "f32", "q31", "q15"): a [M, 2K] and
+    b [K, 2N] hold interleaved (re, im) words, C is [M, 2N].  scratch (q15 only): an int16 array of
+    2 K N words that receives B transposed, as the reference's pScratch does; None passes NULL."""
+    dt = {"f32": np.float32, "q15": np.int16, "q31": np.int32}[kind]
+    inst = _abi.CMPLX_MAT_INST[kind]
+    a = np.ascontiguousarray(a, dtype=dt)
+    b = np.ascontiguousarray(b, dtype=dt)
+    c = np.zeros((a.shape[0], b.shape[1]), dtype=dt)
+    ptr = {"f32": _abi.c_f32p, "q15": _abi.c_i16p, "q31": _abi.c_i32p}[kind]
+    A, B, Cm = (inst(x.shape[0], x.shape[1] // 2, C.cast(x.ctypes.data, ptr)) for x in (a, b, c))
+    fn = getattr(lib, f"arm_mat_cmplx_mult_{kind}")
+    args = [C.byref(A), C.byref(B), C.byref(Cm)]
+    if kind == "q15":
+        args.append(None if scratch is None else scratch.ctypes.data)
+    st = fn(*args)
+    _check_void(f"arm_mat_cmplx_mult_{kind}")
+    return st, c
+
+
+def mat_cmplx_mult_batch(a, b, c, stream=None):
+    """The complex product c[i] = a[i] b[i] for device tensors [batch, M, 2K] x [batch, K, 2N] ->
+    [batch, M, 2N] of interleaved (re, im) words; float32 -> arm_mat_cmplx_mult_f32_batch, int16 -> _q15,
+    int32 -> _q31."""
+    import torch
+    batch, m, k2 = a.shape
+    n2 = b.shape[2]
+    kind, ptr = {torch.float32: ("f32", _abi.c_f32p), torch.int16: ("q15", _abi.c_i16p),
+                 torch.int32: ("q31", _abi.c_i32p)}[a.dtype]
+    inst = _abi.CMPLX_MAT_INST[kind]
+    A, B, Cm = inst(m, k2 // 2, C.cast(a.data_ptr(), ptr)), inst(b.shape[1], n2 // 2, C.cast(b.data_ptr(), ptr)), \
+        inst(c.shape[1], c.shape[2] // 2, C.cast(c.data_ptr(), ptr))
+    fn = getattr(lib, f"arm_mat_cmplx_mult_{kind}_batch")
+    st = fn(C.byref(A), C.byref(B), C.byref(Cm), batch, _stream_ptr(stream))
+    if st != ARM_MATH_SUCCESS:
+        raise RuntimeError(f"{fn.__name__} -> {st}: {last_error()[1]}")
 
 
 def mat_mult_batch(a, b, c, stream=None, fast=False):

@@ -337,6 +337,15 @@ for _f, (_inst, _init, _extra) in ADAPTIVE_FUNCS.items():
         ADAPTIVE[_f] = (None, [P(_inst), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32])
         ADAPTIVE[_init] = (None, [P(_inst), C.c_uint16, C.c_void_p, C.c_void_p, _extra[0], C.c_uint32] + _extra[1:])
 
+# Complex matrix multiply: the drop-ins (q15 takes pScratch), the batched and the multi-shard forms.  The
+# product only, as BIQUAD (tests/golden/cmplx_mat.npz holds the reference's outputs).
+CMPLX_MAT_INST = {"f32": arm_matrix_instance_f32, "q31": arm_matrix_instance_q31, "q15": arm_matrix_instance_q15}
+CMPLX_MAT = {}
+for _t, _inst in CMPLX_MAT_INST.items():
+    CMPLX_MAT[f"arm_mat_cmplx_mult_{_t}"] = (C.c_int, [P(_inst)] * 3 + ([C.c_void_p] if _t == "q15" else []))
+    CMPLX_MAT[f"arm_mat_cmplx_mult_{_t}_batch"] = (C.c_int, [P(_inst)] * 3 + [C.c_uint32, C.c_void_p])
+    CMPLX_MAT[f"arm_mat_cmplx_mult_{_t}_batch_multi"] = (C.c_int, [P(_inst)] * 3 + [C.c_uint32] + [C.c_void_p] * 5)
+
 # per-length MFCC init functions (the product and the reference build; the oracle has the
 # generic init only)
 MFCC_LEN = {f"arm_mfcc_init_{n}_f32": (C.c_int, [P(arm_mfcc_instance_f32), C.c_uint32, C.c_uint32, C.c_void_p,

@@ -1218,13 +1218,18 @@ arm_status mat_batch_multi(const M* pSrcA, const M* pSrcB, M* pDst, uint32_t nsh
   });
 }
 
-// drop-in matrix multiply (host or device operands), synchronous; launch as for mat_batch_multi
+// drop-in matrix multiply (host or device operands), synchronous; launch as for mat_batch_multi.
+// words: T words per element (2: interleaved complex).  bt (complex q15 only, host or device, may
+// be null): receives B transposed, the n rows of k complex words that arm_mat_cmplx_mult_q15 leaves
+// in pScratch.
 template <typename T, typename M, typename Launch>
-arm_status mat_mult_sync(const M* pSrcA, const M* pSrcB, M* pDst, const char* what, Launch&& launch) {
+arm_status mat_mult_sync(const M* pSrcA, const M* pSrcB, M* pDst, const char* what, Launch&& launch, int words = 1,
+                         T* bt = nullptr) {
   if (!pSrcA || !pSrcB || !pDst) return ARM_MATH_ARGUMENT_ERROR;
   if (!mat_shapes_ok(pSrcA, pSrcB, pDst)) return ARM_MATH_SIZE_MISMATCH;
   const int m = pSrcA->numRows, k = pSrcA->numCols, n = pSrcB->numCols;
-  const size_t ab = sizeof(T) * (size_t)m * k, bb = sizeof(T) * (size_t)k * n, cb = sizeof(T) * (size_t)m * n;
+  const size_t ab = sizeof(T) * (size_t)m * k * words, bb = sizeof(T) * (size_t)k * n * words,
+               cb = sizeof(T) * (size_t)m * n * words;
   hipStream_t st = sync_stream();
   const bool da = is_device_ptr(pSrcA->pData), db = is_device_ptr(pSrcB->pData), dc = is_device_ptr(pDst->pData);
   T* A = da ? pSrcA->pData : (T*)scratch(ab + 16, 0);
@@ -1237,6 +1242,15 @@ arm_status mat_mult_sync(const M* pSrcA, const M* pSrcB, M* pDst, const char* wh
   if (e == hipSuccess && !db) e = io.in(B, pSrcB->pData, bb);
   if (e == hipSuccess) e = launch(m, k, n, A, B, Cd, 1, st);
   if (e == hipSuccess && !dc) e = io.out(pDst->pData, Cd, cb);
+  if constexpr (sizeof(T) == 2) {
+    if (e == hipSuccess && bt && bb) {
+      const bool dt = is_device_ptr(bt);
+      T* Bt = dt ? bt : (T*)scratch(bb, 3);
+      if (!Bt) e = hipErrorOutOfMemory;
+      if (e == hipSuccess) e = mat_cmplx_trans_q15_launch(k, n, B, Bt, st);
+      if (e == hipSuccess && !dt) e = io.out(bt, Bt, bb);
+    }
+  }
   if (e == hipSuccess) e = io.finish();
   return batch_status(e, what);
 }
@@ -1598,6 +1612,41 @@ MI355X_MAT_BATCH(arm_mat_mult_q31_batch, arm_matrix_instance_q31, mat_mult_q31_l
 MI355X_MAT_BATCH(arm_mat_mult_fast_q15_batch, arm_matrix_instance_q15, mat_mult_fast_q15_launch)
 MI355X_MAT_BATCH(arm_mat_mult_fast_q31_batch, arm_matrix_instance_q31, mat_mult_fast_q31_launch)
 #undef MI355X_MAT_BATCH
+
+// ---- complex matrix multiply f32 / q31 / q15 ----------------------------------------
+// arm_mat_cmplx_mult_f32.c:1225-1392, arm_mat_cmplx_mult_q31.c:836-1057 (scalar branch: wrapping q63
+// sums, clip_q63_to_q31(sum >> 31)), arm_mat_cmplx_mult_q15.c:433-582 (!ARM_MATH_DSP: q63 sums,
+// __SSAT(sum >> 15, 16); B is first transposed into pScratch, which the call leaves there).
+// numRows / numCols count complex elements; pData holds interleaved (re, im) words.
+arm_status arm_mat_cmplx_mult_f32(const arm_matrix_instance_f32* pSrcA, const arm_matrix_instance_f32* pSrcB,
+                                  arm_matrix_instance_f32* pDst) {
+  return mat_mult_sync<float>(pSrcA, pSrcB, pDst, "arm_mat_cmplx_mult_f32", mat_cmplx_mult_f32_launch, 2);
+}
+arm_status arm_mat_cmplx_mult_q31(const arm_matrix_instance_q31* pSrcA, const arm_matrix_instance_q31* pSrcB,
+                                  arm_matrix_instance_q31* pDst) {
+  return mat_mult_sync<int32_t>(pSrcA, pSrcB, pDst, "arm_mat_cmplx_mult_q31", mat_cmplx_mult_q31_launch, 2);
+}
+arm_status arm_mat_cmplx_mult_q15(const arm_matrix_instance_q15* pSrcA, const arm_matrix_instance_q15* pSrcB,
+                                  arm_matrix_instance_q15* pDst, q15_t* pScratch) {
+  return mat_mult_sync<int16_t>(pSrcA, pSrcB, pDst, "arm_mat_cmplx_mult_q15", mat_cmplx_mult_q15_launch, 2,
+                                pScratch);
+}
+#define MI355X_CMAT(SUF, INST, T, CT)                                                                           \
+  arm_status arm_mat_cmplx_mult_##SUF##_batch(const INST* pSrcA, const INST* pSrcB, INST* pDst, uint32_t batch, \
+                                              void* stream) {                                                   \
+    return mat_batch(pSrcA, pSrcB, pDst, batch, stream, "arm_mat_cmplx_mult_" #SUF "_batch",                    \
+                     mat_cmplx_mult_##SUF##_launch);                                                            \
+  }                                                                                                             \
+  arm_status arm_mat_cmplx_mult_##SUF##_batch_multi(const INST* pSrcA, const INST* pSrcB, INST* pDst,           \
+                                                    uint32_t nshards, const int* devices, const T* const* d_a,  \
+                                                    const T* const* d_b, T* const* d_c, const uint32_t* batch) { \
+    return mat_batch_multi<CT>(pSrcA, pSrcB, pDst, nshards, devices, d_a, d_b, d_c, batch,                      \
+                               "arm_mat_cmplx_mult_" #SUF "_batch_multi", mat_cmplx_mult_##SUF##_launch);       \
+  }
+MI355X_CMAT(f32, arm_matrix_instance_f32, float32_t, float)
+MI355X_CMAT(q31, arm_matrix_instance_q31, q31_t, int32_t)
+MI355X_CMAT(q15, arm_matrix_instance_q15, q15_t, int16_t)
+#undef MI355X_CMAT
 
 // ---- convolution ------------------------------------------------------------------
 #define MI355X_CONV_FULL(NAME, T, CT, OP, VAR)                                                                  \

@@ -244,5 +244,19 @@ hipError_t mat_mult_fast_q15_launch(int m, int k, int n, const int16_t* a, const
                                     uint32_t batch, hipStream_t st);
 hipError_t mat_mult_fast_q31_launch(int m, int k, int n, const int32_t* a, const int32_t* b, int32_t* c,
                                     uint32_t batch, hipStream_t st);
+// Complex C[b] = A[b] (m x k) * B[b] (k x n), interleaved (re, im) words, contiguous batch; m, k, n
+// count complex elements.  The real kernels above on the embedded product A (m x 2k) * B' (2k x 2n),
+// B' formed while staging B: f32 is the k-ascending fmaf chain re = fma(-b, d, fma(a, c, re)),
+// im = fma(b, c, fma(a, d, im)); q15 / q31 are bit-exact (arm_mat_cmplx_mult_q15 / _q31: wrapping q63
+// sum, >> 15 / >> 31, saturated).
+hipError_t mat_cmplx_mult_f32_launch(int m, int k, int n, const float* a, const float* b, float* c, uint32_t batch,
+                                     hipStream_t st);
+hipError_t mat_cmplx_mult_q15_launch(int m, int k, int n, const int16_t* a, const int16_t* b, int16_t* c,
+                                     uint32_t batch, hipStream_t st);
+hipError_t mat_cmplx_mult_q31_launch(int m, int k, int n, const int32_t* a, const int32_t* b, int32_t* c,
+                                     uint32_t batch, hipStream_t st);
+// bt (n rows of k complex words) = b (k rows of n complex words) transposed: the pScratch contents of
+// arm_mat_cmplx_mult_q15 (arm_mat_cmplx_mult_q15.c:433-468).
+hipError_t mat_cmplx_trans_q15_launch(int k, int n, const int16_t* b, int16_t* bt, hipStream_t st);
 
 }  // namespace mi355x

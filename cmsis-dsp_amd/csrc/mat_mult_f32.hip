@@ -20,6 +20,14 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kBM = 128, kBN = 128, kBK = 16;
 constexpr int kLdA = kBM + 4;   // padded k-major rows of A (avoid write conflicts on the transpose)
 
+// CX (arm_mat_cmplx_mult_f32, arm_mat_cmplx_mult_f32.c:1225-1392): A is M x K/2 complex read as the
+// M x K real matrix it is in memory, B is K/2 x N/2 complex (K/2 rows of N words), and the tile of
+// the embedded B' (K x N: row 2k = (c, d) as loaded, row 2k + 1 = (-d, c)) exists only in LDS:
+// every thread that loads a word of B's row k writes it to LDS row 2k and, pair-swapped and with
+// the sign of d flipped, to LDS row 2k + 1.  One MFMA then consumes the k pair (2k, 2k + 1), i.e.
+// re = fma(-b, d, fma(a, c, re)), im = fma(b, c, fma(a, d, im)) in ascending k.  Words outside
+// the matrix stay +0 in both rows, as in the real kernel.
+template <bool CX>
 __global__ __launch_bounds__(256) void mat_mult_f32_kernel(const float* __restrict__ A, const float* __restrict__ B,
                                                            float* __restrict__ C, int M, int K, int N) {
   __shared__ __attribute__((aligned(16))) float As[2][kBK][kLdA];
@@ -34,7 +42,7 @@ __global__ __launch_bounds__(256) void mat_mult_f32_kernel(const float* __restri
   const int tm = tile / tilesN, tn = tile % tilesN;
   const size_t bz = blockIdx.z;
   A += bz * (size_t)M * K;
-  B += bz * (size_t)K * N;
+  B += bz * (size_t)(CX ? K / 2 : K) * N;
   C += bz * (size_t)M * N;
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -49,7 +57,9 @@ __global__ __launch_bounds__(256) void mat_mult_f32_kernel(const float* __restri
 
   // global -> register staging of one K tile: A 128x16 (8 floats/thread), B 16x128 (8 floats/thread)
   float ra[8], rb[8];
+  [[maybe_unused]] uint32_t flip = 0;           // CX: sign bits for row 2k + 1 (in-range imaginary words), by u
   auto load_tile = [&](int k0) {
+    if constexpr (CX) flip = 0;
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int e = tid + u * 256;              // A element: row e/16, k e%16
@@ -57,8 +67,17 @@ __global__ __launch_bounds__(256) void mat_mult_f32_kernel(const float* __restri
       const int gr = row0 + ar, gk = k0 + ak;
       ra[u] = (gr < M && gk < K) ? A[(size_t)gr * K + gk] : 0.0f;
       const int bk = e >> 7, bc = e & 127;       // B element: k e/128, col e%128
-      const int gk2 = k0 + bk, gc = col0 + bc;
-      rb[u] = (gk2 < K && gc < N) ? B[(size_t)gk2 * N + gc] : 0.0f;
+      if constexpr (CX) {
+        if (u < 4) {                             // 8 complex rows of 128 words
+          const int gk2 = (k0 >> 1) + bk, gc = col0 + bc;
+          const bool in = gk2 < (K >> 1) && gc < N;
+          rb[u] = in ? B[(size_t)gk2 * N + gc] : 0.0f;
+          flip |= (in && (bc & 1)) ? 0x80000000u >> u : 0u;    // the fill stays +0 in both rows
+        }
+      } else {
+        const int gk2 = k0 + bk, gc = col0 + bc;
+        rb[u] = (gk2 < K && gc < N) ? B[(size_t)gk2 * N + gc] : 0.0f;
+      }
     }
   };
   auto store_tile = [&](int buf) {
@@ -66,7 +85,15 @@ __global__ __launch_bounds__(256) void mat_mult_f32_kernel(const float* __restri
     for (int u = 0; u < 8; ++u) {
       const int e = tid + u * 256;
       As[buf][e & 15][e >> 4] = ra[u];
-      Bs[buf][e >> 7][e & 127] = rb[u];
+      if constexpr (CX) {
+        if (u < 4) {
+          Bs[buf][2 * (e >> 7)][e & 127] = rb[u];
+          Bs[buf][2 * (e >> 7) + 1][(e & 127) ^ 1] =
+              __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, rb[u]) ^ ((flip << u) & 0x80000000u));
+        }
+      } else {
+        Bs[buf][e >> 7][e & 127] = rb[u];
+      }
     }
   };
 
@@ -120,6 +147,9 @@ __global__ __launch_bounds__(256) void mat_mult_f32_kernel(const float* __restri
 #endif
 constexpr int kLdA4 = kBM + 2;
 
+// CX as above: one float4 of B per thread and K tile (8 complex rows of 128 words), written to LDS
+// rows 2k (as loaded) and 2k + 1 ((-d, c) per pair), both with ds_write_b128.
+template <bool CX>
 __global__ __launch_bounds__(256) void mat_mult_f32_full_kernel(const float* __restrict__ A,
                                                                 const float* __restrict__ B,
                                                                 float* __restrict__ C, int M, int K, int N) {
@@ -149,8 +179,8 @@ __global__ __launch_bounds__(256) void mat_mult_f32_full_kernel(const float* __r
   const int a_row = tid >> 2, a_kq = (tid & 3) * 4;
   const int b_k = tid >> 5, b_c = (tid & 31) * 4;
   const float* pa = A + bz * (size_t)M * K + (size_t)(row0 + a_row) * K + a_kq;
-  const float* pb = B + bz * (size_t)K * N + (size_t)b_k * N + col0 + b_c;
-  const size_t a_step2 = (size_t)64 * K, b_step2 = (size_t)8 * N, b_tile = (size_t)kBK * N;
+  const float* pb = B + bz * (size_t)(CX ? K / 2 : K) * N + (size_t)b_k * N + col0 + b_c;
+  const size_t a_step2 = (size_t)64 * K, b_step2 = (size_t)8 * N, b_tile = (size_t)(CX ? kBK / 2 : kBK) * N;
 
   f32x16 acc[2][2];
 #pragma unroll
@@ -166,7 +196,7 @@ __global__ __launch_bounds__(256) void mat_mult_f32_full_kernel(const float* __r
     ra0 = *reinterpret_cast<const float4*>(a_);                                  \
     ra1 = *reinterpret_cast<const float4*>(a_ + a_step2);                        \
     rb0 = *reinterpret_cast<const float4*>(b_);                                  \
-    rb1 = *reinterpret_cast<const float4*>(b_ + b_step2);                        \
+    if constexpr (!CX) rb1 = *reinterpret_cast<const float4*>(b_ + b_step2);     \
   } while (0)
 #define MM_STORE(buf)                                                            \
   do {                                                                           \
@@ -174,8 +204,14 @@ __global__ __launch_bounds__(256) void mat_mult_f32_full_kernel(const float* __r
     As[buf][a_kq + 1][a_row] = ra0.y; As[buf][a_kq + 1][a_row + 64] = ra1.y;      \
     As[buf][a_kq + 2][a_row] = ra0.z; As[buf][a_kq + 2][a_row + 64] = ra1.z;      \
     As[buf][a_kq + 3][a_row] = ra0.w; As[buf][a_kq + 3][a_row + 64] = ra1.w;      \
-    *reinterpret_cast<float4*>(&Bs[buf][b_k][b_c]) = rb0;                        \
-    *reinterpret_cast<float4*>(&Bs[buf][b_k + 8][b_c]) = rb1;                    \
+    if constexpr (CX) {                                                          \
+      *reinterpret_cast<float4*>(&Bs[buf][2 * b_k][b_c]) = rb0;                  \
+      *reinterpret_cast<float4*>(&Bs[buf][2 * b_k + 1][b_c]) =                   \
+          make_float4(-rb0.y, rb0.x, -rb0.w, rb0.z);                             \
+    } else {                                                                     \
+      *reinterpret_cast<float4*>(&Bs[buf][b_k][b_c]) = rb0;                      \
+      *reinterpret_cast<float4*>(&Bs[buf][b_k + 8][b_c]) = rb1;                  \
+    }                                                                            \
   } while (0)
 
   const int nk = K / kBK;
@@ -217,8 +253,10 @@ __global__ __launch_bounds__(256) void mat_mult_f32_full_kernel(const float* __r
       }
 }
 
-hipError_t mat_mult_f32_launch(int m, int k, int n, const float* a, const float* b, float* c, uint32_t batch,
-                               hipStream_t st) {
+// m x k x n real; CX: the embedded shape (k and n twice the complex ones, b is k/2 rows of n words)
+template <bool CX>
+static hipError_t launch_f32(int m, int k, int n, const float* a, const float* b, float* c, uint32_t batch,
+                             hipStream_t st) {
   if (batch == 0 || m == 0 || n == 0) return hipSuccess;
   if (k == 0) return hipMemsetAsync(c, 0, sizeof(float) * (size_t)m * n * batch, st);
   const int tiles = ((m + kBM - 1) / kBM) * ((n + kBN - 1) / kBN);
@@ -226,11 +264,22 @@ hipError_t mat_mult_f32_launch(int m, int k, int n, const float* a, const float*
                     ((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0;
   if (full && (!MI355X_MATF32_XCD || (uint64_t)tiles * batch <= 0x7fffffffull)) {
     const dim3 grid = MI355X_MATF32_XCD ? dim3((uint32_t)((uint64_t)tiles * batch)) : dim3(tiles, 1, batch);
-    hipLaunchKernelGGL(mat_mult_f32_full_kernel, grid, dim3(256), 0, st, a, b, c, m, k, n);
+    hipLaunchKernelGGL(mat_mult_f32_full_kernel<CX>, grid, dim3(256), 0, st, a, b, c, m, k, n);
     return hipGetLastError();
   }
-  hipLaunchKernelGGL(mat_mult_f32_kernel, dim3(tiles, 1, batch), dim3(256), 0, st, a, b, c, m, k, n);
+  hipLaunchKernelGGL(mat_mult_f32_kernel<CX>, dim3(tiles, 1, batch), dim3(256), 0, st, a, b, c, m, k, n);
   return hipGetLastError();
+}
+
+hipError_t mat_mult_f32_launch(int m, int k, int n, const float* a, const float* b, float* c, uint32_t batch,
+                               hipStream_t st) {
+  return launch_f32<false>(m, k, n, a, b, c, batch, st);
+}
+// m, k, n count complex elements; the embedded real depth and width stay below 2^31 for every
+// arm_matrix_instance (uint16_t dimensions)
+hipError_t mat_cmplx_mult_f32_launch(int m, int k, int n, const float* a, const float* b, float* c, uint32_t batch,
+                                     hipStream_t st) {
+  return launch_f32<true>(m, 2 * k, 2 * n, a, b, c, batch, st);
 }
 
 }  // namespace mi355x

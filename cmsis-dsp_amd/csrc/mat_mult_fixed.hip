@@ -114,10 +114,26 @@ __device__ uint64_t g_i8_stamps[kI8Stamps][8];
 #define I8_STAMP(i) do { } while (0)
 #endif
 
+// ---- complex product (CX; arm_mat_cmplx_mult_q15.c:433-582, arm_mat_cmplx_mult_q31.c:836-1057).
+// A (M x K/2 complex) is the M x K real matrix it already is in memory; B (K/2 x N/2 complex, i.e.
+// K/2 rows of N words (c, d)) is embedded while staging: B' row 2k is the row as loaded, row 2k + 1
+// its pair-swapped words (~d, c).  ~d = -d - 1 always fits the type where -d does not (d the
+// minimum), and since -b d = b (~d) + b the real outputs (even columns) get the row's sum of A's
+// imaginary words added in the int64 epilogue; that sum is gathered while staging A.  Zero-filled
+// words outside B become (-1, 0) in the odd rows: they are staged and column-summed as such, so
+// the slicing identity still gives sum_k A_ik B'staged_kj, in which A's zero fill removes them;
+// columns outside the matrix are never stored.
+// cx_swap: the (c, d) pairs of one odd row -> (~d, c)
+__device__ __forceinline__ uint32_t cx_swap_q15(uint32_t w) { return ((w >> 16) | (w << 16)) ^ 0x0000ffffu; }
+// clip_q63_to_q31 (none.h:136-141)
+__device__ __forceinline__ int32_t clip_q63_q31(int64_t v) {
+  return v > 0x7fffffffLL ? 0x7fffffff : (v < -0x80000000LL ? (int32_t)0x80000000 : (int32_t)v);
+}
+
 // FULL: M % BM == 0, N % BN == 0, K % 64 == 0 and 16-B / 8-B aligned rows -- no bounds
 // checks, so the K loop is one basic block the scheduler can interleave (loads, staging,
 // MFMAs); otherwise every load is guarded and zero-filled.
-template <typename T, bool FULL>
+template <typename T, bool FULL, bool CX = false>
 __global__ __launch_bounds__(kNT2) void mat_mult_i8v2_kernel(const T* __restrict__ A, const T* __restrict__ B,
                                                              T* __restrict__ C, int M, int K, int N, int fast) {
   using G = I8Cfg<T>;
@@ -147,7 +163,7 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v2_kernel(const T* __restrict
   const int tm = t / tilesN, tn = t % tilesN;
   const size_t bz = lin / (uint32_t)tiles;
   A += bz * (size_t)M * K;
-  B += bz * (size_t)K * N;
+  B += bz * (size_t)(CX ? K / 2 : K) * N;
   C += bz * (size_t)M * N;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int row0 = tm * BM, col0 = tn * BN;
@@ -195,11 +211,14 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v2_kernel(const T* __restrict
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const int kb = k0 + 8 * kb8 + i;
+        if constexpr (CX) {
+          if (i & 1) continue;                     // row 2k + 1: formed from row 2k's words in stage()
+        }
         if (FULL || (vecB8 && kb < K && gcp + 2 <= N)) {
-          b8[i] = *reinterpret_cast<const uint32_t*>(B + (size_t)kb * N + gcp);
+          b8[i] = *reinterpret_cast<const uint32_t*>(B + (size_t)(CX ? kb >> 1 : kb) * N + gcp);
         } else {
-          const uint32_t lo = (kb < K && gcp < N) ? (uint32_t)(uint16_t)B[(size_t)kb * N + gcp] : 0u;
-          const uint32_t hi = (kb < K && gcp + 1 < N) ? (uint32_t)(uint16_t)B[(size_t)kb * N + gcp + 1] : 0u;
+          const uint32_t lo = (kb < K && gcp < N) ? (uint32_t)(uint16_t)B[(size_t)(CX ? kb >> 1 : kb) * N + gcp] : 0u;
+          const uint32_t hi = (kb < K && gcp + 1 < N) ? (uint32_t)(uint16_t)B[(size_t)(CX ? kb >> 1 : kb) * N + gcp + 1] : 0u;
           b8[i] = lo | (hi << 16);
         }
       }
@@ -207,12 +226,15 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v2_kernel(const T* __restrict
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int kb = k0 + 4 * bq + i;
+      if constexpr (CX) {
+        if (i & 1) continue;                       // row 2k + 1: formed from row 2k's words in stage()
+      }
       if (FULL || (vecB && kb < K && gc + CW <= N)) {
         if constexpr (BD == 4) {
-          const uint4 v = *reinterpret_cast<const uint4*>(B + (size_t)kb * N + gc);
+          const uint4 v = *reinterpret_cast<const uint4*>(B + (size_t)(CX ? kb >> 1 : kb) * N + gc);
           bd[i][0] = v.x; bd[i][1] = v.y; bd[i][2] = v.z; bd[i][3] = v.w;
         } else {
-          const uint2 v = *reinterpret_cast<const uint2*>(B + (size_t)kb * N + gc);
+          const uint2 v = *reinterpret_cast<const uint2*>(B + (size_t)(CX ? kb >> 1 : kb) * N + gc);
           bd[i][0] = v.x; bd[i][1] = v.y;
         }
       } else {
@@ -222,7 +244,7 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v2_kernel(const T* __restrict
 #pragma unroll
           for (int e = 0; e < EPD; ++e) {
             const int c = gc + d * EPD + e;
-            const uint32_t v = (kb < K && c < N) ? (uint32_t)B[(size_t)kb * N + c] : 0u;
+            const uint32_t v = (kb < K && c < N) ? (uint32_t)B[(size_t)(CX ? kb >> 1 : kb) * N + c] : 0u;
             w |= (EPD == 2 ? (v & 0xffffu) : v) << (16 * e);
           }
           bd[i][d] = w;
@@ -236,6 +258,7 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v2_kernel(const T* __restrict
   // 16 x 511 values of |v| <= 2^15 per partial), int64 for q31
   using PS = typename std::conditional<sizeof(T) == 2, int32_t, int64_t>::type;
   PS my_rsum = 0, my_csum[CW];
+  [[maybe_unused]] PS my_isum = 0;               // CX: the sum of this thread's imaginary (odd) words of A
 #pragma unroll
   for (int c = 0; c < CW; ++c) my_csum[c] = 0;
   int32_t bcs[2] = {0, 0};                       // B8: columns 2cp, 2cp + 1 (exact: <= 8 x 511 x 2^15)
@@ -252,13 +275,37 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v2_kernel(const T* __restrict
   auto stage = [&](int buf) {
     auto As = reinterpret_cast<int8_t (*)[BM][kPitch2]>(lds + buf * BUF);
     auto Bs = reinterpret_cast<int8_t (*)[BN][kPitch2]>(lds + buf * BUF + P * BM * kPitch2);
+    // CX, B8: b8[0], b8[2], b8[4], b8[6] hold the four complex rows; the odd rows of B' exist only as the
+    // byte selectors and complement masks of the plane gather below
+    if constexpr (CX && !B8) {                     // the odd rows of B' (here, not in load(): no wait on the loads there)
+#pragma unroll
+      for (int i = 1; i < 4; i += 2)
+#pragma unroll
+        for (int d = 0; d < BD; ++d) {
+          if constexpr (EPD == 2) bd[i][d] = cx_swap_q15(bd[i - 1][d]);
+          else bd[i][d] = (d & 1) ? bd[i - 1][d - 1] : ~bd[i - 1][d + 1];
+        }
+    }
     // exact row / column sums of the original values
     if constexpr (sizeof(T) == 2) {
       int32_t ra = 0;
 #pragma unroll
       for (int d = 0; d < AKD; ++d) ra = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, ad[d]), s2x{1, 1}, ra, false);
       my_rsum += ra;
-      if constexpr (B8) {
+      if constexpr (CX) {
+        int32_t ia = 0;
+#pragma unroll
+        for (int d = 0; d < AKD; ++d) ia = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, ad[d]), s2x{0, 1}, ia, false);
+        my_isum += ia;
+      }
+      if constexpr (B8 && CX) {                    // rows (c, d) and (~d, c): c - d - 1 and d + c per complex row
+#pragma unroll
+        for (int i = 0; i < 8; i += 2) {
+          bcs[0] = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, b8[i]), s2x{1, -1}, bcs[0], false);
+          bcs[1] = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, b8[i]), s2x{1, 1}, bcs[1], false);
+        }
+        bcs[0] -= 4;
+      } else if constexpr (B8) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           bcs[0] = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, b8[i]), s2x{1, 0}, bcs[0], false);
@@ -277,6 +324,10 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v2_kernel(const T* __restrict
     } else {
 #pragma unroll
       for (int d = 0; d < AKD; ++d) my_rsum += (int32_t)ad[d];
+      if constexpr (CX) {
+#pragma unroll
+        for (int d = 1; d < AKD; d += 2) my_isum += (int32_t)ad[d];
+      }
 #pragma unroll
       for (int c = 0; c < CW; ++c)
 #pragma unroll
@@ -299,8 +350,18 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v2_kernel(const T* __restrict
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
           const int o = 2 * c + p;                // byte of column 2cp + c, plane p, in a dword
-          uint32_t g0 = gather4(b8[0], b8[1], b8[2], b8[3], o), g1 = gather4(b8[4], b8[5], b8[6], b8[7], o);
-          if (p != P - 1) { g0 ^= 0x80808080u; g1 ^= 0x80808080u; }
+          uint32_t g0, g1;
+          if constexpr (CX) {
+            // k rows (2k, 2k + 1, 2k + 2, 2k + 3) from complex rows (k, k + 1): the odd rows take the pair's
+            // other word (byte o ^ 2), complemented in column 0 (~d)
+            const uint32_t sel = (uint32_t)o | (uint32_t)(o ^ 2) << 8 | (uint32_t)(4 + o) << 16 | (uint32_t)(4 + (o ^ 2)) << 24;
+            const uint32_t xm = (p != P - 1 ? 0x80808080u : 0u) ^ (c == 0 ? 0xff00ff00u : 0u);
+            g0 = __builtin_amdgcn_perm(b8[2], b8[0], sel) ^ xm;
+            g1 = __builtin_amdgcn_perm(b8[6], b8[4], sel) ^ xm;
+          } else {
+            g0 = gather4(b8[0], b8[1], b8[2], b8[3], o), g1 = gather4(b8[4], b8[5], b8[6], b8[7], o);
+            if (p != P - 1) { g0 ^= 0x80808080u; g1 ^= 0x80808080u; }
+          }
           const int row = i8_brow8(2 * cp + c);
           *reinterpret_cast<uint2*>(&Bs[p][row][16 * i8_chunk(row, kb8 >> 1) + 8 * (kb8 & 1)]) = make_uint2(g0, g1);
         }
@@ -467,8 +528,12 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v2_kernel(const T* __restrict
   int64_t* rfin = cs + NQ * BN;                             // [BM] final row sums
   int64_t* cfin = rfin + BM;                                // [BN] final column sums
   T* ct = reinterpret_cast<T*>(cfin + BN);                  // [BM][BN] output tile (FULL)
-  static_assert((AQ * BM + NQ * BN + BM + BN) * 8 + BM * BN * sizeof(T) <= 2 * BUF, "epilogue fits the planes");
+  int64_t* is = reinterpret_cast<int64_t*>(ct + BM * BN);   // CX: [AQ][BM] partial imaginary sums
+  int64_t* ifin = is + AQ * BM;                             // CX: [BM] final ones
+  static_assert((AQ * BM + NQ * BN + BM + BN + (CX ? AQ * BM + BM : 0)) * 8 + BM * BN * sizeof(T) <= 2 * BUF,
+                "epilogue fits the planes");
   rs[(tid % AQ) * BM + ar] = (int64_t)my_rsum;
+  if constexpr (CX) is[(tid % AQ) * BM + ar] = (int64_t)my_isum;
   if constexpr (B8) {
     cs[kb8 * BN + 2 * cp] = (int64_t)bcs[0];
     cs[kb8 * BN + 2 * cp + 1] = (int64_t)bcs[1];
@@ -483,6 +548,12 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v2_kernel(const T* __restrict
 #pragma unroll
       for (int q = 0; q < AQ; ++q) sum += rs[q * BM + i];
       rfin[i] = sum;
+      if constexpr (CX) {
+        int64_t isum = 0;
+#pragma unroll
+        for (int q = 0; q < AQ; ++q) isum += is[q * BM + i];
+        ifin[i] = isum;
+      }
     } else {
 #pragma unroll
       for (int q = 0; q < NQB; ++q) sum += cs[q * BN + (i - BM)];
@@ -505,10 +576,14 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v2_kernel(const T* __restrict
         uint64_t v = (uint64_t)(C0 * (rfin[rr] + csum)) - (uint64_t)kpad * (uint64_t)(C0 * C0);
 #pragma unroll
         for (int s = 0; s < S; ++s) v += (uint64_t)(int64_t)acc[s][i][j][reg] << (8 * s);
+        if constexpr (CX) {
+          if (!(cc & 1)) v += (uint64_t)ifin[rr];             // real outputs: b (~d) + b = -b d
+        }
         const int64_t sum = (int64_t)v;
         // fast q15 (arm_mat_mult_fast_q15.c:356-401 host branch): q31_t modular sum, (q15)(sum >> 15)
         T o;
         if constexpr (sizeof(T) == 2) o = fast ? (T)((int32_t)(uint32_t)v >> 15) : (T)ssat16((int32_t)(sum >> 15));
+        else if constexpr (CX) o = (T)clip_q63_q31(sum >> 31);   // arm_mat_cmplx_mult_q31.c:1029-1030
         else o = (T)(int32_t)(sum >> 31);
         if constexpr (FULL) ct[rr * BN + cc] = o;
         else if (grow < M && gcol < N) C[(size_t)grow * N + gcol] = o;
@@ -555,7 +630,7 @@ __device__ __forceinline__ v2i32_t tr_b8(const int8_t* p) {   // p: a generic po
   return __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) v2i32_t*)p);
 }
 
-template <typename T, bool FULL>
+template <typename T, bool FULL, bool CX = false>
 __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict__ A, const T* __restrict__ B,
                                                              T* __restrict__ C, int M, int K, int N, int fast) {
   using G = I8Cfg<T>;
@@ -570,7 +645,7 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict
   constexpr int BUF = ABUF + BBUF;
   // the epilogue reuses the plane buffers: partial sums (one column partial per staged k-row),
   // final sums and the output tile
-  constexpr int EPI = (AQ * BM + kKT2 * BN + BM + BN) * 8 + BM * BN * (int)sizeof(T);
+  constexpr int EPI = (AQ * BM + kKT2 * BN + BM + BN + (CX ? AQ * BM + BM : 0)) * 8 + BM * BN * (int)sizeof(T);
   __shared__ __attribute__((aligned(16))) int8_t lds[2 * BUF > EPI ? 2 * BUF : EPI];
 
   const int tilesN = (N + BN - 1) / BN, tiles = tilesN * ((M + BM - 1) / BM);
@@ -581,7 +656,7 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict
   const int tm = t / tilesN, tn = t % tilesN;
   const size_t bz = lin / (uint32_t)tiles;
   A += bz * (size_t)M * K;
-  B += bz * (size_t)K * N;
+  B += bz * (size_t)(CX ? K / 2 : K) * N;
   C += bz * (size_t)M * N;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int row0 = tm * BM, col0 = tn * BN;
@@ -618,7 +693,7 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict
     }
     const int kb = k0 + bk;
     if (FULL || (vecB && kb < K && gc + EB <= N)) {
-      const uint4* p = reinterpret_cast<const uint4*>(B + (size_t)kb * N + gc);
+      const uint4* p = reinterpret_cast<const uint4*>(B + (size_t)(CX ? kb >> 1 : kb) * N + gc);
 #pragma unroll
       for (int i = 0; i < EBD / 4; ++i) {
         const uint4 v = p[i];
@@ -631,7 +706,7 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict
 #pragma unroll
         for (int e = 0; e < EPD; ++e) {
           const int c = gc + d * EPD + e;
-          const uint32_t v = (kb < K && c < N) ? (uint32_t)B[(size_t)kb * N + c] : 0u;
+          const uint32_t v = (kb < K && c < N) ? (uint32_t)B[(size_t)(CX ? kb >> 1 : kb) * N + c] : 0u;
           w |= (EPD == 2 ? (v & 0xffffu) : v) << (16 * e);
         }
         bd[d] = w;
@@ -639,7 +714,13 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict
     }
   };
 
-  int64_t my_rsum = 0;
+  int64_t my_rsum = 0;                           // CX, q31: the even (real) words only, the odd ones in my_isum
+  [[maybe_unused]] int64_t my_isum = 0;          // CX: the sum of this thread's imaginary (odd) words of A
+  // CX: this thread's plane row bk is row 2k (the words as loaded) or row 2k + 1 ((~d, c) per pair) for the
+  // whole K loop.  An odd row is never formed in registers: its planes come from the loaded words with the
+  // pair-swapping byte selector and the complement mask below, and its column sums from the loaded words'
+  // sums at the end (sum of ~d = -(sum of d) - the number of staged rows, zero fill included)
+  [[maybe_unused]] const bool odd = CX && (bk & 1);
   // column sums of the k-rows this thread stages (at most K / 64 <= 511 of them): exact in int32
   // for q15 (|v| <= 2^15), int64 for q31
   using CS = typename std::conditional<sizeof(T) == 2, int32_t, int64_t>::type;
@@ -664,6 +745,12 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict
 #pragma unroll
       for (int d = 0; d < AKD; ++d) ra = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, ad[d]), s2x{1, 1}, ra, false);
       my_rsum += ra;
+      if constexpr (CX) {
+        int32_t ia = 0;
+#pragma unroll
+        for (int d = 0; d < AKD; ++d) ia = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, ad[d]), s2x{0, 1}, ia, false);
+        my_isum += ia;
+      }
 #pragma unroll
       for (int d = 0; d < EBD; ++d) {
         my_csum[2 * d] += (int16_t)(bd[d] & 0xffffu);
@@ -671,7 +758,14 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict
       }
     } else {
 #pragma unroll
-      for (int d = 0; d < AKD; ++d) my_rsum += (int32_t)ad[d];
+      for (int d = 0; d < AKD; ++d) {
+        if constexpr (CX) {
+          if (d & 1) my_isum += (int32_t)ad[d];
+          else my_rsum += (int32_t)ad[d];
+        } else {
+          my_rsum += (int32_t)ad[d];
+        }
+      }
 #pragma unroll
       for (int d = 0; d < EBD; ++d) my_csum[d] += (int32_t)bd[d];
     }
@@ -689,10 +783,26 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict
             make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
       // B: plane p of this thread's EB values, EB contiguous bytes of plane row bk
       uint32_t wb[EB / 4];
+      if constexpr (CX) {
+        // byte p of the four values of a dword group, the pairs swapped in an odd row; there the first
+        // byte of each pair (~d) is complemented on top of the lower planes' -128
+        const uint32_t up = (uint32_t)p;
+        const uint32_t se = sizeof(T) == 2 ? (up | (2 + up) << 8 | (4 + up) << 16 | (6 + up) << 24) : 0x0c0c0400u + 0x0101u * up;
+        const uint32_t so = sizeof(T) == 2 ? ((2 + up) | up << 8 | (6 + up) << 16 | (4 + up) << 24) : 0x0c0c0004u + 0x0101u * up;
+        const uint32_t sel = odd ? so : se;
+        const uint32_t xm = (p != P - 1 ? 0x80808080u : 0u) ^ (odd ? 0x00ff00ffu : 0u);
+#pragma unroll
+        for (int q = 0; q < EB / 4; ++q) {
+          if constexpr (sizeof(T) == 2) wb[q] = __builtin_amdgcn_perm(bd[2 * q + 1], bd[2 * q], sel) ^ xm;
+          else wb[q] = (__builtin_amdgcn_perm(bd[4 * q + 1], bd[4 * q], sel) |
+                        (__builtin_amdgcn_perm(bd[4 * q + 3], bd[4 * q + 2], sel) << 16)) ^ xm;
+        }
+      } else {
 #pragma unroll
       for (int q = 0; q < EB / 4; ++q) {
         if constexpr (sizeof(T) == 2) wb[q] = plane_q15<P>(bd[2 * q], bd[2 * q + 1], p);
         else wb[q] = plane4<P>(bd[4 * q], bd[4 * q + 1], bd[4 * q + 2], bd[4 * q + 3], p);
+      }
       }
       int8_t* dstb = Bs + (size_t)p * kKT2 * BP + bk * BP + bc;
       if constexpr (EB == 16) *reinterpret_cast<uint4*>(dstb) = make_uint4(wb[0], wb[1], wb[2], wb[3]);
@@ -847,9 +957,21 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict
   int64_t* rfin = cs + NQB * BN;
   int64_t* cfin = rfin + BM;
   T* ct = reinterpret_cast<T*>(cfin + BN);
-  rs[(tid % AQ) * BM + ar] = my_rsum;
+  int64_t* is = reinterpret_cast<int64_t*>(ct + BM * BN);   // CX: [AQ][BM] partial imaginary sums
+  int64_t* ifin = is + AQ * BM;                             // CX: [BM] final ones
+  if constexpr (CX && sizeof(T) == 4) rs[(tid % AQ) * BM + ar] = my_rsum + my_isum;
+  else rs[(tid % AQ) * BM + ar] = my_rsum;
+  if constexpr (CX) is[(tid % AQ) * BM + ar] = my_isum;
 #pragma unroll
-  for (int c = 0; c < EB; ++c) cs[bk * BN + bc + c] = (int64_t)my_csum[c];
+  for (int c = 0; c < EB; ++c) {
+    if constexpr (CX) {                          // an odd row staged (~d, c): the sums of those words
+      int64_t v = (int64_t)my_csum[c];
+      if (odd) v = (c & 1) ? (int64_t)my_csum[c - 1] : -(int64_t)my_csum[c + 1] - (int64_t)nk;
+      cs[bk * BN + bc + c] = v;
+    } else {
+      cs[bk * BN + bc + c] = (int64_t)my_csum[c];
+    }
+  }
   __syncthreads();
   for (int i = tid; i < BM + BN; i += kNT2) {
     int64_t sum = 0;
@@ -857,6 +979,12 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict
 #pragma unroll
       for (int q = 0; q < AQ; ++q) sum += rs[q * BM + i];
       rfin[i] = sum;
+      if constexpr (CX) {
+        int64_t isum = 0;
+#pragma unroll
+        for (int q = 0; q < AQ; ++q) isum += is[q * BM + i];
+        ifin[i] = isum;
+      }
     } else {
       for (int q = 0; q < NQB; ++q) sum += cs[q * BN + (i - BM)];
       cfin[i - BM] = sum;
@@ -878,9 +1006,13 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict
         uint64_t v = (uint64_t)(C0 * (rfin[rr] + csum)) - (uint64_t)kpad * (uint64_t)(C0 * C0);
 #pragma unroll
         for (int s2 = 0; s2 < S; ++s2) v += (uint64_t)(int64_t)acc[s2][i][j][reg] << (8 * s2);
+        if constexpr (CX) {
+          if (!(cc & 1)) v += (uint64_t)ifin[rr];             // real outputs: b (~d) + b = -b d
+        }
         const int64_t sum = (int64_t)v;
         T o;
         if constexpr (sizeof(T) == 2) o = fast ? (T)((int32_t)(uint32_t)v >> 15) : (T)ssat16((int32_t)(sum >> 15));
+        else if constexpr (CX) o = (T)clip_q63_q31(sum >> 31);
         else o = (T)(int32_t)(sum >> 31);
         if constexpr (FULL) ct[rr * BN + cc] = o;
         else if (grow < M && gcol < N) C[(size_t)grow * N + gcol] = o;
@@ -917,7 +1049,29 @@ __global__ __launch_bounds__(256) void mat_mult_fixed_valu_kernel(const T* __res
   else C[bz * (size_t)M * N + (size_t)i * N + j] = (T)(int32_t)(s >> 31);
 }
 
+// CX beyond that range: one thread per output word (column j = 2n + part), the reference's q63 sum
+// (wrapping) over the K/2 complex terms; M, K, N are the embedded real shape.
 template <typename T>
+__global__ __launch_bounds__(256) void mat_cmplx_mult_fixed_valu_kernel(const T* __restrict__ A,
+                                                                        const T* __restrict__ B, T* __restrict__ C,
+                                                                        int M, int K, int N) {
+  const size_t bz = blockIdx.z;
+  const int i = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= N) return;
+  const T* a = A + bz * (size_t)M * K + (size_t)i * K;
+  const T* b = B + bz * (size_t)(K / 2) * N + (j & ~1);
+  uint64_t sum = 0;
+  for (int k = 0; k < K / 2; ++k) {
+    const int64_t ar = a[2 * k], ai = a[2 * k + 1], br = b[(size_t)k * N], bi = b[(size_t)k * N + 1];
+    if (j & 1) sum += (uint64_t)(ar * bi) + (uint64_t)(ai * br);
+    else sum += (uint64_t)(ar * br) - (uint64_t)(ai * bi);
+  }
+  const int64_t s = (int64_t)sum;
+  if constexpr (sizeof(T) == 2) C[bz * (size_t)M * N + (size_t)i * N + j] = (T)ssat16((int32_t)(s >> 15));
+  else C[bz * (size_t)M * N + (size_t)i * N + j] = (T)clip_q63_q31(s >> 31);
+}
+
+template <typename T, bool CX = false>
 static hipError_t launch_fixed(int m, int k, int n, const T* a, const T* b, T* c, uint32_t batch, hipStream_t st,
                                int fast = 0) {
   if (batch == 0 || m == 0 || n == 0) return hipSuccess;
@@ -928,19 +1082,23 @@ static hipError_t launch_fixed(int m, int k, int n, const T* a, const T* b, T* c
     const bool full = m % G::BM == 0 && n % G::BN == 0 && k % G::KT == 0 &&
                       ((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0 && (k * sizeof(T)) % 16 == 0 &&
                       (n * sizeof(T)) % 16 == 0 && ((uintptr_t)c & 15) == 0;
-    if (MI355X_I8_V3 == 1 || (MI355X_I8_V3 == 2 && sizeof(T) == 4)) {   // 2: q31 only
+    constexpr int V3 = CX ? MI355X_I8_CX_V3 : MI355X_I8_V3;
+    if (V3 == 1 || (V3 == 2 && sizeof(T) == 4)) {   // 2: q31 only
       if (full)
-        hipLaunchKernelGGL((mat_mult_i8v3_kernel<T, true>), dim3(tiles * batch), dim3(kNT2), 0, st, a, b, c, m, k, n,
+        hipLaunchKernelGGL((mat_mult_i8v3_kernel<T, true, CX>), dim3(tiles * batch), dim3(kNT2), 0, st, a, b, c, m, k, n,
                            fast);
       else
-        hipLaunchKernelGGL((mat_mult_i8v3_kernel<T, false>), dim3(tiles * batch), dim3(kNT2), 0, st, a, b, c, m, k,
+        hipLaunchKernelGGL((mat_mult_i8v3_kernel<T, false, CX>), dim3(tiles * batch), dim3(kNT2), 0, st, a, b, c, m, k,
                            n, fast);
     } else if (full)
-      hipLaunchKernelGGL((mat_mult_i8v2_kernel<T, true>), dim3(tiles * batch), dim3(kNT2), 0, st, a, b, c, m, k, n,
+      hipLaunchKernelGGL((mat_mult_i8v2_kernel<T, true, CX>), dim3(tiles * batch), dim3(kNT2), 0, st, a, b, c, m, k, n,
                          fast);
     else
-      hipLaunchKernelGGL((mat_mult_i8v2_kernel<T, false>), dim3(tiles * batch), dim3(kNT2), 0, st, a, b, c, m, k, n,
+      hipLaunchKernelGGL((mat_mult_i8v2_kernel<T, false, CX>), dim3(tiles * batch), dim3(kNT2), 0, st, a, b, c, m, k, n,
                          fast);
+  } else if (CX) {
+    hipLaunchKernelGGL(mat_cmplx_mult_fixed_valu_kernel<T>, dim3((n + 255) / 256, m, batch), dim3(256), 0, st, a, b,
+                       c, m, k, n);
   } else {
     hipLaunchKernelGGL(mat_mult_fixed_valu_kernel<T>, dim3((n + 255) / 256, m, batch), dim3(256), 0, st, a, b, c,
                        m, k, n, fast);
@@ -1023,6 +1181,34 @@ hipError_t mat_mult_q15_launch(int m, int k, int n, const int16_t* a, const int1
 hipError_t mat_mult_q31_launch(int m, int k, int n, const int32_t* a, const int32_t* b, int32_t* c, uint32_t batch,
                                hipStream_t st) {
   return launch_fixed<int32_t>(m, k, n, a, b, c, batch, st);
+}
+
+// m, k, n count complex elements (arm_matrix_instance dimensions are uint16_t, so the embedded real
+// depth and width fit an int); 2k <= kMatI8MaxK, i.e. k <= 16352, runs on the matrix cores
+hipError_t mat_cmplx_mult_q15_launch(int m, int k, int n, const int16_t* a, const int16_t* b, int16_t* c,
+                                     uint32_t batch, hipStream_t st) {
+  return launch_fixed<int16_t, true>(m, 2 * k, 2 * n, a, b, c, batch, st);
+}
+hipError_t mat_cmplx_mult_q31_launch(int m, int k, int n, const int32_t* a, const int32_t* b, int32_t* c,
+                                     uint32_t batch, hipStream_t st) {
+  return launch_fixed<int32_t, true>(m, 2 * k, 2 * n, a, b, c, batch, st);
+}
+
+// one thread per complex element; 2-byte accesses (pData need not be 4-byte aligned)
+__global__ __launch_bounds__(256) void mat_cmplx_trans_q15_kernel(const int16_t* __restrict__ b,
+                                                                  int16_t* __restrict__ bt, int k, int n) {
+  const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+  if (idx >= (uint32_t)k * (uint32_t)n) return;
+  const uint32_t r = idx / (uint32_t)n, c = idx % (uint32_t)n;
+  const size_t o = 2 * ((size_t)c * k + r);
+  bt[o] = b[2 * (size_t)idx];
+  bt[o + 1] = b[2 * (size_t)idx + 1];
+}
+hipError_t mat_cmplx_trans_q15_launch(int k, int n, const int16_t* b, int16_t* bt, hipStream_t st) {
+  const uint64_t total = (uint64_t)k * n;      // < 2^32 for uint16_t dimensions
+  if (total == 0) return hipSuccess;
+  hipLaunchKernelGGL(mat_cmplx_trans_q15_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, st, b, bt, k, n);
+  return hipGetLastError();
 }
 
 #if MI355X_I8_STAMPS

@@ -180,6 +180,9 @@
 #ifndef MI355X_I8_V3
 #define MI355X_I8_V3 2
 #endif
+#ifndef MI355X_I8_CX_V3     // the same choice for the complex products (arm_mat_cmplx_mult_q15 / _q31)
+#define MI355X_I8_CX_V3 MI355X_I8_V3
+#endif
 
 // ---- mfcc_f32.hip
 #ifndef MI355X_MFCC_UNROLL

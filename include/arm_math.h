@@ -935,6 +935,23 @@ arm_status arm_mat_mult_fast_q15(const arm_matrix_instance_q15 *pSrcA, const arm
 arm_status arm_mat_mult_fast_q31(const arm_matrix_instance_q31 *pSrcA, const arm_matrix_instance_q31 *pSrcB,
                                  arm_matrix_instance_q31 *pDst);
 
+/* Complex matrix multiply (matrix_functions.h: arm_mat_cmplx_mult_f32 / _q15 / _q31).  numRows and
+ * numCols count complex elements; pData holds interleaved (re, im) words.  Bodies:
+ * Source/MatrixFunctions/arm_mat_cmplx_mult_q15.c:433-582 (!ARM_MATH_DSP: q63 sums of exact
+ * products, __SSAT(sum >> 15, 16); pScratch, host or device, receives B transposed (numColsB rows of
+ * numRowsB complex words) as the reference leaves it, NULL is tolerated),
+ * arm_mat_cmplx_mult_q31.c:836-1057 (q63 sums wrapping mod 2^64, clip_q63_to_q31(sum >> 31)): both
+ * bit-exact.  arm_mat_cmplx_mult_f32.c:1225-1392: the k-ascending fmaf chain
+ * re = fma(-b, d, fma(a, c, re)), im = fma(b, c, fma(a, d, im)) from +0, within
+ * 2K 2^-24 (|A||B'|)ij of the exact product (finite inputs; DESIGN.md, complex matrix multiply).
+ * Size check always on. */
+arm_status arm_mat_cmplx_mult_f32(const arm_matrix_instance_f32 *pSrcA, const arm_matrix_instance_f32 *pSrcB,
+                                  arm_matrix_instance_f32 *pDst);
+arm_status arm_mat_cmplx_mult_q15(const arm_matrix_instance_q15 *pSrcA, const arm_matrix_instance_q15 *pSrcB,
+                                  arm_matrix_instance_q15 *pDst, q15_t *pScratch);
+arm_status arm_mat_cmplx_mult_q31(const arm_matrix_instance_q31 *pSrcA, const arm_matrix_instance_q31 *pSrcB,
+                                  arm_matrix_instance_q31 *pDst);
+
 #ifdef __cplusplus
 }
 #endif

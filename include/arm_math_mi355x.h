@@ -9,7 +9,8 @@
  *     stream) and the call returns without synchronising;
  *   - results are bit-identical to calling the reference scalar function on each item in
  *     turn (f32 CFFT/RFFT/FIR and all fixed-point functions), or within the stated
- *     tolerance (arm_mat_mult_f32_batch, MFMA accumulation — DESIGN.md §mat_mult);
+ *     tolerance (arm_mat_mult_f32_batch and arm_mat_cmplx_mult_f32_batch, MFMA accumulation —
+ *     DESIGN.md §mat_mult and "complex matrix multiply");
  *   - return ARM_MATH_SUCCESS, ARM_MATH_ARGUMENT_ERROR (unsupported length, NULL pointer,
  *     launch failure; details in arm_mi355x_last_error_string()).
  * Instance structs are the reference's own (arm_math.h).  Tables and coefficients they point
@@ -296,6 +297,15 @@ arm_status arm_mat_mult_fast_q15_batch(const arm_matrix_instance_q15 *pSrcA, con
                                        arm_matrix_instance_q15 *pDst, uint32_t batch, void *stream);
 arm_status arm_mat_mult_fast_q31_batch(const arm_matrix_instance_q31 *pSrcA, const arm_matrix_instance_q31 *pSrcB,
                                        arm_matrix_instance_q31 *pDst, uint32_t batch, void *stream);
+/* Complex analogues (arm_mat_cmplx_mult_f32 / _q31 / _q15 per matrix; numRows / numCols count
+ * complex elements, items are contiguous interleaved matrices).  q31 / q15 bit-exact, f32 the
+ * stated fmaf chain; no scratch is taken or written. */
+arm_status arm_mat_cmplx_mult_f32_batch(const arm_matrix_instance_f32 *pSrcA, const arm_matrix_instance_f32 *pSrcB,
+                                        arm_matrix_instance_f32 *pDst, uint32_t batch, void *stream);
+arm_status arm_mat_cmplx_mult_q31_batch(const arm_matrix_instance_q31 *pSrcA, const arm_matrix_instance_q31 *pSrcB,
+                                        arm_matrix_instance_q31 *pDst, uint32_t batch, void *stream);
+arm_status arm_mat_cmplx_mult_q15_batch(const arm_matrix_instance_q15 *pSrcA, const arm_matrix_instance_q15 *pSrcB,
+                                        arm_matrix_instance_q15 *pDst, uint32_t batch, void *stream);
 
 /* Multi-GPU complex FFT (SURVEY §8b "a multi-GPU entry point"; per item: arm_cfft_f32 /
  * _q31 / _q15, transform_functions.h:456-460).  Shard s of `nshards` is batch[s] contiguous
@@ -362,6 +372,20 @@ arm_status arm_mat_mult_q31_batch_multi(const arm_matrix_instance_q31 *pSrcA, co
                                         arm_matrix_instance_q31 *pDst, uint32_t nshards, const int *devices,
                                         const q31_t *const *d_a, const q31_t *const *d_b, q31_t *const *d_c,
                                         const uint32_t *batch);
+/* ... and of the complex matrix multiply. */
+arm_status arm_mat_cmplx_mult_f32_batch_multi(const arm_matrix_instance_f32 *pSrcA,
+                                              const arm_matrix_instance_f32 *pSrcB, arm_matrix_instance_f32 *pDst,
+                                              uint32_t nshards, const int *devices, const float32_t *const *d_a,
+                                              const float32_t *const *d_b, float32_t *const *d_c,
+                                              const uint32_t *batch);
+arm_status arm_mat_cmplx_mult_q31_batch_multi(const arm_matrix_instance_q31 *pSrcA,
+                                              const arm_matrix_instance_q31 *pSrcB, arm_matrix_instance_q31 *pDst,
+                                              uint32_t nshards, const int *devices, const q31_t *const *d_a,
+                                              const q31_t *const *d_b, q31_t *const *d_c, const uint32_t *batch);
+arm_status arm_mat_cmplx_mult_q15_batch_multi(const arm_matrix_instance_q15 *pSrcA,
+                                              const arm_matrix_instance_q15 *pSrcB, arm_matrix_instance_q15 *pDst,
+                                              uint32_t nshards, const int *devices, const q15_t *const *d_a,
+                                              const q15_t *const *d_b, q15_t *const *d_c, const uint32_t *batch);
 
 /* Number of HIP devices visible to the process (0 when none). */
 int arm_mi355x_device_count(void);
