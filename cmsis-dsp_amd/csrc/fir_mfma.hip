@@ -47,33 +47,7 @@
 #define MI355X_FIR_Q15_MFMA_WG 3
 #endif
 
-#ifndef MI355X_FIR_Q15_ALN        // fir_q15 / fast_q15: the 16-B aligned window mode when the shapes allow it
-#define MI355X_FIR_Q15_ALN 1
-#endif
-#ifndef MI355X_FIR_Q7_ALN         // fir_q7: the 16-B aligned window mode when the shapes allow it
-#define MI355X_FIR_Q7_ALN 1
-#endif
-#ifndef MI355X_FIR_Q31_ALN        // fir_q31: the 16-B aligned window mode when the shapes allow it
-#define MI355X_FIR_Q31_ALN 1
-#endif
-#ifndef MI355X_FIR_STAMP
-#define MI355X_FIR_STAMP 0
-#endif
-#ifndef MI355X_FIR_Q15_DIAG        // 1: diagnostic only -- no window loads after the first item (wrong output)
-#define MI355X_FIR_Q15_DIAG 0
-#endif
-
 namespace mi355x {
-
-#if MI355X_FIR_STAMP   // diagnostic: s_memtime per phase of the first 64 items of workgroups 0-63 (wave 0)
-__device__ unsigned long long fir_stamp_buf[64][64][8];
-#define FM_STAMP(k, e)                                                                              \
-  do {                                                                                              \
-    if (blockIdx.x < 64 && tid == 0 && (k) < 64) fir_stamp_buf[blockIdx.x][(k)][(e)] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
-#else
-#define FM_STAMP(k, e) do { } while (0)
-#endif
 
 namespace {
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -199,7 +173,7 @@ __device__ __forceinline__ void fm_tile_y(const uint4* __restrict__ imgd, const 
 // of the tile, half h), then reads chunks L and 64 + L back, so each global store instruction
 // writes 1 KiB of consecutive outputs -- stored straight from the accumulator layout, every lane
 // wrote 8 B into its own 64-B segment and the store phase took ~1,100 of an item's ~6,900 ticks
-// (tools/probes/fir_stamps.hip).  Chunks are XOR-swizzled (c ^ ((c >> 4) & 3)) so that the writes
+// (in-kernel phase stamps).  Chunks are XOR-swizzled (c ^ ((c >> 4) & 3)) so that the writes
 // spread over the 16 four-bank groups.
 __device__ __forceinline__ int fm_ochunk(int c) { return c ^ ((c >> 4) & 3); }
 __device__ __forceinline__ void fm_tile_store(const uint32_t (&y)[8], int wid, int L, int count,
@@ -268,8 +242,8 @@ __global__ __launch_bounds__(256, MI355X_FIR_Q15_MFMA_WG) void fir_q15_mfma_kern
   // Window words: every word is loaded as one aligned dword from a CLAMPED block-input address with no
   // branch and no select, so nothing in the load phase waits for a load (a per-lane "block word or
   // per-sample path" select put the wave behind its own loads -- the result register's join made
-  // the compiler wait there; phase stamps, tools/probes/fir_stamps.hip, had the load phase at 53 % of
-  // an item).  The words before u_lo (a filter's first item: the history) come from per-sample head
+  // the compiler wait there; in-kernel phase stamps, DESIGN §4, had the load phase at 53 % of an
+  // item).  The words before u_lo (a filter's first item: the history) come from per-sample head
   // samples and a block ending mid-word (odd blockSize) from the tail sample, both landed in LDS by
   // DMA; they are combined when the window is staged.
   struct Win { int u_lo, u_hi; bool straddle; };
@@ -394,27 +368,20 @@ __global__ __launch_bounds__(256, MI355X_FIR_Q15_MFMA_WG) void fir_q15_mfma_kern
   if (it >= items) return;
   Item cur = item_of(it);
   load_window(cur);
-  for (int kk = 0;; ++kk) {
-    FM_STAMP(kk, 0);
+  for (;;) {
     __syncthreads();                                     // the previous item's reads are done
-    FM_STAMP(kk, 1);
     if constexpr (ALN) stage_window_aln(cur); else stage_window(cur);
-    FM_STAMP(kk, 2);
     __syncthreads();
-    FM_STAMP(kk, 3);
     const uint32_t nxt = it + gridDim.x;
     const Item next = item_of(nxt < items ? nxt : it);
-    if (nxt < items && !MI355X_FIR_Q15_DIAG) load_window(next);   // in flight under this item's MFMAs
-    FM_STAMP(kk, 4);
+    if (nxt < items) load_window(next);   // in flight under this item's MFMAs
 
     if (wrap) {
       fm_wrap_item(ph, pl, coeffs, T, B, cur.n0, cur.d, cur.count, tid, dst + (uint64_t)cur.f * B);
     } else if (1024 * wid < cur.count) {
       uint32_t y[8];
       fm_tile_y<KS, FAST>(imgl + (cur.d - d_base) * KS * 3 * 64, ph, pl, wid, L, sumc, y);
-      FM_STAMP(kk, 5);
       fm_tile_store(y, wid, L, cur.count, dst + (uint64_t)cur.f * B + cur.n0, ot[wid]);
-      FM_STAMP(kk, 6);
     }
     if (nxt >= items) break;
     it = nxt;
@@ -435,7 +402,7 @@ bool fir_q15_mfma_launch(const int16_t* coeffs, int T, const int16_t* src, int16
   // aligned mode: shift d8 = (-T1) mod 8 when blockSize % 8 == 0, the data is 16-B aligned and the
   // shift costs no K step (K >= numTaps - 1 + d8 + 31 + 1)
   const int d8 = (8 - (T - 1) % 8) % 8;
-  const bool aln = MI355X_FIR_Q15_ALN && B % 8 == 0 && ((uintptr_t)src & 15) == 0 && (T + d8 + 31 + 31) / 32 <= ks;
+  const bool aln = B % 8 == 0 && ((uintptr_t)src & 15) == 0 && (T + d8 + 31 + 31) / 32 <= ks;
   const int d_base = aln ? d8 : 0;
   // the coefficient image (2 shifts x KS steps x 3 planes x 64 lanes x 16 B) and [sum, wrap]
   const size_t img_bytes = (size_t)2 * ks * 3 * 64 * 16;
@@ -757,7 +724,7 @@ bool fir_q31_mfma_launch(const int32_t* coeffs, int T, const int32_t* src, int32
   // aligned mode: the shift d = (-T1) mod 4 puts every region of every window on a 16-B boundary;
   // taken when blockSize % 4 == 0, the pointers are 16-B aligned and the shift costs no K step
   const int d4 = (4 - (T - 1) % 4) % 4;
-  const bool aln = MI355X_FIR_Q31_ALN && B % 4 == 0 && ((uintptr_t)src & 15) == 0 && (T + 31 + d4 + 31) / 32 == ks;
+  const bool aln = B % 4 == 0 && ((uintptr_t)src & 15) == 0 && (T + 31 + d4 + 31) / 32 == ks;
   const int d = aln ? d4 : 0;
   const size_t img_bytes = (size_t)ks * 4 * 64 * 16;
   void* buf = nullptr;
@@ -1016,7 +983,7 @@ bool fir_q7_mfma_launch(const int8_t* coeffs, int T, const int8_t* src, int8_t* 
   // otherwise the window shift d <= 3 per item, K >= numTaps + 34
   const int d16 = (16 - (T - 1) % 16) % 16;
   const int ks_aln = (T + d16 + 31 + 31) / 32;
-  const bool aln = MI355X_FIR_Q7_ALN && B % 16 == 0 && ((uintptr_t)src & 15) == 0 && ks_aln <= kFmMaxKS;
+  const bool aln = B % 16 == 0 && ((uintptr_t)src & 15) == 0 && ks_aln <= kFmMaxKS;
   const int ks = aln ? ks_aln : (T + 34 + 31) / 32;
   const int d_base = aln ? d16 : 0;
   const size_t img_bytes = (size_t)4 * ks * 64 * 16;

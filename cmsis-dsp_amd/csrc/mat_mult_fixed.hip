@@ -17,8 +17,6 @@
 // K <= kMatI8MaxK keeps every int32 accumulator exact; longer K uses the VALU kernel.
 // Operand maps (verified with exact data, tools/probes/mfma_i8_layout.hip): lane l holds
 // A[row l&31][k = 16(l>>5) + j] and B[k = 16(l>>5) + j][col l&31] in byte j.
-#include <type_traits>
-
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -30,10 +28,6 @@ typedef short s2x __attribute__((ext_vector_type(2)));
 
 constexpr int kMatI8MaxK = 32704;
 
-template <typename T> struct Slices;
-template <> struct Slices<int16_t> { static constexpr int P = 2; static constexpr int64_t C0 = 128; };
-template <> struct Slices<int32_t> { static constexpr int P = 4; static constexpr int64_t C0 = 128LL * (1 + 256 + 65536); };
-
 // Plane p of four values given as the low bytes p of four dwords: signed bytes, the lower
 // planes offset by -128 (x - 128 = x ^ 0x80 on a byte).
 template <int P>
@@ -44,36 +38,30 @@ __device__ __forceinline__ uint32_t plane4(uint32_t v0, uint32_t v1, uint32_t v2
   return p == P - 1 ? w : w ^ 0x80808080u;
 }
 
-// ---- v2 kernel: 128 x 128 (q15) / 128 x 64 (q31) workgroup tiles of 8 waves (4 x 2), wave
-// tiles 32 x 64 / 32 x 32 (accumulators fit two waves per SIMD, so one wave's MFMAs overlap
-// the other's staging), double-buffered LDS planes (one barrier per K step), step kt+2's
-// global loads in flight under step kt's MFMAs.  B arrives row-major [k][n]; the MFMA wants
-// 16 k-consecutive bytes per column, so staging transposes 4 k-rows x CW columns per thread
-// into k-contiguous dwords (v_perm) before the LDS write.
+// ---- both kernels (v2: q15, v3: q31): 128 x 128 (q15) / 128 x 64 (q31) workgroup tiles of 8
+// waves (4 x 2), wave tiles 32 x 64 / 32 x 32 (accumulators fit two waves per SIMD, so one wave's
+// MFMAs overlap the other's staging), double-buffered LDS planes (one barrier per K step), step
+// kt+2's global loads in flight under step kt's MFMAs.  B arrives row-major [k][n]; the MFMA
+// wants 16 k-consecutive bytes per column: v2's staging transposes 8 k-rows x 2 columns per
+// thread into k-contiguous dwords (v_perm) before the LDS write, v3 stages B as it is and reads
+// it transposed.
 template <typename T> struct I8Cfg;
 template <> struct I8Cfg<int16_t> { static constexpr int BM = 128, BN = 128, WBM = 1, WBN = 2, KT = 64; };
 template <> struct I8Cfg<int32_t> { static constexpr int BM = 128, BN = 64, WBM = 1, WBN = 1, KT = 64; };
 constexpr int kNT2 = 512, kWavesM = 4, kWavesN = 2;
 
-// LDS plane layout: rows of 64 k-bytes (4 chunks of 16 B) with no padding; chunk c of row
-// `row` sits at chunk c ^ ((row >> 2) & 3), and B's column `col` at row col ^ ((col >> CWL) & 1)
-// (CWL = log2 of the columns one staging thread owns).  Conflict free for every access
-// (MI355X_MICROARCH.md §LDS):
+// LDS plane layout (A in both kernels, B in v2): rows of 64 k-bytes (4 chunks of 16 B) with no
+// padding; chunk c of row `row` sits at chunk c ^ ((row >> 2) & 3), and B's column `col` at row
+// i8_brow8(col).  Conflict free for the reads and A's writes (MI355X_MICROARCH.md §LDS):
 //  * fragment reads (ds_read_b128, 16-lane groups {0-3,12-15,20-27}, ..., banks mod 64): the 16
 //    rows of a group hold (row mod 4, swizzled chunk) pairs that are all distinct, i.e. 16
 //    distinct 4-bank sets (B's row permutation only swaps rows within such groups);
 //  * A staging (ds_write_b128, 8 contiguous lanes, banks mod 32): two consecutive rows x 4
-//    chunks -- the rows' parities differ, so the 16-dword halves do;
-//  * B staging (ds_write_b32, 32-lane groups, banks mod 32): lanes 0-15 and 16-31 write 16
-//    k-dwords of columns CW apart, whose rows the column permutation gives opposite parities.
+//    chunks -- the rows' parities differ, so the 16-dword halves do.
 // (Round 2's 80-byte pitch left both staging writes two-way conflicted: 12.5 M / 54.8 M conflict
 // cycles per launch for q15 / q31, profiles/r02/mat_mult_q15|q31/pmc.json.)
 __device__ __forceinline__ int i8_chunk(int row, int c) { return (c ^ (row >> 2)) & 3; }
-template <int CW> __device__ __forceinline__ int i8_brow(int col) {
-  constexpr int L = CW == 8 ? 3 : CW == 4 ? 2 : CW == 2 ? 1 : 0;
-  return col ^ ((col >> L) & 1);
-}
-// B8 staging (ds_write_b64 of 8 k-bytes, 16-lane groups on consecutive column pairs, banks mod 32):
+// B staging in v2 (ds_write_b64 of 8 k-bytes, 16-lane groups on consecutive column pairs, banks mod 32):
 // flipping the row parity on bit 1 of the column spreads a group over both row parities, the
 // most any 16 writes of 8 bytes into 64-byte rows can use (2-way); fragment reads keep each
 // aligned row quad, so they stay conflict free.
@@ -92,28 +80,6 @@ __device__ __forceinline__ uint32_t gather4(uint32_t r0, uint32_t r1, uint32_t r
   return __builtin_amdgcn_perm(r1, r0, sel) | (__builtin_amdgcn_perm(r3, r2, sel) << 16);
 }
 
-// Diagnostic build only (MI355X_I8_STAMPS, tools/probes/i8_phases.py): thread 0 of each
-// workgroup records s_memtime after the tile decode, the prologue, the K loop, the epilogue
-// arithmetic and the copy-out, plus s_memrealtime and its HW_ID / XCC_ID, into a device buffer.
-#if MI355X_I8_STAMPS
-constexpr int kI8Stamps = 1 << 16;
-__device__ uint64_t g_i8_stamps[kI8Stamps][8];
-#define I8_STAMP(i)                                                                       \
-  do {                                                                                    \
-    if (threadIdx.x == 0 && blockIdx.x < (uint32_t)kI8Stamps) {                           \
-      g_i8_stamps[blockIdx.x][i] = __builtin_amdgcn_s_memtime();                          \
-      if ((i) == 0) {                                                                     \
-        g_i8_stamps[blockIdx.x][5] = __builtin_amdgcn_s_memrealtime();                    \
-        g_i8_stamps[blockIdx.x][7] = (uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 4) | \
-                                     ((uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32); \
-      }                                                                                   \
-      if ((i) == 4) g_i8_stamps[blockIdx.x][6] = __builtin_amdgcn_s_memrealtime();        \
-    }                                                                                     \
-  } while (0)
-#else
-#define I8_STAMP(i) do { } while (0)
-#endif
-
 // ---- complex product (CX; arm_mat_cmplx_mult_q15.c:433-582, arm_mat_cmplx_mult_q31.c:836-1057).
 // A (M x K/2 complex) is the M x K real matrix it already is in memory; B (K/2 x N/2 complex, i.e.
 // K/2 rows of N words (c, d)) is embedded while staging: B' row 2k is the row as loaded, row 2k + 1
@@ -123,32 +89,27 @@ __device__ uint64_t g_i8_stamps[kI8Stamps][8];
 // words outside B become (-1, 0) in the odd rows: they are staged and column-summed as such, so
 // the slicing identity still gives sum_k A_ik B'staged_kj, in which A's zero fill removes them;
 // columns outside the matrix are never stored.
-// cx_swap: the (c, d) pairs of one odd row -> (~d, c)
-__device__ __forceinline__ uint32_t cx_swap_q15(uint32_t w) { return ((w >> 16) | (w << 16)) ^ 0x0000ffffu; }
 // clip_q63_to_q31 (none.h:136-141)
 __device__ __forceinline__ int32_t clip_q63_q31(int64_t v) {
   return v > 0x7fffffffLL ? 0x7fffffff : (v < -0x80000000LL ? (int32_t)0x80000000 : (int32_t)v);
 }
 
-// FULL: M % BM == 0, N % BN == 0, K % 64 == 0 and 16-B / 8-B aligned rows -- no bounds
-// checks, so the K loop is one basic block the scheduler can interleave (loads, staging,
-// MFMAs); otherwise every load is guarded and zero-filled.
-template <typename T, bool FULL, bool CX = false>
-__global__ __launch_bounds__(kNT2) void mat_mult_i8v2_kernel(const T* __restrict__ A, const T* __restrict__ B,
-                                                             T* __restrict__ C, int M, int K, int N, int fast) {
-  using G = I8Cfg<T>;
-  constexpr int P = Slices<T>::P, S = 2 * P - 1;
-  constexpr int64_t C0 = Slices<T>::C0;
+// FULL: M % BM == 0, N % BN == 0, K % 64 == 0 and 16-B aligned rows -- no bounds checks, so the
+// K loop is one basic block the scheduler can interleave (loads, staging, MFMAs); otherwise
+// every load is guarded and zero-filled.
+template <bool FULL, bool CX = false>
+__global__ __launch_bounds__(kNT2) void mat_mult_i8v2_kernel(const int16_t* __restrict__ A, const int16_t* __restrict__ B,
+                                                             int16_t* __restrict__ C, int M, int K, int N, int fast) {
+  using G = I8Cfg<int16_t>;
+  constexpr int P = 2, S = 2 * P - 1;            // byte planes, weight classes p + q
+  constexpr int64_t C0 = 128;
   constexpr int BM = G::BM, BN = G::BN, WBM = G::WBM, WBN = G::WBN, kKT2 = G::KT, kPitch2 = kKT2;
   static_assert(kKT2 == 64, "the LDS swizzle assumes 4 chunks of 16 k-bytes per row");
   static_assert(BM == kWavesM * 32 * WBM && BN == kWavesN * 32 * WBN, "wave grid covers the tile");
-  constexpr int EPD = 4 / sizeof(T);             // elements per dword
   constexpr int AK = BM * kKT2 / kNT2;           // A elements per staging thread (16)
-  constexpr int AKD = AK / EPD;                  // ... as dwords
+  constexpr int AKD = AK / 2;                    // ... as dwords
   constexpr int AQ = kKT2 / AK;                  // threads per A row (4)
-  constexpr int NQ = kKT2 / 4;                   // k-quads per K step
-  constexpr int CW = BN / (kNT2 / NQ);           // B columns per staging thread (8 q15 / 2 q31)
-  constexpr int BD = CW / EPD;                   // dwords per B k-row segment (4 / 2)
+  constexpr int NQ = kKT2 / 4;                   // rows of the epilogue's column-partial array
   constexpr int BUF = P * (BM + BN) * kPitch2;   // one K step's planes; two buffers
   __shared__ __attribute__((aligned(16))) int8_t lds[2 * BUF];
 
@@ -167,24 +128,19 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v2_kernel(const T* __restrict
   C += bz * (size_t)M * N;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int row0 = tm * BM, col0 = tn * BN;
-  I8_STAMP(0);
 
-  // staging roles: A row ar, AK k from ak0; B k-quad bq (rows 4bq..4bq+3), columns bg*CW..+CW-1
+  // staging roles: A row ar, AK k from ak0; B: thread (cp, kb8) stages columns 2cp, 2cp + 1 over
+  // k-rows 8 kb8 .. 8 kb8 + 7 (eight coalesced dword loads), i.e. 8 k-bytes per column and plane:
+  // one ds_write_b64 each
   const int ar = tid / AQ, ak0 = AK * (tid % AQ);
-  const int bq = tid % NQ, bg = tid / NQ;
-  const int gr = row0 + ar, gc = col0 + bg * CW;
-  // B8 (q15): thread (cp, kb8) stages columns 2cp, 2cp + 1 over k-rows 8 kb8 .. 8 kb8 + 7 (eight
-  // coalesced dword loads), i.e. 8 k-bytes per column and plane: one ds_write_b64 each (4 per
-  // thread instead of v2's 16 ds_write_b32) and half the transposing v_perm work
-  constexpr bool B8 = MI355X_I8_B8 && sizeof(T) == 2;
-  constexpr int NQB = B8 ? 8 : NQ;               // column-sum partials per column
+  const int gr = row0 + ar;
+  constexpr int NQB = 8;                         // column-sum partials per column (one per kb8)
   const int cp = tid % 64, kb8 = tid / 64;
   const int gcp = col0 + 2 * cp;
-  const bool vecA = FULL || (((K * (int)sizeof(T)) % 16) == 0 && (((uintptr_t)A) & 15) == 0);
-  const bool vecB = FULL || (((N * (int)sizeof(T)) % (4 * BD)) == 0 && (((uintptr_t)B) & (4 * BD - 1)) == 0);
-  const bool vecB8 = FULL || ((N % 2) == 0 && (((uintptr_t)B) & 3) == 0);
+  const bool vecA = FULL || (((K * 2) % 16) == 0 && (((uintptr_t)A) & 15) == 0);
+  const bool vecB = FULL || ((N % 2) == 0 && (((uintptr_t)B) & 3) == 0);
 
-  uint32_t ad[AKD], bd[4][BD], b8[8];
+  uint32_t ad[AKD], b8[8];
   auto load = [&](int k0) {
     const int ka = k0 + ak0;
     if (FULL || (vecA && gr < M && ka + AK <= K)) {
@@ -199,69 +155,35 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v2_kernel(const T* __restrict
       for (int d = 0; d < AKD; ++d) {
         uint32_t w = 0;
 #pragma unroll
-        for (int e = 0; e < EPD; ++e) {
-          const int k = ka + d * EPD + e;
+        for (int e = 0; e < 2; ++e) {
+          const int k = ka + d * 2 + e;
           const uint32_t v = (gr < M && k < K) ? (uint32_t)A[(size_t)gr * K + k] : 0u;
-          w |= (EPD == 2 ? (v & 0xffffu) : v) << (16 * e);
+          w |= (v & 0xffffu) << (16 * e);
         }
         ad[d] = w;
       }
     }
-    if constexpr (B8) {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int kb = k0 + 8 * kb8 + i;
-        if constexpr (CX) {
-          if (i & 1) continue;                     // row 2k + 1: formed from row 2k's words in stage()
-        }
-        if (FULL || (vecB8 && kb < K && gcp + 2 <= N)) {
-          b8[i] = *reinterpret_cast<const uint32_t*>(B + (size_t)(CX ? kb >> 1 : kb) * N + gcp);
-        } else {
-          const uint32_t lo = (kb < K && gcp < N) ? (uint32_t)(uint16_t)B[(size_t)(CX ? kb >> 1 : kb) * N + gcp] : 0u;
-          const uint32_t hi = (kb < K && gcp + 1 < N) ? (uint32_t)(uint16_t)B[(size_t)(CX ? kb >> 1 : kb) * N + gcp + 1] : 0u;
-          b8[i] = lo | (hi << 16);
-        }
-      }
-    } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int kb = k0 + 4 * bq + i;
+    for (int i = 0; i < 8; ++i) {
+      const int kb = k0 + 8 * kb8 + i;
       if constexpr (CX) {
-        if (i & 1) continue;                       // row 2k + 1: formed from row 2k's words in stage()
+        if (i & 1) continue;                     // row 2k + 1: formed from row 2k's words in stage()
       }
-      if (FULL || (vecB && kb < K && gc + CW <= N)) {
-        if constexpr (BD == 4) {
-          const uint4 v = *reinterpret_cast<const uint4*>(B + (size_t)(CX ? kb >> 1 : kb) * N + gc);
-          bd[i][0] = v.x; bd[i][1] = v.y; bd[i][2] = v.z; bd[i][3] = v.w;
-        } else {
-          const uint2 v = *reinterpret_cast<const uint2*>(B + (size_t)(CX ? kb >> 1 : kb) * N + gc);
-          bd[i][0] = v.x; bd[i][1] = v.y;
-        }
+      if (FULL || (vecB && kb < K && gcp + 2 <= N)) {
+        b8[i] = *reinterpret_cast<const uint32_t*>(B + (size_t)(CX ? kb >> 1 : kb) * N + gcp);
       } else {
-#pragma unroll
-        for (int d = 0; d < BD; ++d) {
-          uint32_t w = 0;
-#pragma unroll
-          for (int e = 0; e < EPD; ++e) {
-            const int c = gc + d * EPD + e;
-            const uint32_t v = (kb < K && c < N) ? (uint32_t)B[(size_t)(CX ? kb >> 1 : kb) * N + c] : 0u;
-            w |= (EPD == 2 ? (v & 0xffffu) : v) << (16 * e);
-          }
-          bd[i][d] = w;
-        }
+        const uint32_t lo = (kb < K && gcp < N) ? (uint32_t)(uint16_t)B[(size_t)(CX ? kb >> 1 : kb) * N + gcp] : 0u;
+        const uint32_t hi = (kb < K && gcp + 1 < N) ? (uint32_t)(uint16_t)B[(size_t)(CX ? kb >> 1 : kb) * N + gcp + 1] : 0u;
+        b8[i] = lo | (hi << 16);
       }
-    }
     }
   };
 
-  // this thread's partial row / column sums over the K steps: int32 is exact for q15 (at most
-  // 16 x 511 values of |v| <= 2^15 per partial), int64 for q31
-  using PS = typename std::conditional<sizeof(T) == 2, int32_t, int64_t>::type;
-  PS my_rsum = 0, my_csum[CW];
-  [[maybe_unused]] PS my_isum = 0;               // CX: the sum of this thread's imaginary (odd) words of A
-#pragma unroll
-  for (int c = 0; c < CW; ++c) my_csum[c] = 0;
-  int32_t bcs[2] = {0, 0};                       // B8: columns 2cp, 2cp + 1 (exact: <= 8 x 511 x 2^15)
+  // this thread's partial row / column sums over the K steps: int32 is exact (at most 16 x 511
+  // values of |v| <= 2^15 per partial)
+  int32_t my_rsum = 0;
+  [[maybe_unused]] int32_t my_isum = 0;          // CX: the sum of this thread's imaginary (odd) words of A
+  int32_t bcs[2] = {0, 0};                       // columns 2cp, 2cp + 1 (exact: <= 8 x 511 x 2^15)
   i32x16 acc[S][WBM][WBN];
 #pragma unroll
   for (int s = 0; s < S; ++s)
@@ -275,149 +197,66 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v2_kernel(const T* __restrict
   auto stage = [&](int buf) {
     auto As = reinterpret_cast<int8_t (*)[BM][kPitch2]>(lds + buf * BUF);
     auto Bs = reinterpret_cast<int8_t (*)[BN][kPitch2]>(lds + buf * BUF + P * BM * kPitch2);
-    // CX, B8: b8[0], b8[2], b8[4], b8[6] hold the four complex rows; the odd rows of B' exist only as the
-    // byte selectors and complement masks of the plane gather below
-    if constexpr (CX && !B8) {                     // the odd rows of B' (here, not in load(): no wait on the loads there)
+    // exact row / column sums of the original values.  CX: b8[0], b8[2], b8[4], b8[6] hold the four
+    // complex rows; the odd rows of B' exist only as the byte selectors and complement masks of the
+    // plane gather below
+    int32_t ra = 0;
 #pragma unroll
-      for (int i = 1; i < 4; i += 2)
+    for (int d = 0; d < AKD; ++d) ra = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, ad[d]), s2x{1, 1}, ra, false);
+    my_rsum += ra;
+    if constexpr (CX) {
+      int32_t ia = 0;
 #pragma unroll
-        for (int d = 0; d < BD; ++d) {
-          if constexpr (EPD == 2) bd[i][d] = cx_swap_q15(bd[i - 1][d]);
-          else bd[i][d] = (d & 1) ? bd[i - 1][d - 1] : ~bd[i - 1][d + 1];
-        }
-    }
-    // exact row / column sums of the original values
-    if constexpr (sizeof(T) == 2) {
-      int32_t ra = 0;
+      for (int d = 0; d < AKD; ++d) ia = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, ad[d]), s2x{0, 1}, ia, false);
+      my_isum += ia;
 #pragma unroll
-      for (int d = 0; d < AKD; ++d) ra = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, ad[d]), s2x{1, 1}, ra, false);
-      my_rsum += ra;
-      if constexpr (CX) {
-        int32_t ia = 0;
-#pragma unroll
-        for (int d = 0; d < AKD; ++d) ia = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, ad[d]), s2x{0, 1}, ia, false);
-        my_isum += ia;
+      for (int i = 0; i < 8; i += 2) {           // rows (c, d) and (~d, c): c - d - 1 and d + c per complex row
+        bcs[0] = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, b8[i]), s2x{1, -1}, bcs[0], false);
+        bcs[1] = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, b8[i]), s2x{1, 1}, bcs[1], false);
       }
-      if constexpr (B8 && CX) {                    // rows (c, d) and (~d, c): c - d - 1 and d + c per complex row
-#pragma unroll
-        for (int i = 0; i < 8; i += 2) {
-          bcs[0] = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, b8[i]), s2x{1, -1}, bcs[0], false);
-          bcs[1] = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, b8[i]), s2x{1, 1}, bcs[1], false);
-        }
-        bcs[0] -= 4;
-      } else if constexpr (B8) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          bcs[0] = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, b8[i]), s2x{1, 0}, bcs[0], false);
-          bcs[1] = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, b8[i]), s2x{0, 1}, bcs[1], false);
-        }
-      } else {
-#pragma unroll
-        for (int c = 0; c < CW; ++c) {
-          const s2x sel = (c & 1) ? s2x{0, 1} : s2x{1, 0};
-          int32_t cs = 0;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) cs = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, bd[i][c >> 1]), sel, cs, false);
-          my_csum[c] += cs;
-        }
-      }
+      bcs[0] -= 4;
     } else {
 #pragma unroll
-      for (int d = 0; d < AKD; ++d) my_rsum += (int32_t)ad[d];
-      if constexpr (CX) {
-#pragma unroll
-        for (int d = 1; d < AKD; d += 2) my_isum += (int32_t)ad[d];
+      for (int i = 0; i < 8; ++i) {
+        bcs[0] = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, b8[i]), s2x{1, 0}, bcs[0], false);
+        bcs[1] = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, b8[i]), s2x{0, 1}, bcs[1], false);
       }
-#pragma unroll
-      for (int c = 0; c < CW; ++c)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) my_csum[c] += (int32_t)bd[i][c];
     }
     // byte planes -> LDS
 #pragma unroll
     for (int p = 0; p < P; ++p) {
       uint32_t w[AK / 4];
 #pragma unroll
-      for (int q = 0; q < AK / 4; ++q) {
-        if constexpr (sizeof(T) == 2) w[q] = plane_q15<P>(ad[2 * q], ad[2 * q + 1], p);
-        else w[q] = plane4<P>(ad[4 * q], ad[4 * q + 1], ad[4 * q + 2], ad[4 * q + 3], p);
-      }
+      for (int q = 0; q < AK / 4; ++q) w[q] = plane_q15<P>(ad[2 * q], ad[2 * q + 1], p);
 #pragma unroll
       for (int q = 0; q < AK / 16; ++q)
         *reinterpret_cast<uint4*>(&As[p][ar][16 * i8_chunk(ar, ak0 / 16 + q)]) =
             make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-      if constexpr (B8) {
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          const int o = 2 * c + p;                // byte of column 2cp + c, plane p, in a dword
-          uint32_t g0, g1;
-          if constexpr (CX) {
-            // k rows (2k, 2k + 1, 2k + 2, 2k + 3) from complex rows (k, k + 1): the odd rows take the pair's
-            // other word (byte o ^ 2), complemented in column 0 (~d)
-            const uint32_t sel = (uint32_t)o | (uint32_t)(o ^ 2) << 8 | (uint32_t)(4 + o) << 16 | (uint32_t)(4 + (o ^ 2)) << 24;
-            const uint32_t xm = (p != P - 1 ? 0x80808080u : 0u) ^ (c == 0 ? 0xff00ff00u : 0u);
-            g0 = __builtin_amdgcn_perm(b8[2], b8[0], sel) ^ xm;
-            g1 = __builtin_amdgcn_perm(b8[6], b8[4], sel) ^ xm;
-          } else {
-            g0 = gather4(b8[0], b8[1], b8[2], b8[3], o), g1 = gather4(b8[4], b8[5], b8[6], b8[7], o);
-            if (p != P - 1) { g0 ^= 0x80808080u; g1 ^= 0x80808080u; }
-          }
-          const int row = i8_brow8(2 * cp + c);
-          *reinterpret_cast<uint2*>(&Bs[p][row][16 * i8_chunk(row, kb8 >> 1) + 8 * (kb8 & 1)]) = make_uint2(g0, g1);
+      for (int c = 0; c < 2; ++c) {
+        const int o = 2 * c + p;                // byte of column 2cp + c, plane p, in a dword
+        uint32_t g0, g1;
+        if constexpr (CX) {
+          // k rows (2k, 2k + 1, 2k + 2, 2k + 3) from complex rows (k, k + 1): the odd rows take the pair's
+          // other word (byte o ^ 2), complemented in column 0 (~d)
+          const uint32_t sel = (uint32_t)o | (uint32_t)(o ^ 2) << 8 | (uint32_t)(4 + o) << 16 | (uint32_t)(4 + (o ^ 2)) << 24;
+          const uint32_t xm = (p != P - 1 ? 0x80808080u : 0u) ^ (c == 0 ? 0xff00ff00u : 0u);
+          g0 = __builtin_amdgcn_perm(b8[2], b8[0], sel) ^ xm;
+          g1 = __builtin_amdgcn_perm(b8[6], b8[4], sel) ^ xm;
+        } else {
+          g0 = gather4(b8[0], b8[1], b8[2], b8[3], o), g1 = gather4(b8[4], b8[5], b8[6], b8[7], o);
+          if (p != P - 1) { g0 ^= 0x80808080u; g1 ^= 0x80808080u; }
         }
-      } else {
-#pragma unroll
-        for (int c = 0; c < CW; ++c) {
-          const int d = c / EPD, o = (c % EPD) * (int)sizeof(T) + p;
-          uint32_t g = gather4(bd[0][d], bd[1][d], bd[2][d], bd[3][d], o);
-          if (p != P - 1) g ^= 0x80808080u;
-          const int row = i8_brow<CW>(bg * CW + c);
-          *reinterpret_cast<uint32_t*>(&Bs[p][row][16 * i8_chunk(row, bq >> 2) + 4 * (bq & 3)]) = g;
-        }
+        const int row = i8_brow8(2 * cp + c);
+        *reinterpret_cast<uint2*>(&Bs[p][row][16 * i8_chunk(row, kb8 >> 1) + 8 * (kb8 & 1)]) = make_uint2(g0, g1);
       }
     }
   };
-  constexpr int KS = kKT2 / 32;                  // MFMA k-steps per K step
-  i32x4 fa[KS][P][WBM], fb[KS][P][WBN];
-  auto frags = [&](int buf) {
-    auto As = reinterpret_cast<const int8_t (*)[BM][kPitch2]>(lds + buf * BUF);
-    auto Bs = reinterpret_cast<const int8_t (*)[BN][kPitch2]>(lds + buf * BUF + P * BM * kPitch2);
-#pragma unroll
-    for (int kk = 0; kk < KS; ++kk)
-#pragma unroll
-      for (int p = 0; p < P; ++p) {
-#pragma unroll
-        for (int i = 0; i < WBM; ++i) {
-          const int row = wm * 32 * WBM + i * 32 + r;
-          fa[kk][p][i] = *reinterpret_cast<const i32x4*>(&As[p][row][16 * i8_chunk(row, 2 * kk + h)]);
-        }
-#pragma unroll
-        for (int j = 0; j < WBN; ++j) {
-          const int n = wn * 32 * WBN + j * 32 + r;
-          const int row = B8 ? i8_brow8(n) : i8_brow<CW>(n);
-          fb[kk][p][j] = *reinterpret_cast<const i32x4*>(&Bs[p][row][16 * i8_chunk(row, 2 * kk + h)]);
-        }
-      }
-  };
-  auto mma = [&]() {
-#pragma unroll
-    for (int kk = 0; kk < KS; ++kk)
-#pragma unroll
-      for (int p = 0; p < P; ++p)
-#pragma unroll
-        for (int q = 0; q < P; ++q)
-#pragma unroll
-          for (int i = 0; i < WBM; ++i)
-#pragma unroll
-            for (int j = 0; j < WBN; ++j)
-              acc[p + q][i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[kk][p][i], fb[kk][q][j], acc[p + q][i][j], 0, 0, 0);
-  };
-
-  // SPLIT: the second MFMA k-step (kk = 1) of K step kt runs at the head of step kt + 1, from
-  // registers, while that step's first fragment reads are in flight (the barrier only orders the
-  // LDS; register fragments may cross it)
-  constexpr bool SPLIT = MI355X_I8_SPLIT && KS == 2;
-  i32x4 ga[P][WBM], gb[P][WBN], ha[P][WBM], hb[P][WBN];   // SPLIT: kk = 0 / kk = 1 fragments
+  // The second MFMA k-step (kk = 1) of K step kt runs at the head of step kt + 1, from registers,
+  // while that step's first fragment reads are in flight (the barrier only orders the LDS;
+  // register fragments may cross it)
+  static_assert(kKT2 / 32 == 2, "two MFMA k-steps per K step");
+  i32x4 ga[P][WBM], gb[P][WBN], ha[P][WBM], hb[P][WBN];   // kk = 0 / kk = 1 fragments
   auto frags_kk = [&](int buf, int kk, i32x4 (&FA)[P][WBM], i32x4 (&FB)[P][WBN]) {
     auto As = reinterpret_cast<const int8_t (*)[BM][kPitch2]>(lds + buf * BUF);
     auto Bs = reinterpret_cast<const int8_t (*)[BN][kPitch2]>(lds + buf * BUF + P * BM * kPitch2);
@@ -430,8 +269,7 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v2_kernel(const T* __restrict
       }
 #pragma unroll
       for (int j = 0; j < WBN; ++j) {
-        const int n = wn * 32 * WBN + j * 32 + r;
-        const int row = B8 ? i8_brow8(n) : i8_brow<CW>(n);
+        const int row = i8_brow8(wn * 32 * WBN + j * 32 + r);
         FB[p][j] = *reinterpret_cast<const i32x4*>(&Bs[p][row][16 * i8_chunk(row, 2 * kk + h)]);
       }
     }
@@ -456,91 +294,57 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v2_kernel(const T* __restrict
   stage(0);
   if (nk > 1) load(kKT2);
   __syncthreads();
-  I8_STAMP(1);
-  int kt = 0;
-  if constexpr (SPLIT) {
-    frags_kk(0, 0, ga, gb);                      // step 0: nothing outstanding yet
-    frags_kk(0, 1, ha, hb);
-    if (nk > 1) stage(1);
-    if (nk > 2) load(2 * kKT2);
-    mma_kk(ga, gb);
-    __syncthreads();
-    kt = 1;
-    for (; kt + 2 < nk; ++kt) {                  // steady state: one basic block when FULL
-      const int cur = kt & 1;
-      frags_kk(cur, 0, ga, gb);
-      mma_kk(ha, hb);                            // step kt - 1, kk = 1
-      frags_kk(cur, 1, ha, hb);
-      stage(cur ^ 1);
-      load((kt + 2) * kKT2);
-      mma_kk(ga, gb);
-#if MI355X_I8_SCHED
-#pragma unroll
-      for (int i = 0; i < 2 * P * P * WBM * WBN; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, MI355X_I8_SCHED, 0);
-      }
-#endif
-      __syncthreads();
-    }
-    for (; kt < nk; ++kt) {
-      const int cur = kt & 1;
-      frags_kk(cur, 0, ga, gb);
-      mma_kk(ha, hb);
-      frags_kk(cur, 1, ha, hb);
-      if (kt + 1 < nk) stage(cur ^ 1);
-      mma_kk(ga, gb);
-      __syncthreads();
-    }
-    mma_kk(ha, hb);                              // the last step's kk = 1
-  }
-  for (; !SPLIT && kt + 2 < nk; ++kt) {           // steady state: one basic block when FULL
+  frags_kk(0, 0, ga, gb);                      // step 0: nothing outstanding yet
+  frags_kk(0, 1, ha, hb);
+  if (nk > 1) stage(1);
+  if (nk > 2) load(2 * kKT2);
+  mma_kk(ga, gb);
+  __syncthreads();
+  int kt = 1;
+  for (; kt + 2 < nk; ++kt) {                  // steady state: one basic block when FULL
     const int cur = kt & 1;
-    frags(cur);
+    frags_kk(cur, 0, ga, gb);
+    mma_kk(ha, hb);                            // step kt - 1, kk = 1
+    frags_kk(cur, 1, ha, hb);
     stage(cur ^ 1);
     load((kt + 2) * kKT2);
-    mma();
-#if MI355X_I8_SCHED
+    mma_kk(ga, gb);
 #pragma unroll
-    for (int i = 0; i < KS * P * P * WBM * WBN; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                 // one MFMA
-      __builtin_amdgcn_sched_group_barrier(0x002, MI355X_I8_SCHED, 0);   // then VALU
+    for (int i = 0; i < 2 * P * P * WBM * WBN; ++i) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);    // one MFMA
+      __builtin_amdgcn_sched_group_barrier(0x002, 10, 0);   // then up to 10 VALU (DESIGN §4 has the sweep)
     }
-#endif
     __syncthreads();
   }
-  for (; !SPLIT && kt < nk; ++kt) {
+  for (; kt < nk; ++kt) {
     const int cur = kt & 1;
-    frags(cur);
+    frags_kk(cur, 0, ga, gb);
+    mma_kk(ha, hb);
+    frags_kk(cur, 1, ha, hb);
     if (kt + 1 < nk) stage(cur ^ 1);
-    mma();
+    mma_kk(ga, gb);
     __syncthreads();
   }
-  I8_STAMP(2);
+  mma_kk(ha, hb);                              // the last step's kk = 1
 
   // ---- epilogue: exact sums through LDS (reusing the plane buffers), int64 combine.  The
   // partial row / column sums are reduced once (one thread per row, one per column), then every
-  // output reads its two final sums; whole tiles are staged as T in LDS and leave as 16-B
-  // stores, 16 threads per 256-B row (the per-element stores issued one 2- / 4-byte store per
-  // output, 32 lanes covering 64 / 128 B).
+  // output reads its two final sums; whole tiles are staged in LDS and leave as 16-B stores,
+  // 16 threads per 256-B row (the per-element stores issued one 2-byte store per output, 32 lanes
+  // covering 64 B).
   int64_t* rs = reinterpret_cast<int64_t*>(lds);            // [AQ][BM] partials
-  int64_t* cs = rs + AQ * BM;                               // [NQ][BN]
+  int64_t* cs = rs + AQ * BM;                               // [NQ][BN], the first NQB rows in use
   int64_t* rfin = cs + NQ * BN;                             // [BM] final row sums
   int64_t* cfin = rfin + BM;                                // [BN] final column sums
-  T* ct = reinterpret_cast<T*>(cfin + BN);                  // [BM][BN] output tile (FULL)
+  int16_t* ct = reinterpret_cast<int16_t*>(cfin + BN);      // [BM][BN] output tile (FULL)
   int64_t* is = reinterpret_cast<int64_t*>(ct + BM * BN);   // CX: [AQ][BM] partial imaginary sums
   int64_t* ifin = is + AQ * BM;                             // CX: [BM] final ones
-  static_assert((AQ * BM + NQ * BN + BM + BN + (CX ? AQ * BM + BM : 0)) * 8 + BM * BN * sizeof(T) <= 2 * BUF,
+  static_assert((AQ * BM + NQ * BN + BM + BN + (CX ? AQ * BM + BM : 0)) * 8 + BM * BN * 2 <= 2 * BUF,
                 "epilogue fits the planes");
   rs[(tid % AQ) * BM + ar] = (int64_t)my_rsum;
   if constexpr (CX) is[(tid % AQ) * BM + ar] = (int64_t)my_isum;
-  if constexpr (B8) {
-    cs[kb8 * BN + 2 * cp] = (int64_t)bcs[0];
-    cs[kb8 * BN + 2 * cp + 1] = (int64_t)bcs[1];
-  } else {
-#pragma unroll
-    for (int c = 0; c < CW; ++c) cs[bq * BN + bg * CW + c] = (int64_t)my_csum[c];
-  }
+  cs[kb8 * BN + 2 * cp] = (int64_t)bcs[0];
+  cs[kb8 * BN + 2 * cp + 1] = (int64_t)bcs[1];
   __syncthreads();
   for (int i = tid; i < BM + BN; i += kNT2) {
     int64_t sum = 0;
@@ -581,71 +385,57 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v2_kernel(const T* __restrict
         }
         const int64_t sum = (int64_t)v;
         // fast q15 (arm_mat_mult_fast_q15.c:356-401 host branch): q31_t modular sum, (q15)(sum >> 15)
-        T o;
-        if constexpr (sizeof(T) == 2) o = fast ? (T)((int32_t)(uint32_t)v >> 15) : (T)ssat16((int32_t)(sum >> 15));
-        else if constexpr (CX) o = (T)clip_q63_q31(sum >> 31);   // arm_mat_cmplx_mult_q31.c:1029-1030
-        else o = (T)(int32_t)(sum >> 31);
+        const int16_t o = fast ? (int16_t)((int32_t)(uint32_t)v >> 15) : (int16_t)ssat16((int32_t)(sum >> 15));
         if constexpr (FULL) ct[rr * BN + cc] = o;
         else if (grow < M && gcol < N) C[(size_t)grow * N + gcol] = o;
       }
     }
   }
-  I8_STAMP(3);
   if constexpr (FULL) {
     __syncthreads();
-    constexpr int VPR = BN * (int)sizeof(T) / 16;            // 16-B words per tile row
-    static_assert(VPR * 16 == BN * (int)sizeof(T), "whole 16-B words per row");
+    constexpr int VPR = BN * 2 / 16;                         // 16-B words per tile row
+    static_assert(VPR * 16 == BN * 2, "whole 16-B words per row");
 #pragma unroll
     for (int w = tid; w < BM * VPR; w += kNT2) {
       const int rr = w / VPR, cw = w % VPR;
-      *reinterpret_cast<uint4*>(C + (size_t)(row0 + rr) * N + col0 + cw * (16 / (int)sizeof(T))) =
-          *reinterpret_cast<const uint4*>(ct + rr * BN + cw * (16 / (int)sizeof(T)));
+      *reinterpret_cast<uint4*>(C + (size_t)(row0 + rr) * N + col0 + cw * 8) =
+          *reinterpret_cast<const uint4*>(ct + rr * BN + cw * 8);
     }
   }
-  I8_STAMP(4);
 }
 
-// ---- v3 kernel (round 4): the v2 tiling with B staged ROW-major.  B's
+// ---- v3 kernel (q31; round 4): the v2 tiling with B staged ROW-major.  B's
 // planes are stored as [k][n] byte rows (the global layout) and the MFMA's k-contiguous
 // operand is read with ds_read_b64_tr_b8 (gfx950's 8-bit transposed LDS read: per 16-lane group
 // an 8-row x 16-column byte block, lane i receiving column i, row q in byte q;
 // tools/probes/tr_b8.hip), so the v_perm transpose of v2's staging disappears: a thread stages
 // one k-row segment of B (32 bytes) with two 16-B loads and splits it into planes with one
 // v_perm per 4 values.  Column sums accumulate per thread over the k-rows it stages (its
-// columns are fixed for the whole K loop).  Selected by MI355X_I8_V3.
-template <typename T> struct I8B3 {               // B staging geometry
-  static constexpr int BN = I8Cfg<T>::BN, EB = 64 * BN / kNT2;   // elements per thread (16 q15 / 8 q31)
-  static constexpr int TPR = BN / EB;                            // threads per k-row (8)
-  // bytes per plane row: a multiple of 32 that is an odd multiple of 8 dwords mod 64, so the
-  // 8 rows x 8 dwords a 32-lane group of ds_read_b64_tr_b8 touches cover the 64 banks once
-  // (MI355X_I8_V3P overrides; BN + 16 measured 8x the v2 conflicts)
-#ifdef MI355X_I8_V3P
-  static constexpr int PITCH = MI355X_I8_V3P;
-#else
-  static constexpr int PITCH = BN == 128 ? 160 : 96;
-#endif
-};
+// columns are fixed for the whole K loop).
 typedef int v2i32_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ v2i32_t tr_b8(const int8_t* p) {   // p: a generic pointer into LDS
   return __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) v2i32_t*)p);
 }
 
-template <typename T, bool FULL, bool CX = false>
-__global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict__ A, const T* __restrict__ B,
-                                                             T* __restrict__ C, int M, int K, int N, int fast) {
-  using G = I8Cfg<T>;
-  using GB = I8B3<T>;
-  constexpr int P = Slices<T>::P, S = 2 * P - 1;
-  constexpr int64_t C0 = Slices<T>::C0;
+template <bool FULL, bool CX = false>
+__global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const int32_t* __restrict__ A, const int32_t* __restrict__ B,
+                                                             int32_t* __restrict__ C, int M, int K, int N, int fast) {
+  using G = I8Cfg<int32_t>;
+  constexpr int P = 4, S = 2 * P - 1;            // byte planes, weight classes p + q
+  constexpr int64_t C0 = 128LL * (1 + 256 + 65536);
   constexpr int BM = G::BM, BN = G::BN, WBM = G::WBM, WBN = G::WBN, kKT2 = G::KT, kPitch2 = kKT2;
-  constexpr int EPD = 4 / sizeof(T);
-  constexpr int AK = BM * kKT2 / kNT2, AKD = AK / EPD, AQ = kKT2 / AK;
-  constexpr int EB = GB::EB, EBD = EB / EPD, TPR = GB::TPR, BP = GB::PITCH;
+  constexpr int EPD = 1;                         // elements per dword (the guarded loads share v2's loop nest)
+  constexpr int AK = BM * kKT2 / kNT2, AKD = AK, AQ = kKT2 / AK;   // A elements per staging thread (16), threads per row
+  constexpr int EB = kKT2 * BN / kNT2, EBD = EB, TPR = BN / EB;    // B elements per staging thread (8), threads per k-row
+  // bytes per B plane row: a multiple of 32 that is an odd multiple of 8 dwords mod 64, so the
+  // 8 rows x 8 dwords a 32-lane group of ds_read_b64_tr_b8 touches cover the 64 banks once
+  // (BN + 16 measured 8x the v2 conflicts)
+  constexpr int BP = 96;
   constexpr int ABUF = P * BM * kPitch2, BBUF = P * kKT2 * BP;
   constexpr int BUF = ABUF + BBUF;
   // the epilogue reuses the plane buffers: partial sums (one column partial per staged k-row),
   // final sums and the output tile
-  constexpr int EPI = (AQ * BM + kKT2 * BN + BM + BN + (CX ? AQ * BM + BM : 0)) * 8 + BM * BN * (int)sizeof(T);
+  constexpr int EPI = (AQ * BM + kKT2 * BN + BM + BN + (CX ? AQ * BM + BM : 0)) * 8 + BM * BN * 4;
   __shared__ __attribute__((aligned(16))) int8_t lds[2 * BUF > EPI ? 2 * BUF : EPI];
 
   const int tilesN = (N + BN - 1) / BN, tiles = tilesN * ((M + BM - 1) / BM);
@@ -665,8 +455,8 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict
   const int ar = tid / AQ, ak0 = AK * (tid % AQ);
   const int bk = tid / TPR, bc = EB * (tid % TPR);
   const int gr = row0 + ar, gc = col0 + bc;
-  const bool vecA = FULL || (((K * (int)sizeof(T)) % 16) == 0 && (((uintptr_t)A) & 15) == 0);
-  const bool vecB = FULL || (((N * (int)sizeof(T)) % 16) == 0 && (((uintptr_t)B) & 15) == 0);
+  const bool vecA = FULL || (((K * 4) % 16) == 0 && (((uintptr_t)A) & 15) == 0);
+  const bool vecB = FULL || (((N * 4) % 16) == 0 && (((uintptr_t)B) & 15) == 0);
 
   uint32_t ad[AKD], bd[EBD];
   auto load = [&](int k0) {
@@ -686,7 +476,7 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict
         for (int e = 0; e < EPD; ++e) {
           const int k = ka + d * EPD + e;
           const uint32_t v = (gr < M && k < K) ? (uint32_t)A[(size_t)gr * K + k] : 0u;
-          w |= (EPD == 2 ? (v & 0xffffu) : v) << (16 * e);
+          w |= v << (16 * e);
         }
         ad[d] = w;
       }
@@ -707,24 +497,22 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict
         for (int e = 0; e < EPD; ++e) {
           const int c = gc + d * EPD + e;
           const uint32_t v = (kb < K && c < N) ? (uint32_t)B[(size_t)(CX ? kb >> 1 : kb) * N + c] : 0u;
-          w |= (EPD == 2 ? (v & 0xffffu) : v) << (16 * e);
+          w |= v << (16 * e);
         }
         bd[d] = w;
       }
     }
   };
 
-  int64_t my_rsum = 0;                           // CX, q31: the even (real) words only, the odd ones in my_isum
+  int64_t my_rsum = 0;                           // CX: the even (real) words only, the odd ones in my_isum
   [[maybe_unused]] int64_t my_isum = 0;          // CX: the sum of this thread's imaginary (odd) words of A
   // CX: this thread's plane row bk is row 2k (the words as loaded) or row 2k + 1 ((~d, c) per pair) for the
   // whole K loop.  An odd row is never formed in registers: its planes come from the loaded words with the
   // pair-swapping byte selector and the complement mask below, and its column sums from the loaded words'
   // sums at the end (sum of ~d = -(sum of d) - the number of staged rows, zero fill included)
   [[maybe_unused]] const bool odd = CX && (bk & 1);
-  // column sums of the k-rows this thread stages (at most K / 64 <= 511 of them): exact in int32
-  // for q15 (|v| <= 2^15), int64 for q31
-  using CS = typename std::conditional<sizeof(T) == 2, int32_t, int64_t>::type;
-  CS my_csum[EB];
+  // column sums of the k-rows this thread stages (at most K / 64 <= 511 of them)
+  int64_t my_csum[EB];
 #pragma unroll
   for (int c = 0; c < EB; ++c) my_csum[c] = 0;
   i32x16 acc[S][WBM][WBN];
@@ -740,43 +528,22 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict
   auto stage = [&](int buf) {
     auto As = reinterpret_cast<int8_t (*)[BM][kPitch2]>(lds + buf * BUF);
     int8_t* Bs = lds + buf * BUF + ABUF;           // [P][kKT2][BP]
-    if constexpr (sizeof(T) == 2) {
-      int32_t ra = 0;
 #pragma unroll
-      for (int d = 0; d < AKD; ++d) ra = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, ad[d]), s2x{1, 1}, ra, false);
-      my_rsum += ra;
+    for (int d = 0; d < AKD; ++d) {
       if constexpr (CX) {
-        int32_t ia = 0;
-#pragma unroll
-        for (int d = 0; d < AKD; ++d) ia = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2x, ad[d]), s2x{0, 1}, ia, false);
-        my_isum += ia;
+        if (d & 1) my_isum += (int32_t)ad[d];
+        else my_rsum += (int32_t)ad[d];
+      } else {
+        my_rsum += (int32_t)ad[d];
       }
-#pragma unroll
-      for (int d = 0; d < EBD; ++d) {
-        my_csum[2 * d] += (int16_t)(bd[d] & 0xffffu);
-        my_csum[2 * d + 1] += (int16_t)(bd[d] >> 16);
-      }
-    } else {
-#pragma unroll
-      for (int d = 0; d < AKD; ++d) {
-        if constexpr (CX) {
-          if (d & 1) my_isum += (int32_t)ad[d];
-          else my_rsum += (int32_t)ad[d];
-        } else {
-          my_rsum += (int32_t)ad[d];
-        }
-      }
-#pragma unroll
-      for (int d = 0; d < EBD; ++d) my_csum[d] += (int32_t)bd[d];
     }
+#pragma unroll
+    for (int d = 0; d < EBD; ++d) my_csum[d] += (int32_t)bd[d];
 #pragma unroll
     for (int p = 0; p < P; ++p) {
       uint32_t w[AK / 4];
 #pragma unroll
-      for (int q = 0; q < AK / 4; ++q) {
-        if constexpr (sizeof(T) == 2) w[q] = plane_q15<P>(ad[2 * q], ad[2 * q + 1], p);
-        else w[q] = plane4<P>(ad[4 * q], ad[4 * q + 1], ad[4 * q + 2], ad[4 * q + 3], p);
-      }
+      for (int q = 0; q < AK / 4; ++q) w[q] = plane4<P>(ad[4 * q], ad[4 * q + 1], ad[4 * q + 2], ad[4 * q + 3], p);
 #pragma unroll
       for (int q = 0; q < AK / 16; ++q)
         *reinterpret_cast<uint4*>(&As[p][ar][16 * i8_chunk(ar, ak0 / 16 + q)]) =
@@ -787,26 +554,20 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict
         // byte p of the four values of a dword group, the pairs swapped in an odd row; there the first
         // byte of each pair (~d) is complemented on top of the lower planes' -128
         const uint32_t up = (uint32_t)p;
-        const uint32_t se = sizeof(T) == 2 ? (up | (2 + up) << 8 | (4 + up) << 16 | (6 + up) << 24) : 0x0c0c0400u + 0x0101u * up;
-        const uint32_t so = sizeof(T) == 2 ? ((2 + up) | up << 8 | (6 + up) << 16 | (4 + up) << 24) : 0x0c0c0004u + 0x0101u * up;
+        const uint32_t se = 0x0c0c0400u + 0x0101u * up, so = 0x0c0c0004u + 0x0101u * up;
         const uint32_t sel = odd ? so : se;
         const uint32_t xm = (p != P - 1 ? 0x80808080u : 0u) ^ (odd ? 0x00ff00ffu : 0u);
 #pragma unroll
-        for (int q = 0; q < EB / 4; ++q) {
-          if constexpr (sizeof(T) == 2) wb[q] = __builtin_amdgcn_perm(bd[2 * q + 1], bd[2 * q], sel) ^ xm;
-          else wb[q] = (__builtin_amdgcn_perm(bd[4 * q + 1], bd[4 * q], sel) |
-                        (__builtin_amdgcn_perm(bd[4 * q + 3], bd[4 * q + 2], sel) << 16)) ^ xm;
-        }
+        for (int q = 0; q < EB / 4; ++q)
+          wb[q] = (__builtin_amdgcn_perm(bd[4 * q + 1], bd[4 * q], sel) |
+                   (__builtin_amdgcn_perm(bd[4 * q + 3], bd[4 * q + 2], sel) << 16)) ^ xm;
       } else {
 #pragma unroll
-      for (int q = 0; q < EB / 4; ++q) {
-        if constexpr (sizeof(T) == 2) wb[q] = plane_q15<P>(bd[2 * q], bd[2 * q + 1], p);
-        else wb[q] = plane4<P>(bd[4 * q], bd[4 * q + 1], bd[4 * q + 2], bd[4 * q + 3], p);
-      }
+        for (int q = 0; q < EB / 4; ++q) wb[q] = plane4<P>(bd[4 * q], bd[4 * q + 1], bd[4 * q + 2], bd[4 * q + 3], p);
       }
       int8_t* dstb = Bs + (size_t)p * kKT2 * BP + bk * BP + bc;
-      if constexpr (EB == 16) *reinterpret_cast<uint4*>(dstb) = make_uint4(wb[0], wb[1], wb[2], wb[3]);
-      else *reinterpret_cast<uint2*>(dstb) = make_uint2(wb[0], wb[1]);
+      static_assert(EB == 8, "one ds_write_b64 per plane");
+      *reinterpret_cast<uint2*>(dstb) = make_uint2(wb[0], wb[1]);
     }
   };
   constexpr int KS = kKT2 / 32;
@@ -850,99 +611,27 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict
               acc[p + q][i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[kk][p][i], fb[kk][q][j], acc[p + q][i][j], 0, 0, 0);
   };
 
-  // as v2 (kk = 1 MFMAs under the next step's reads) for q15 only: with q31's four planes the two
-  // fragment sets spill
-  constexpr bool SPLIT = MI355X_I8_SPLIT && KS == 2 && sizeof(T) == 2;
-  i32x4 ga[P][WBM], gb[P][WBN], ha[P][WBM], hb[P][WBN];
-  auto frags_kk = [&](int buf, int kk, i32x4 (&FA)[P][WBM], i32x4 (&FB)[P][WBN]) {
-    auto As = reinterpret_cast<const int8_t (*)[BM][kPitch2]>(lds + buf * BUF);
-    const int8_t* Bs = lds + buf * BUF + ABUF;
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-#pragma unroll
-      for (int i = 0; i < WBM; ++i) {
-        const int row = wm * 32 * WBM + i * 32 + r;
-        FA[p][i] = *reinterpret_cast<const i32x4*>(&As[p][row][16 * i8_chunk(row, 2 * kk + h)]);
-      }
-#pragma unroll
-      for (int j = 0; j < WBN; ++j) {
-        const int col = wn * 32 * WBN + j * 32 + 16 * gq + 8 * (li & 1);
-        const int8_t* b0 = Bs + (size_t)p * kKT2 * BP + (32 * kk + 16 * h + (li >> 1)) * BP + col;
-        const v2i32_t lo = tr_b8(b0), hi = tr_b8(b0 + 8 * BP);
-        FB[p][j] = i32x4{lo.x, lo.y, hi.x, hi.y};
-      }
-    }
-  };
-  auto mma_kk = [&](const i32x4 (&FA)[P][WBM], const i32x4 (&FB)[P][WBN]) {
-#pragma unroll
-    for (int p = 0; p < P; ++p)
-#pragma unroll
-      for (int q = 0; q < P; ++q)
-#pragma unroll
-        for (int i = 0; i < WBM; ++i)
-#pragma unroll
-          for (int j = 0; j < WBN; ++j)
-            acc[p + q][i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(FA[p][i], FB[q][j], acc[p + q][i][j], 0, 0, 0);
-  };
-
+  // (no split of the MFMA k-steps as in v2: with four planes the two fragment sets spill)
   const int nk = (K + kKT2 - 1) / kKT2;
   load(0);
   stage(0);
   if (nk > 1) load(kKT2);
   __syncthreads();
   int kt = 0;
-  if constexpr (SPLIT) {
-    frags_kk(0, 0, ga, gb);
-    frags_kk(0, 1, ha, hb);
-    if (nk > 1) stage(1);
-    if (nk > 2) load(2 * kKT2);
-    mma_kk(ga, gb);
-    __syncthreads();
-    kt = 1;
-    for (; kt + 2 < nk; ++kt) {
-      const int cur = kt & 1;
-      frags_kk(cur, 0, ga, gb);
-      mma_kk(ha, hb);
-      frags_kk(cur, 1, ha, hb);
-      stage(cur ^ 1);
-      load((kt + 2) * kKT2);
-      mma_kk(ga, gb);
-#if MI355X_I8_SCHED_V3
-#pragma unroll
-      for (int i = 0; i < 2 * P * P * WBM * WBN; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, MI355X_I8_SCHED_V3, 0);
-      }
-#endif
-      __syncthreads();
-    }
-    for (; kt < nk; ++kt) {
-      const int cur = kt & 1;
-      frags_kk(cur, 0, ga, gb);
-      mma_kk(ha, hb);
-      frags_kk(cur, 1, ha, hb);
-      if (kt + 1 < nk) stage(cur ^ 1);
-      mma_kk(ga, gb);
-      __syncthreads();
-    }
-    mma_kk(ha, hb);
-  }
-  for (; !SPLIT && kt + 2 < nk; ++kt) {
+  for (; kt + 2 < nk; ++kt) {
     const int cur = kt & 1;
     frags(cur);
     stage(cur ^ 1);
     load((kt + 2) * kKT2);
     mma();
-#if MI355X_I8_SCHED_V3
 #pragma unroll
     for (int i = 0; i < KS * P * P * WBM * WBN; ++i) {
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                 // one MFMA
-      __builtin_amdgcn_sched_group_barrier(0x002, MI355X_I8_SCHED_V3, 0);   // then VALU
+      __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);                 // then up to 6 VALU (DESIGN §4 has the sweep)
     }
-#endif
     __syncthreads();
   }
-  for (; !SPLIT && kt < nk; ++kt) {
+  for (; kt < nk; ++kt) {
     const int cur = kt & 1;
     frags(cur);
     if (kt + 1 < nk) stage(cur ^ 1);
@@ -956,10 +645,10 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict
   int64_t* cs = rs + AQ * BM;                               // [64 k-rows][BN]
   int64_t* rfin = cs + NQB * BN;
   int64_t* cfin = rfin + BM;
-  T* ct = reinterpret_cast<T*>(cfin + BN);
+  int32_t* ct = reinterpret_cast<int32_t*>(cfin + BN);
   int64_t* is = reinterpret_cast<int64_t*>(ct + BM * BN);   // CX: [AQ][BM] partial imaginary sums
   int64_t* ifin = is + AQ * BM;                             // CX: [BM] final ones
-  if constexpr (CX && sizeof(T) == 4) rs[(tid % AQ) * BM + ar] = my_rsum + my_isum;
+  if constexpr (CX) rs[(tid % AQ) * BM + ar] = my_rsum + my_isum;
   else rs[(tid % AQ) * BM + ar] = my_rsum;
   if constexpr (CX) is[(tid % AQ) * BM + ar] = my_isum;
 #pragma unroll
@@ -1010,10 +699,9 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict
           if (!(cc & 1)) v += (uint64_t)ifin[rr];             // real outputs: b (~d) + b = -b d
         }
         const int64_t sum = (int64_t)v;
-        T o;
-        if constexpr (sizeof(T) == 2) o = fast ? (T)((int32_t)(uint32_t)v >> 15) : (T)ssat16((int32_t)(sum >> 15));
-        else if constexpr (CX) o = (T)clip_q63_q31(sum >> 31);
-        else o = (T)(int32_t)(sum >> 31);
+        int32_t o;
+        if constexpr (CX) o = clip_q63_q31(sum >> 31);       // arm_mat_cmplx_mult_q31.c:1029-1030
+        else o = (int32_t)(sum >> 31);
         if constexpr (FULL) ct[rr * BN + cc] = o;
         else if (grow < M && gcol < N) C[(size_t)grow * N + gcol] = o;
       }
@@ -1021,12 +709,12 @@ __global__ __launch_bounds__(kNT2) void mat_mult_i8v3_kernel(const T* __restrict
   }
   if constexpr (FULL) {
     __syncthreads();
-    constexpr int VPR = BN * (int)sizeof(T) / 16;
+    constexpr int VPR = BN * 4 / 16;
 #pragma unroll
     for (int w = tid; w < BM * VPR; w += kNT2) {
       const int rr = w / VPR, cw = w % VPR;
-      *reinterpret_cast<uint4*>(C + (size_t)(row0 + rr) * N + col0 + cw * (16 / (int)sizeof(T))) =
-          *reinterpret_cast<const uint4*>(ct + rr * BN + cw * (16 / (int)sizeof(T)));
+      *reinterpret_cast<uint4*>(C + (size_t)(row0 + rr) * N + col0 + cw * 4) =
+          *reinterpret_cast<const uint4*>(ct + rr * BN + cw * 4);
     }
   }
 }
@@ -1082,20 +770,11 @@ static hipError_t launch_fixed(int m, int k, int n, const T* a, const T* b, T* c
     const bool full = m % G::BM == 0 && n % G::BN == 0 && k % G::KT == 0 &&
                       ((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0 && (k * sizeof(T)) % 16 == 0 &&
                       (n * sizeof(T)) % 16 == 0 && ((uintptr_t)c & 15) == 0;
-    constexpr int V3 = CX ? MI355X_I8_CX_V3 : MI355X_I8_V3;
-    if (V3 == 1 || (V3 == 2 && sizeof(T) == 4)) {   // 2: q31 only
-      if (full)
-        hipLaunchKernelGGL((mat_mult_i8v3_kernel<T, true, CX>), dim3(tiles * batch), dim3(kNT2), 0, st, a, b, c, m, k, n,
-                           fast);
-      else
-        hipLaunchKernelGGL((mat_mult_i8v3_kernel<T, false, CX>), dim3(tiles * batch), dim3(kNT2), 0, st, a, b, c, m, k,
-                           n, fast);
-    } else if (full)
-      hipLaunchKernelGGL((mat_mult_i8v2_kernel<T, true, CX>), dim3(tiles * batch), dim3(kNT2), 0, st, a, b, c, m, k, n,
-                         fast);
-    else
-      hipLaunchKernelGGL((mat_mult_i8v2_kernel<T, false, CX>), dim3(tiles * batch), dim3(kNT2), 0, st, a, b, c, m, k, n,
-                         fast);
+    auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(tiles * batch), dim3(kNT2), 0, st, a, b, c, m, k, n, fast);
+    };
+    if constexpr (sizeof(T) == 2) full ? go(mat_mult_i8v2_kernel<true, CX>) : go(mat_mult_i8v2_kernel<false, CX>);
+    else full ? go(mat_mult_i8v3_kernel<true, CX>) : go(mat_mult_i8v3_kernel<false, CX>);
   } else if (CX) {
     hipLaunchKernelGGL(mat_cmplx_mult_fixed_valu_kernel<T>, dim3((n + 255) / 256, m, batch), dim3(256), 0, st, a, b,
                        c, m, k, n);
@@ -1210,12 +889,5 @@ hipError_t mat_cmplx_trans_q15_launch(int k, int n, const int16_t* b, int16_t* b
   hipLaunchKernelGGL(mat_cmplx_trans_q15_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, st, b, bt, k, n);
   return hipGetLastError();
 }
-
-#if MI355X_I8_STAMPS
-extern "C" int arm_mi355x_i8_stamps(uint64_t* out, size_t rows) {   // diagnostic builds only
-  const size_t n = rows < (size_t)kI8Stamps ? rows : (size_t)kI8Stamps;
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_i8_stamps), n * 8 * sizeof(uint64_t), 0, hipMemcpyDeviceToHost);
-}
-#endif
 
 }  // namespace mi355x

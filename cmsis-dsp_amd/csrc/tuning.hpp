@@ -161,29 +161,6 @@
 #define MI355X_LMS_LDS 64  // most taps with coefficients and ring in LDS (512 B per tap and wave); beyond: global
 #endif
 
-// ---- mat_mult_fixed.hip
-#ifndef MI355X_I8_SCHED
-#define MI355X_I8_SCHED 10
-#endif
-#ifndef MI355X_I8_SCHED_V3  // the same hint in the tr_b8 kernel (q31)
-#define MI355X_I8_SCHED_V3 6
-#endif
-#ifndef MI355X_I8_STAMPS    // diagnostic: per-workgroup phase timestamps (mat_mult_fixed.hip)
-#define MI355X_I8_STAMPS 0
-#endif
-#ifndef MI355X_I8_B8        // q15: B staged by 8-row x column-pair threads (ds_write_b64)
-#define MI355X_I8_B8 1
-#endif
-#ifndef MI355X_I8_SPLIT     // v2: a K step's second MFMA k-step issued under the next step's fragment reads
-#define MI355X_I8_SPLIT 1
-#endif
-#ifndef MI355X_I8_V3
-#define MI355X_I8_V3 2
-#endif
-#ifndef MI355X_I8_CX_V3     // the same choice for the complex products (arm_mat_cmplx_mult_q15 / _q31)
-#define MI355X_I8_CX_V3 MI355X_I8_V3
-#endif
-
 // ---- mfcc_f32.hip
 #ifndef MI355X_MFCC_UNROLL
 #define MI355X_MFCC_UNROLL 8        // Mel / DCT dot products: loads issued 8 taps ahead

@@ -61,15 +61,15 @@ template <typename T> struct V3Cfg;
 // accumulators per 32 x 32 subtile; D = LDS ring depth (K steps resident).  4-wave workgroups
 // with a 64 KiB ring, so two independent workgroups share a CU and one's prologue, barrier
 // waits and epilogue overlap the other's MFMAs.
-#ifndef MI355X_I8_RING
-#define MI355X_I8_RING 2
+#ifndef PROBE_I8_RING
+#define PROBE_I8_RING 2
 #endif
 template <> struct V3Cfg<int16_t> {
-  static constexpr int WM = 2, WN = 2, WBM = 2, WBN = 2, D = MI355X_I8_RING;
+  static constexpr int WM = 2, WN = 2, WBM = 2, WBN = 2, D = PROBE_I8_RING;
   static constexpr int BM = 32 * WM * WBM, BN = 32 * WN * WBN, NT = 64 * WM * WN;
 };
 template <> struct V3Cfg<int32_t> {
-  static constexpr int WM = 2, WN = 2, WBM = 1, WBN = 1, D = MI355X_I8_RING;
+  static constexpr int WM = 2, WN = 2, WBM = 1, WBN = 1, D = PROBE_I8_RING;
   static constexpr int BM = 32 * WM * WBM, BN = 32 * WN * WBN, NT = 64 * WM * WN;
 };
 
