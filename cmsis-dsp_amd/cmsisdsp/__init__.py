@@ -514,6 +514,34 @@ def arm_mat_cmplx_mult_q15(pSrcA, pSrcB, pScratch):
     return _amd.arm_mat_cmplx_mult("q15", _arr(pSrcA, _np.int16), b, _np.zeros(max(b.size, 1), dtype=_np.int16))
 
 
+def arm_mat_inverse_f32(src):
+    """cmsisdsp_matrix.c cmsis_arm_mat_inverse_f32 (:1832-1860): (status, dst).  The wrapper inverts a private
+    copy, so the caller's array is left as it is."""
+    return _amd.arm_mat_inverse(_arr(src, _np.float32))
+
+
+def arm_mat_cholesky_f32(src):
+    """cmsis_arm_mat_cholesky_f32 (:1896-1933): (status, dst), dst zero-filled before the call as there, so its
+    strict upper triangle is zero."""
+    return _amd.arm_mat_cholesky(_arr(src, _np.float32))
+
+
+def arm_mat_ldlt_f32(src):
+    """cmsis_arm_mat_ldlt_f32 (:1977-2015): (status, l, d, perm), perm an int16 array as there."""
+    st, l, d, pp = _amd.arm_mat_ldlt(_arr(src, _np.float32))
+    return st, l, d, pp.view(_np.int16)
+
+
+def arm_mat_solve_lower_triangular_f32(pSrcA, pSrcB):
+    """cmsis_arm_mat_solve_lower_triangular_f32 (:2063-2098): (status, x) with pSrcA x = pSrcB [n, cols]."""
+    return _amd.arm_mat_solve_lower_triangular(_arr(pSrcA, _np.float32), _arr(pSrcB, _np.float32))
+
+
+def arm_mat_solve_upper_triangular_f32(pSrcA, pSrcB):
+    """cmsis_arm_mat_solve_upper_triangular_f32 (:2137-2171)."""
+    return _amd.arm_mat_solve_upper_triangular(_arr(pSrcA, _np.float32), _arr(pSrcB, _np.float32))
+
+
 def arm_mat_mult_fast_q31(pSrcA, pSrcB):
     """cmsisdsp_matrix.c cmsis_arm_mat_mult_fast_q31: (status, C)."""
     return _amd.arm_mat_mult_fixed("fast_q31", _arr(pSrcA, _np.int32), _arr(pSrcB, _np.int32))

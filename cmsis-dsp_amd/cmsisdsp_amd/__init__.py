@@ -51,6 +51,7 @@ def _load():
     _abi.bind(lib, _abi.BIQUAD)
     _abi.bind(lib, _abi.ADAPTIVE)
     _abi.bind(lib, _abi.CMPLX_MAT)
+    _abi.bind(lib, _abi.MAT_SOLVE)
     _abi.bind(lib, _abi.BATCHED)
     return lib
 
@@ -660,6 +661,108 @@ def mat_cmplx_mult_batch(a, b, c, stream=None):
     st = fn(C.byref(A), C.byref(B), C.byref(Cm), batch, _stream_ptr(stream))
     if st != ARM_MATH_SUCCESS:
         raise RuntimeError(f"{fn.__name__} -> {st}: {last_error()[1]}")
+
+
+def _matf(x):
+    """arm_matrix_instance_f32 over a 2-D numpy array (its own shape) or the items of a [batch, r, c] tensor."""
+    if isinstance(x, np.ndarray):
+        return _abi.arm_matrix_instance_f32(x.shape[0], x.shape[1], C.cast(x.ctypes.data, _abi.c_f32p))
+    return _abi.arm_matrix_instance_f32(x.shape[-2], x.shape[-1], C.cast(x.data_ptr(), _abi.c_f32p))
+
+
+def arm_mat_inverse(src):
+    """(status, dst) through arm_mat_inverse_f32 (drop-in, numpy).  The call destroys its copy of src."""
+    s = np.array(src, dtype=np.float32, order="C")
+    d = np.zeros_like(s)
+    st = lib.arm_mat_inverse_f32(C.byref(_matf(s)), C.byref(_matf(d)))
+    _check_void("arm_mat_inverse_f32")
+    return st, d
+
+
+def arm_mat_cholesky(src):
+    """(status, dst) through arm_mat_cholesky_f32: dst starts as zeros, so its strict upper triangle is zero."""
+    s = np.ascontiguousarray(src, dtype=np.float32)
+    d = np.zeros_like(s)
+    st = lib.arm_mat_cholesky_f32(C.byref(_matf(s)), C.byref(_matf(d)))
+    _check_void("arm_mat_cholesky_f32")
+    return st, d
+
+
+def arm_mat_ldlt(src):
+    """(status, l, d, pp) through arm_mat_ldlt_f32: P A P^T = L D L^T, pp the uint16 pivot of each step."""
+    s = np.ascontiguousarray(src, dtype=np.float32)
+    l, d = np.zeros_like(s), np.zeros_like(s)
+    pp = np.zeros(s.shape[0], dtype=np.uint16)
+    st = lib.arm_mat_ldlt_f32(C.byref(_matf(s)), C.byref(_matf(l)), C.byref(_matf(d)), pp.ctypes.data)
+    _check_void("arm_mat_ldlt_f32")
+    return st, l, d, pp
+
+
+def _arm_mat_solve(fn, t, a):
+    t = np.ascontiguousarray(t, dtype=np.float32)
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    x = np.zeros_like(a)
+    st = getattr(lib, fn)(C.byref(_matf(t)), C.byref(_matf(a)), C.byref(_matf(x)))
+    _check_void(fn)
+    return st, x
+
+
+def arm_mat_solve_lower_triangular(lt, a):
+    """(status, x) with lt x = a through arm_mat_solve_lower_triangular_f32; a is [n, cols]."""
+    return _arm_mat_solve("arm_mat_solve_lower_triangular_f32", lt, a)
+
+
+def arm_mat_solve_upper_triangular(ut, a):
+    """(status, x) with ut x = a through arm_mat_solve_upper_triangular_f32; a is [n, cols]."""
+    return _arm_mat_solve("arm_mat_solve_upper_triangular_f32", ut, a)
+
+
+def _solve_status(ref, status):
+    import torch
+    if status is None:
+        status = torch.empty(ref.shape[0], dtype=torch.int32, device=ref.device)
+    return status, C.c_void_p(status.data_ptr() if status is not False else None)
+
+
+def _solve_call(name, *args):
+    st = getattr(lib, name)(*args)
+    if st != ARM_MATH_SUCCESS:
+        raise RuntimeError(f"{name} -> {st}: {last_error()[1]}")
+
+
+def mat_inverse_batch(src, dst, status=None, stream=None):
+    """dst[i] = inverse(src[i]) for contiguous float32 device tensors [batch, n, n] (arm_mat_inverse_f32_batch);
+    src is destroyed as by the reference.  Returns the per-item int32 status tensor (status: a tensor to fill,
+    None to allocate one, False to pass NULL and return None)."""
+    status, ps = _solve_status(src, status)
+    _solve_call("arm_mat_inverse_f32_batch", C.byref(_matf(src)), C.byref(_matf(dst)), src.shape[0], ps,
+                _stream_ptr(stream))
+    return None if status is False else status
+
+
+def mat_cholesky_batch(src, dst, status=None, stream=None):
+    """The lower triangle of dst[i] = cholesky(src[i]) (arm_mat_cholesky_f32_batch); dst may be src."""
+    status, ps = _solve_status(src, status)
+    _solve_call("arm_mat_cholesky_f32_batch", C.byref(_matf(src)), C.byref(_matf(dst)), src.shape[0], ps,
+                _stream_ptr(stream))
+    return None if status is False else status
+
+
+def mat_ldlt_batch(src, l, d, pp, stream=None):
+    """l[i], d[i], pp[i] = ldlt(src[i]) (arm_mat_ldlt_f32_batch); pp is an int16 / uint16 tensor [batch, n]
+    holding the uint16 pivots.  Every item succeeds, as in the reference."""
+    _solve_call("arm_mat_ldlt_f32_batch", C.byref(_matf(src)), C.byref(_matf(l)), C.byref(_matf(d)),
+                C.c_void_p(pp.data_ptr()), src.shape[0], _stream_ptr(stream))
+
+
+def mat_solve_triangular_batch(t, a, dst, lower, status=None, stream=None):
+    """t[i] dst[i] = a[i] for device tensors t [batch, n, n], a and dst [batch, n, cols]
+    (arm_mat_solve_{lower,upper}_triangular_f32_batch); dst may be a.  Returns the status tensor as
+    mat_inverse_batch does."""
+    status, ps = _solve_status(t, status)
+    _solve_call(f"arm_mat_solve_{'lower' if lower else 'upper'}_triangular_f32_batch", C.byref(_matf(t)),
+                C.byref(_matf(a)), C.byref(_matf(dst)), t.shape[0], ps, _stream_ptr(stream))
+    return None if status is False else status
 
 
 def mat_mult_batch(a, b, c, stream=None, fast=False):

@@ -346,6 +346,22 @@ for _t, _inst in CMPLX_MAT_INST.items():
     CMPLX_MAT[f"arm_mat_cmplx_mult_{_t}_batch"] = (C.c_int, [P(_inst)] * 3 + [C.c_uint32, C.c_void_p])
     CMPLX_MAT[f"arm_mat_cmplx_mult_{_t}_batch_multi"] = (C.c_int, [P(_inst)] * 3 + [C.c_uint32] + [C.c_void_p] * 5)
 
+# Inverse, Cholesky, LDLT and triangular solves: the drop-ins and the batched forms (d_status / d_pp are device
+# pointers).  The product only, as CMPLX_MAT (tests/golden/mat_solve.npz holds the reference's outputs).
+_MF = P(arm_matrix_instance_f32)
+MAT_SOLVE = {
+    "arm_mat_inverse_f32": (C.c_int, [_MF, _MF]),
+    "arm_mat_cholesky_f32": (C.c_int, [_MF, _MF]),
+    "arm_mat_ldlt_f32": (C.c_int, [_MF, _MF, _MF, C.c_void_p]),
+    "arm_mat_solve_lower_triangular_f32": (C.c_int, [_MF, _MF, _MF]),
+    "arm_mat_solve_upper_triangular_f32": (C.c_int, [_MF, _MF, _MF]),
+    "arm_mat_inverse_f32_batch": (C.c_int, [_MF, _MF, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "arm_mat_cholesky_f32_batch": (C.c_int, [_MF, _MF, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "arm_mat_ldlt_f32_batch": (C.c_int, [_MF, _MF, _MF, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "arm_mat_solve_lower_triangular_f32_batch": (C.c_int, [_MF, _MF, _MF, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "arm_mat_solve_upper_triangular_f32_batch": (C.c_int, [_MF, _MF, _MF, C.c_uint32, C.c_void_p, C.c_void_p]),
+}
+
 # per-length MFCC init functions (the product and the reference build; the oracle has the
 # generic init only)
 MFCC_LEN = {f"arm_mfcc_init_{n}_f32": (C.c_int, [P(arm_mfcc_instance_f32), C.c_uint32, C.c_uint32, C.c_void_p,

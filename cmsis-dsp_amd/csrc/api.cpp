@@ -1315,6 +1315,81 @@ arm_status mfcc_batch(const Inst* S, T* d_src, T* d_dst, T* d_tmp, uint32_t batc
 }
 }  // namespace
 
+// ---- inverse, Cholesky, LDLT, triangular solves (f32) ---------------------------------
+// matrix_functions.h:659-777; kernels and the reference bodies they restate: mat_solve.hip.  The shape rules
+// are those the reference states under ARM_MATH_MATRIX_CHECK, applied always (as mat_shapes_ok is), plus
+// a / dst agreement in the solves.
+namespace {
+using MatF = arm_matrix_instance_f32;
+
+// One operand of a synchronous drop-in call: host words are staged into device scratch (in) and copied
+// back after the launch (out); a device pointer is used in place.
+struct SolveBuf {
+  void* p;
+  size_t bytes;
+  bool in, out;
+  void* d = nullptr;
+  bool dev = false;
+};
+
+// launch(st, d_status) -> hipError_t runs one item on the staged operands; returns the item's status.
+template <typename Launch>
+arm_status mat_solve_sync(SolveBuf* bufs, int nb, const char* what, Launch&& launch) {
+  hipStream_t st = sync_stream();
+  int32_t* d_status = (int32_t*)scratch(16, nb);
+  for (int i = 0; i < nb; ++i) {
+    SolveBuf& b = bufs[i];
+    b.dev = is_device_ptr(b.p);
+    b.d = b.dev ? b.p : scratch(b.bytes + 16, i);
+    for (int j = 0; j < i; ++j)          // exact alias (cholesky in place, solve into a): one staged copy
+      if (!b.dev && bufs[j].p == b.p) b.d = bufs[j].d;
+    if (!b.d) d_status = nullptr;
+  }
+  if (!d_status) { set_error(hipErrorOutOfMemory, what); return ARM_MATH_ARGUMENT_ERROR; }
+  HostIO io(st);
+  int32_t status = ARM_MATH_SUCCESS;
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < nb && e == hipSuccess; ++i)
+    if (!bufs[i].dev && bufs[i].in) e = io.in(bufs[i].d, bufs[i].p, bufs[i].bytes);
+  if (e == hipSuccess) e = launch(st, d_status);
+  for (int i = 0; i < nb && e == hipSuccess; ++i)
+    if (!bufs[i].dev && bufs[i].out) e = io.out(bufs[i].p, bufs[i].d, bufs[i].bytes);
+  if (e == hipSuccess) e = io.out(&status, d_status, sizeof(status));
+  if (e == hipSuccess) e = io.finish();
+  if (e != hipSuccess) return batch_status(e, what);
+  return (arm_status)status;
+}
+
+bool square(const MatF* m) { return m->numRows == m->numCols; }
+
+arm_status solve_tri_sync(bool lower, const MatF* t, const MatF* a, MatF* dst, const char* what) {
+  if (!t || !a || !dst || !t->pData || !a->pData || !dst->pData) return ARM_MATH_ARGUMENT_ERROR;
+  if (!square(t) || t->numRows != a->numRows || a->numRows != dst->numRows || a->numCols != dst->numCols)
+    return ARM_MATH_SIZE_MISMATCH;
+  const int n = t->numRows, cols = a->numCols;
+  if (n == 0 || cols == 0) return ARM_MATH_SUCCESS;
+  // dst is staged in as well: a failing solve leaves most of its words alone
+  SolveBuf b[3] = {{t->pData, sizeof(float) * n * n, true, false},
+                   {a->pData, sizeof(float) * n * cols, true, false},
+                   {dst->pData, sizeof(float) * n * cols, true, true}};
+  return mat_solve_sync(b, 3, what, [&](hipStream_t st, int32_t* ds) {
+    return mat_solve_tri_f32_launch(lower, n, cols, (const float*)b[0].d, (const float*)b[1].d, (float*)b[2].d, 1, ds,
+                                    st);
+  });
+}
+
+arm_status solve_tri_batch(bool lower, const MatF* t, const MatF* a, MatF* dst, uint32_t batch, int32_t* d_status,
+                           void* stream, const char* what) {
+  if (!t || !a || !dst) return ARM_MATH_ARGUMENT_ERROR;
+  if (!square(t) || t->numRows != a->numRows || a->numRows != dst->numRows || a->numCols != dst->numCols)
+    return ARM_MATH_SIZE_MISMATCH;
+  if (batch == 0 || t->numRows == 0 || a->numCols == 0) return ARM_MATH_SUCCESS;
+  if (!t->pData || !a->pData || !dst->pData) return ARM_MATH_ARGUMENT_ERROR;
+  return batch_status(mat_solve_tri_f32_launch(lower, t->numRows, a->numCols, t->pData, a->pData, dst->pData, batch,
+                                               d_status, (hipStream_t)stream), what);
+}
+}  // namespace
+
 extern "C" {
 
 #ifndef MI355X_BUILD_DEFS
@@ -1647,6 +1722,101 @@ MI355X_CMAT(f32, arm_matrix_instance_f32, float32_t, float)
 MI355X_CMAT(q31, arm_matrix_instance_q31, q31_t, int32_t)
 MI355X_CMAT(q15, arm_matrix_instance_q15, q15_t, int16_t)
 #undef MI355X_CMAT
+
+// ---- inverse, Cholesky, LDLT, triangular solves (f32); mat_solve_sync and its kin precede the C block ----
+arm_status arm_mat_inverse_f32(const arm_matrix_instance_f32* pSrc, arm_matrix_instance_f32* pDst) {
+  if (!pSrc || !pDst || !pSrc->pData || !pDst->pData) return ARM_MATH_ARGUMENT_ERROR;
+  if (!square(pSrc) || !square(pDst) || pSrc->numRows != pDst->numRows) return ARM_MATH_SIZE_MISMATCH;
+  const int n = pSrc->numRows;
+  if (n == 0) return ARM_MATH_SUCCESS;
+  // src is written back: the reference destroys it, and its final words are part of the contract
+  SolveBuf b[2] = {{pSrc->pData, sizeof(float) * n * n, true, true}, {pDst->pData, sizeof(float) * n * n, false, true}};
+  return mat_solve_sync(b, 2, "arm_mat_inverse_f32", [&](hipStream_t st, int32_t* ds) {
+    return mat_inverse_f32_launch(n, (float*)b[0].d, (float*)b[1].d, 1, ds, st);
+  });
+}
+
+arm_status arm_mat_cholesky_f32(const arm_matrix_instance_f32* pSrc, arm_matrix_instance_f32* pDst) {
+  if (!pSrc || !pDst || !pSrc->pData || !pDst->pData) return ARM_MATH_ARGUMENT_ERROR;
+  if (!square(pSrc) || !square(pDst) || pSrc->numRows != pDst->numRows) return ARM_MATH_SIZE_MISMATCH;
+  const int n = pSrc->numRows;
+  if (n == 0) return ARM_MATH_SUCCESS;
+  // dst is staged in as well: its strict upper triangle, and the columns past a failure, are never written
+  SolveBuf b[2] = {{pSrc->pData, sizeof(float) * n * n, true, false}, {pDst->pData, sizeof(float) * n * n, true, true}};
+  return mat_solve_sync(b, 2, "arm_mat_cholesky_f32", [&](hipStream_t st, int32_t* ds) {
+    return mat_cholesky_f32_launch(n, (const float*)b[0].d, (float*)b[1].d, 1, ds, st);
+  });
+}
+
+arm_status arm_mat_ldlt_f32(const arm_matrix_instance_f32* pSrc, arm_matrix_instance_f32* pl,
+                            arm_matrix_instance_f32* pd, uint16_t* pp) {
+  if (!pSrc || !pl || !pd || !pp || !pSrc->pData || !pl->pData || !pd->pData) return ARM_MATH_ARGUMENT_ERROR;
+  if (!square(pSrc) || !square(pl) || !square(pd) || pl->numRows != pd->numRows || pSrc->numRows != pl->numRows)
+    return ARM_MATH_SIZE_MISMATCH;
+  const int n = pSrc->numRows;
+  if (n == 0) return ARM_MATH_SUCCESS;
+  SolveBuf b[4] = {{pSrc->pData, sizeof(float) * n * n, true, false},
+                   {pl->pData, sizeof(float) * n * n, false, true},
+                   {pd->pData, sizeof(float) * n * n, false, true},
+                   {pp, sizeof(uint16_t) * n, false, true}};
+  return mat_solve_sync(b, 4, "arm_mat_ldlt_f32", [&](hipStream_t st, int32_t* ds) {
+    hipError_t e = hipMemsetAsync(ds, 0, sizeof(int32_t), st);       // the function cannot fail
+    if (e == hipSuccess)
+      e = mat_ldlt_f32_launch(n, (const float*)b[0].d, (float*)b[1].d, (float*)b[2].d, (uint16_t*)b[3].d, 1, st);
+    return e;
+  });
+}
+
+arm_status arm_mat_solve_lower_triangular_f32(const arm_matrix_instance_f32* lt, const arm_matrix_instance_f32* a,
+                                              arm_matrix_instance_f32* dst) {
+  return solve_tri_sync(true, lt, a, dst, "arm_mat_solve_lower_triangular_f32");
+}
+arm_status arm_mat_solve_upper_triangular_f32(const arm_matrix_instance_f32* ut, const arm_matrix_instance_f32* a,
+                                              arm_matrix_instance_f32* dst) {
+  return solve_tri_sync(false, ut, a, dst, "arm_mat_solve_upper_triangular_f32");
+}
+
+arm_status arm_mat_inverse_f32_batch(const arm_matrix_instance_f32* pSrc, arm_matrix_instance_f32* pDst,
+                                     uint32_t batch, int32_t* d_status, void* stream) {
+  if (!pSrc || !pDst) return ARM_MATH_ARGUMENT_ERROR;
+  if (!square(pSrc) || !square(pDst) || pSrc->numRows != pDst->numRows) return ARM_MATH_SIZE_MISMATCH;
+  if (batch == 0 || pSrc->numRows == 0) return ARM_MATH_SUCCESS;
+  if (!pSrc->pData || !pDst->pData) return ARM_MATH_ARGUMENT_ERROR;
+  return batch_status(mat_inverse_f32_launch(pSrc->numRows, pSrc->pData, pDst->pData, batch, d_status,
+                                             (hipStream_t)stream), "arm_mat_inverse_f32_batch");
+}
+
+arm_status arm_mat_cholesky_f32_batch(const arm_matrix_instance_f32* pSrc, arm_matrix_instance_f32* pDst,
+                                      uint32_t batch, int32_t* d_status, void* stream) {
+  if (!pSrc || !pDst) return ARM_MATH_ARGUMENT_ERROR;
+  if (!square(pSrc) || !square(pDst) || pSrc->numRows != pDst->numRows) return ARM_MATH_SIZE_MISMATCH;
+  if (batch == 0 || pSrc->numRows == 0) return ARM_MATH_SUCCESS;
+  if (!pSrc->pData || !pDst->pData) return ARM_MATH_ARGUMENT_ERROR;
+  return batch_status(mat_cholesky_f32_launch(pSrc->numRows, pSrc->pData, pDst->pData, batch, d_status,
+                                              (hipStream_t)stream), "arm_mat_cholesky_f32_batch");
+}
+
+arm_status arm_mat_ldlt_f32_batch(const arm_matrix_instance_f32* pSrc, arm_matrix_instance_f32* pl,
+                                  arm_matrix_instance_f32* pd, uint16_t* d_pp, uint32_t batch, void* stream) {
+  if (!pSrc || !pl || !pd) return ARM_MATH_ARGUMENT_ERROR;
+  if (!square(pSrc) || !square(pl) || !square(pd) || pl->numRows != pd->numRows || pSrc->numRows != pl->numRows)
+    return ARM_MATH_SIZE_MISMATCH;
+  if (batch == 0 || pSrc->numRows == 0) return ARM_MATH_SUCCESS;
+  if (!pSrc->pData || !pl->pData || !pd->pData || !d_pp) return ARM_MATH_ARGUMENT_ERROR;
+  return batch_status(mat_ldlt_f32_launch(pSrc->numRows, pSrc->pData, pl->pData, pd->pData, d_pp, batch,
+                                          (hipStream_t)stream), "arm_mat_ldlt_f32_batch");
+}
+
+arm_status arm_mat_solve_lower_triangular_f32_batch(const arm_matrix_instance_f32* lt,
+                                                    const arm_matrix_instance_f32* a, arm_matrix_instance_f32* dst,
+                                                    uint32_t batch, int32_t* d_status, void* stream) {
+  return solve_tri_batch(true, lt, a, dst, batch, d_status, stream, "arm_mat_solve_lower_triangular_f32_batch");
+}
+arm_status arm_mat_solve_upper_triangular_f32_batch(const arm_matrix_instance_f32* ut,
+                                                    const arm_matrix_instance_f32* a, arm_matrix_instance_f32* dst,
+                                                    uint32_t batch, int32_t* d_status, void* stream) {
+  return solve_tri_batch(false, ut, a, dst, batch, d_status, stream, "arm_mat_solve_upper_triangular_f32_batch");
+}
 
 // ---- convolution ------------------------------------------------------------------
 #define MI355X_CONV_FULL(NAME, T, CT, OP, VAR)                                                                  \

@@ -259,4 +259,20 @@ hipError_t mat_cmplx_mult_q31_launch(int m, int k, int n, const int32_t* a, cons
 // arm_mat_cmplx_mult_q15 (arm_mat_cmplx_mult_q15.c:433-468).
 hipError_t mat_cmplx_trans_q15_launch(int k, int n, const int16_t* b, int16_t* bt, hipStream_t st);
 
+// Inverse, Cholesky, LDLT and triangular solves over `batch` contiguous row-major n x n items (solves: t n x n,
+// a and x n x cols), bit-exact with the reference's scalar branches, failures included (mat_solve.hip).
+// status (may be null): one int32 per item, 0 / ARM_MATH_SINGULAR / ARM_MATH_DECOMPOSITION_FAILURE.  Any
+// n >= 1: an item lives in LDS while a workgroup's share fits kMatSolveLds (inverse, 2 n^2 words: n <= 143;
+// Cholesky and LDLT, n (n | 1) words: n <= 201), past that one workgroup works on it in global memory; the
+// solves read t and a from global memory and keep x in LDS as well up to n = 64.
+// The inverse destroys src as the reference does; cholesky's dst may be src, a solve's x may be a.
+constexpr size_t kMatSolveLds = 160 * 1024;
+hipError_t mat_inverse_f32_launch(int n, float* src, float* dst, uint32_t batch, int32_t* status, hipStream_t st);
+hipError_t mat_cholesky_f32_launch(int n, const float* src, float* dst, uint32_t batch, int32_t* status,
+                                   hipStream_t st);
+hipError_t mat_ldlt_f32_launch(int n, const float* src, float* pl, float* pd, uint16_t* pp, uint32_t batch,
+                               hipStream_t st);
+hipError_t mat_solve_tri_f32_launch(bool lower, int n, int cols, const float* t, const float* a, float* x,
+                                    uint32_t batch, int32_t* status, hipStream_t st);
+
 }  // namespace mi355x

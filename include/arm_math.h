@@ -952,6 +952,32 @@ arm_status arm_mat_cmplx_mult_q15(const arm_matrix_instance_q15 *pSrcA, const ar
 arm_status arm_mat_cmplx_mult_q31(const arm_matrix_instance_q31 *pSrcA, const arm_matrix_instance_q31 *pSrcB,
                                   arm_matrix_instance_q31 *pDst);
 
+/* Inverse, Cholesky, LDLT and triangular solves (matrix_functions.h:659-777, groups MatrixInv and
+ * MatrixChol), bit-exact with the reference's scalar branches: the status and the words an early return
+ * leaves included.  Host or device pData (and pp), synchronous.
+ *   arm_mat_inverse_f32   Gauss-Jordan with the reference's pivot rule.  pSrc is destroyed as there (its final
+ *                         words are written back); ARM_MATH_SINGULAR on a zero pivot, with both matrices as
+ *                         they stand at that moment.
+ *   arm_mat_cholesky_f32  writes the lower triangle of pDst only; ARM_MATH_DECOMPOSITION_FAILURE at the first
+ *                         diagonal <= 0 (that column unscaled, later columns untouched).  pDst->pData may be
+ *                         pSrc->pData.
+ *   arm_mat_ldlt_f32      P A P^T = L D L^T as the reference computes it (pivot rule, 1.0e-8f rank cut and
+ *                         its diag = k - 1 included); always ARM_MATH_SUCCESS.
+ *   arm_mat_solve_{lower,upper}_triangular_f32   dst (n x cols) from lt / ut (n x n) and a (n x cols);
+ *                         ARM_MATH_SINGULAR at a zero diagonal (then only column 0's earlier rows are
+ *                         written).  dst->pData may be a->pData.
+ * ARM_MATH_SIZE_MISMATCH on the shapes the reference rejects under ARM_MATH_MATRIX_CHECK (always on here) and
+ * when a and dst differ; ARM_MATH_ARGUMENT_ERROR on a null pointer.  Any overlap but the two exact aliases
+ * named above is undefined. */
+arm_status arm_mat_inverse_f32(const arm_matrix_instance_f32 *pSrc, arm_matrix_instance_f32 *pDst);
+arm_status arm_mat_cholesky_f32(const arm_matrix_instance_f32 *pSrc, arm_matrix_instance_f32 *pDst);
+arm_status arm_mat_ldlt_f32(const arm_matrix_instance_f32 *pSrc, arm_matrix_instance_f32 *pl,
+                            arm_matrix_instance_f32 *pd, uint16_t *pp);
+arm_status arm_mat_solve_lower_triangular_f32(const arm_matrix_instance_f32 *lt, const arm_matrix_instance_f32 *a,
+                                              arm_matrix_instance_f32 *dst);
+arm_status arm_mat_solve_upper_triangular_f32(const arm_matrix_instance_f32 *ut, const arm_matrix_instance_f32 *a,
+                                              arm_matrix_instance_f32 *dst);
+
 #ifdef __cplusplus
 }
 #endif

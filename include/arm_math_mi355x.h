@@ -306,6 +306,27 @@ arm_status arm_mat_cmplx_mult_q31_batch(const arm_matrix_instance_q31 *pSrcA, co
                                         arm_matrix_instance_q31 *pDst, uint32_t batch, void *stream);
 arm_status arm_mat_cmplx_mult_q15_batch(const arm_matrix_instance_q15 *pSrcA, const arm_matrix_instance_q15 *pSrcB,
                                         arm_matrix_instance_q15 *pDst, uint32_t batch, void *stream);
+/* Inverse, Cholesky, LDLT and triangular solves of `batch` independent items (per item: arm_mat_inverse_f32,
+ * arm_mat_cholesky_f32, arm_mat_ldlt_f32, arm_mat_solve_{lower,upper}_triangular_f32, bit-exact).  pData
+ * points at the first of `batch` contiguous row-major items of the instance's shape; each item of a solve has
+ * its own triangular matrix and right-hand sides; d_pp holds batch rows of n words.  d_status (device, may
+ * be NULL) receives one int32 per item: ARM_MATH_SUCCESS, ARM_MATH_SINGULAR or
+ * ARM_MATH_DECOMPOSITION_FAILURE; a failing item leaves the words the reference leaves and does not disturb
+ * its neighbours.  The return value reports shape, argument and launch errors only.  The inverse destroys
+ * pSrc's items; Cholesky's pDst->pData may be pSrc->pData and a solve's dst->pData may be a->pData.
+ * batch == 0 and n == 0 are successful no-ops.  There are no _batch_multi forms. */
+arm_status arm_mat_inverse_f32_batch(const arm_matrix_instance_f32 *pSrc, arm_matrix_instance_f32 *pDst,
+                                     uint32_t batch, int32_t *d_status, void *stream);
+arm_status arm_mat_cholesky_f32_batch(const arm_matrix_instance_f32 *pSrc, arm_matrix_instance_f32 *pDst,
+                                      uint32_t batch, int32_t *d_status, void *stream);
+arm_status arm_mat_solve_lower_triangular_f32_batch(const arm_matrix_instance_f32 *lt,
+                                                    const arm_matrix_instance_f32 *a, arm_matrix_instance_f32 *dst,
+                                                    uint32_t batch, int32_t *d_status, void *stream);
+arm_status arm_mat_solve_upper_triangular_f32_batch(const arm_matrix_instance_f32 *ut,
+                                                    const arm_matrix_instance_f32 *a, arm_matrix_instance_f32 *dst,
+                                                    uint32_t batch, int32_t *d_status, void *stream);
+arm_status arm_mat_ldlt_f32_batch(const arm_matrix_instance_f32 *pSrc, arm_matrix_instance_f32 *pl,
+                                  arm_matrix_instance_f32 *pd, uint16_t *d_pp, uint32_t batch, void *stream);
 
 /* Multi-GPU complex FFT (SURVEY §8b "a multi-GPU entry point"; per item: arm_cfft_f32 /
  * _q31 / _q15, transform_functions.h:456-460).  Shard s of `nshards` is batch[s] contiguous

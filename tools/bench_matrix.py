@@ -8,7 +8,18 @@ REPEATS times each over a window of at least a second, so the repeat spread of e
 ratio.  Rows 0..15 of item 0 are checked bit for bit against the CPU checker first (q15 / q31:
 tests/cmplx_mat_ref.py; f32: the stated fmaf chain, oracle.mat_mult_fmaf on the embedded operands).
 Operations are counted as 8 M N K per complex product (4 multiplies and 4 adds per complex MAC).
-Usage: python tools/bench_matrix.py [f32|q31|q15 ...]  -> one JSON line per workload."""
+Usage: python tools/bench_matrix.py [f32|q31|q15 ...]  -> one JSON line per workload.
+
+Inverse, Cholesky, LDLT and triangular solves (arm_mat_{inverse,cholesky,ldlt,solve_*_triangular}_f32_batch):
+    python tools/bench_matrix.py [inverse|cholesky|ldlt|solve_lower|solve_upper ...] [--gib G]
+n in 4, 8, 16, 32, 64, the batch sized so that the algorithmic traffic is about G GiB (default 1): words read
+and written once, inverse n^2 + 2 n^2, Cholesky n^2 + n (n + 1) / 2, LDLT n^2 + 2 n^2 (+ n / 2 for pp), solves
+(4 right-hand sides) n^2 + 4 n + 4 n.  Each line reports matrices/s, flop/s (inverse 3 n^3: 2 n^3 on dst and n^3
+on the shrinking src; Cholesky n^3 / 3; LDLT n^3, three operations per word of the trailing square; solves
+n^2 cols) and the fraction of 8 TB/s the algorithmic bytes reach.  Yardstick, on the same tensors in the same
+process: torch.linalg.inv, torch.linalg.cholesky, torch.linalg.solve_triangular (LDLT has none that pivots on
+the diagonal and is listed alone).  The first and last item are checked bit for bit against
+tests/mat_solve_ref.py first."""
 import json
 import os
 import sys
@@ -115,8 +126,149 @@ def run(kind):
     return ok
 
 
+HBM_TBPS = 8.0
+SOLVE_SIZES = (4, 8, 16, 32, 64)
+SOLVE_COLS = 4
+SOLVE_WINDOW_MS = 300.0
+
+
+def solve_counts(func, n):
+    """(words moved, flops) per item."""
+    if func == "inverse":
+        return 3 * n * n, 3.0 * n ** 3
+    if func == "cholesky":
+        return n * n + n * (n + 1) // 2, n ** 3 / 3.0
+    if func == "ldlt":
+        return 3 * n * n + (n + 1) // 2, 1.0 * n ** 3
+    return n * n + 2 * n * SOLVE_COLS, 1.0 * n * n * SOLVE_COLS
+
+
+def run_solve(func, n, gib):
+    import mat_solve_ref as mr
+    words, flops = solve_counts(func, n)
+    batch = max(1, int(gib * 2 ** 30 / (4 * words)))
+    gen = torch.Generator(device="cuda").manual_seed(n)
+    rnd = lambda *shape: torch.rand(shape, generator=gen, device="cuda", dtype=torch.float32) * 2 - 1   # noqa: E731
+    status = torch.zeros(batch, dtype=torch.int32, device="cuda")
+    if func == "inverse":
+        src = rnd(batch, n, n)
+        work, dst = torch.empty_like(src), torch.empty_like(src)
+
+        def ours():                          # the call destroys its source: the copy is part of neither count
+            dsp.mat_inverse_batch(work, dst, status=status)
+
+        def prep():
+            work.copy_(src)
+
+        def yard():
+            return torch.linalg.inv(src)
+        operands, outs = {"src": src}, lambda i: {"dst": dst[i], "src_after": work[i]}   # noqa: E731
+    elif func in ("cholesky", "ldlt"):
+        b = rnd(batch, n, n + 3)
+        src = torch.bmm(b, b.transpose(1, 2)).contiguous()
+        del b
+        dst = torch.zeros_like(src)
+        if func == "cholesky":
+            def ours():
+                dsp.mat_cholesky_batch(src, dst, status=status)
+
+            def yard():
+                return torch.linalg.cholesky(src)
+            outs = lambda i: {"dst": dst[i]}                                             # noqa: E731
+        else:
+            dd, pp = torch.zeros_like(src), torch.zeros((batch, n), dtype=torch.int16, device="cuda")
+
+            def ours():
+                dsp.mat_ldlt_batch(src, dst, dd, pp)
+            yard = None
+            outs = lambda i: {"l": dst[i], "d": dd[i], "pp": pp[i]}                      # noqa: E731
+        prep, operands = None, {"src": src}
+    else:
+        lower = func == "solve_lower"
+        t = rnd(batch, n, n)
+        t = (torch.tril(t, -1) if lower else torch.triu(t, 1)) + torch.diag_embed(1 + rnd(batch, n).abs())
+        a, dst = rnd(batch, n, SOLVE_COLS), torch.zeros((batch, n, SOLVE_COLS), device="cuda")
+
+        def ours():
+            dsp.mat_solve_triangular_batch(t, a, dst, lower=lower, status=status)
+
+        def yard():
+            return torch.linalg.solve_triangular(t, a, upper=not lower)
+        prep, operands, outs = None, {"t": t, "a": a}, lambda i: {"dst": dst[i]}         # noqa: E731
+
+    if prep:
+        prep()
+    ours()
+    torch.cuda.synchronize()
+    ok = not bool(status.any())
+    for i in (0, batch - 1):
+        want = mr.run(func, {k: v[i].cpu().numpy() for k, v in operands.items()})
+        for k, v in outs(i).items():
+            got, exp = v.cpu().numpy(), want[k]
+            if func == "cholesky":           # the strict upper triangle is not written
+                got, exp = np.tril(got), np.tril(exp)
+            ok = ok and mr.same_words(got.view(np.uint16) if k == "pp" else got, exp)
+
+    def timed_ours(steps):
+        # the inverse restores its source before every call, outside the timed interval
+        if not prep:
+            return timed(ours, steps)
+        st = torch.cuda.current_stream()
+        total = 0.0
+        for _ in range(steps):
+            prep()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            ours()
+            e1.record(st)
+            e1.synchronize()
+            total += e0.elapsed_time(e1)
+        return total / steps
+
+    settle(ours if not prep else lambda: (prep(), ours()))
+    steps = max(3, min(200, int(np.ceil(SOLVE_WINDOW_MS / max(timed_ours(3), 1e-3)))))
+    ms = [timed_ours(steps) for _ in range(REPEATS)]
+    best = min(ms)
+    line = {"workload": f"mat_{func}_f32", "n": n, "batch": batch, "bitexact_first_last": ok,
+            "value": round(batch / (best * 1e-3) * 1e-6, 3), "unit": "M matrices/s",
+            "gflops": round(flops * batch / (best * 1e-3) * 1e-9, 1),
+            "roofline": {"bound": "hbm", "bytes": 4 * words * batch, "peak_TBps": HBM_TBPS,
+                         "frac": round(4.0 * words * batch / (best * 1e-3) / (HBM_TBPS * 1e12), 4)},
+            "ms": [round(x, 4) for x in ms], "spread": round((max(ms) - best) / best, 4), "steps": steps,
+            "version": dsp.version()}
+    if func in ("solve_lower", "solve_upper"):
+        line["cols"] = SOLVE_COLS
+    if yard:
+        try:
+            ysteps = max(1, min(50, int(np.ceil(SOLVE_WINDOW_MS / max(timed(yard, 1, warmup=1), 1e-3)))))
+            yms = [timed(yard, ysteps, warmup=0) for _ in range(REPEATS)]
+            name = {"inverse": "torch.linalg.inv", "cholesky": "torch.linalg.cholesky"}.get(
+                func, "torch.linalg.solve_triangular")
+            line["yardstick"] = {"workload": name, "ms": [round(x, 4) for x in yms],
+                                 "value": round(batch / (min(yms) * 1e-3) * 1e-6, 3), "steps": ysteps}
+            line["ratio_to_yardstick"] = round(min(yms) / best, 3)
+        except RuntimeError as e:          # e.g. out of memory in the library's workspace
+            line["yardstick"] = {"error": str(e).splitlines()[0][:200]}
+    print(json.dumps(line), flush=True)
+    return ok
+
+
 def main():
-    kinds = sys.argv[1:] or ["f32", "q31", "q15"]
+    args = sys.argv[1:]
+    gib = 1.0
+    if "--gib" in args:
+        i = args.index("--gib")
+        gib = float(args[i + 1])
+        del args[i:i + 2]
+    solves = [k for k in args if k in ("inverse", "cholesky", "ldlt", "solve_lower", "solve_upper")]
+    if solves:
+        bad = [f"{f} n={n}" for f in solves for n in SOLVE_SIZES if not run_solve(f, n, gib)]
+        if bad:
+            sys.exit(f"not bit-exact: {bad}")
+        args = [k for k in args if k not in solves]
+        if not args:
+            return
+    kinds = args or ["f32", "q31", "q15"]
     bad = [k for k in kinds if not run(k)]
     if bad:
         sys.exit(f"not bit-exact: {bad}")
