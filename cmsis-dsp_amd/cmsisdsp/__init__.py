@@ -542,6 +542,76 @@ def arm_mat_solve_upper_triangular_f32(pSrcA, pSrcB):
     return _amd.arm_mat_solve_upper_triangular(_arr(pSrcA, _np.float32), _arr(pSrcB, _np.float32))
 
 
+def _mat_basic(name, kind, doc):
+    """One of the 20 element-wise, transpose and matrix-vector bindings (cmsisdsp_matrix.c)."""
+    op = name[len("arm_mat_"):-len(kind) - 1]
+    dt = _DT[kind]
+    if op in ("add", "sub"):
+        def run(pSrcA, pSrcB):
+            return getattr(_amd, f"arm_mat_{op}")(kind, _arr(pSrcA, dt), _arr(pSrcB, dt))
+    elif op == "scale" and kind == "f32":
+        def run(pSrc, scale):
+            return _amd.arm_mat_scale(kind, _arr(pSrc, dt), scale)
+    elif op == "scale":
+        def run(pSrc, scaleFract, shift):
+            return _amd.arm_mat_scale(kind, _arr(pSrc, dt), scaleFract, shift)
+    elif op == "vec_mult":
+        def run(pSrcA, pSrcB):
+            return _amd.arm_mat_vec_mult(kind, _arr(pSrcA, dt), _arr(pSrcB, dt))
+    else:
+        def run(pSrc):
+            return getattr(_amd, f"arm_mat_{op}")(kind, _arr(pSrc, dt))
+    run.__name__ = name
+    run.__doc__ = doc
+    return run
+
+
+arm_mat_add_f32 = _mat_basic("arm_mat_add_f32", "f32", """cmsisdsp_matrix.c cmsis_arm_mat_add_f32 ("OO", :421-454):
+    (status, dst); dst is created [pSrcA rows, pSrcB cols] as there.""")
+arm_mat_add_q15 = _mat_basic("arm_mat_add_q15", "q15", """cmsis_arm_mat_add_q15 ("OO", :458-494): (status, dst), int16
+    words, saturating.""")
+arm_mat_add_q31 = _mat_basic("arm_mat_add_q31", "q31", """cmsis_arm_mat_add_q31 ("OO", :497-532): (status, dst), int32
+    words, saturating.""")
+arm_mat_sub_f32 = _mat_basic("arm_mat_sub_f32", "f32", """cmsis_arm_mat_sub_f32 ("OO", :1380-1413): (status, dst); dst is
+    created [pSrcA rows, pSrcB cols].""")
+arm_mat_sub_q15 = _mat_basic("arm_mat_sub_q15", "q15", """cmsis_arm_mat_sub_q15 ("OO", :1453-1487): (status, dst),
+    saturating.""")
+arm_mat_sub_q31 = _mat_basic("arm_mat_sub_q31", "q31", """cmsis_arm_mat_sub_q31 ("OO", :1490-1524): (status, dst),
+    saturating.""")
+arm_mat_scale_f32 = _mat_basic("arm_mat_scale_f32", "f32", """cmsis_arm_mat_scale_f32 ("Of", :1527-1556): (status, dst)
+    with dst = pSrc * scale, the shape of pSrc.""")
+arm_mat_scale_q15 = _mat_basic("arm_mat_scale_q15", "q15", """cmsis_arm_mat_scale_q15 ("Ohi", :1560-1590): (status, dst)
+    from scaleFract (a q15 word) and shift; a shift outside -16..15 gives ARM_MATH_ARGUMENT_ERROR and a zero
+    dst here (undefined in the reference).""")
+arm_mat_scale_q31 = _mat_basic("arm_mat_scale_q31", "q31", """cmsis_arm_mat_scale_q31 ("Oii", :1594-1624): (status, dst)
+    from scaleFract (a q31 word) and shift; a shift outside -1..30 gives ARM_MATH_ARGUMENT_ERROR and a zero dst
+    here (undefined in the reference).""")
+arm_mat_trans_f32 = _mat_basic("arm_mat_trans_f32", "f32", """cmsis_arm_mat_trans_f32 ("O", :782-810): (status, dst),
+    dst created [pSrc cols, pSrc rows].""")
+arm_mat_trans_q7 = _mat_basic("arm_mat_trans_q7", "q7", """cmsis_arm_mat_trans_q7 ("O", :844-872): (status, dst), int8
+    words.""")
+arm_mat_trans_q15 = _mat_basic("arm_mat_trans_q15", "q15", """cmsis_arm_mat_trans_q15 ("O", :875-904): (status, dst),
+    int16 words.""")
+arm_mat_trans_q31 = _mat_basic("arm_mat_trans_q31", "q31", """cmsis_arm_mat_trans_q31 ("O", :907-935): (status, dst),
+    int32 words.""")
+arm_mat_cmplx_trans_f32 = _mat_basic("arm_mat_cmplx_trans_f32", "f32", """cmsis_arm_mat_cmplx_trans_f32 ("O", :535-574):
+    a real array [R, 2C] of interleaved (re, im) words -> (status, dst [C, 2R]); the wrapper halves numCols
+    before the call, as here.""")
+arm_mat_cmplx_trans_q31 = _mat_basic("arm_mat_cmplx_trans_q31", "q31", """cmsis_arm_mat_cmplx_trans_q31 ("O", :577-616):
+    [R, 2C] int32 -> (status, dst [C, 2R]).""")
+arm_mat_cmplx_trans_q15 = _mat_basic("arm_mat_cmplx_trans_q15", "q15", """cmsis_arm_mat_cmplx_trans_q15 ("O", :619-658):
+    [R, 2C] int16 -> (status, dst [C, 2R]).""")
+arm_mat_vec_mult_f32 = _mat_basic("arm_mat_vec_mult_f32", "f32", """cmsis_arm_mat_vec_mult_f32 ("OO", :938-968): the
+    matrix and a vector of numCols words -> dst, a 1-D array of numRows words; no status (the C function
+    returns void).""")
+arm_mat_vec_mult_q15 = _mat_basic("arm_mat_vec_mult_q15", "q15", """cmsis_arm_mat_vec_mult_q15 ("OO", :1044-1074): -> dst,
+    numRows int16 words; keeps the reference's 16-bit row offset (INTEGRATION.md).""")
+arm_mat_vec_mult_q7 = _mat_basic("arm_mat_vec_mult_q7", "q7", """cmsis_arm_mat_vec_mult_q7 ("OO", :1077-1107): -> dst,
+    numRows int8 words.""")
+arm_mat_vec_mult_q31 = _mat_basic("arm_mat_vec_mult_q31", "q31", """cmsis_arm_mat_vec_mult_q31 ("OO", :1233-1263): -> dst,
+    numRows int32 words; keeps the reference's 16-bit row offset (INTEGRATION.md).""")
+
+
 def arm_mat_mult_fast_q31(pSrcA, pSrcB):
     """cmsisdsp_matrix.c cmsis_arm_mat_mult_fast_q31: (status, C)."""
     return _amd.arm_mat_mult_fixed("fast_q31", _arr(pSrcA, _np.int32), _arr(pSrcB, _np.int32))

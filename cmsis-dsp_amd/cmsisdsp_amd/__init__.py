@@ -52,6 +52,7 @@ def _load():
     _abi.bind(lib, _abi.ADAPTIVE)
     _abi.bind(lib, _abi.CMPLX_MAT)
     _abi.bind(lib, _abi.MAT_SOLVE)
+    _abi.bind(lib, _abi.MAT_BASIC)
     _abi.bind(lib, _abi.BATCHED)
     return lib
 
@@ -763,6 +764,135 @@ def mat_solve_triangular_batch(t, a, dst, lower, status=None, stream=None):
     _solve_call(f"arm_mat_solve_{'lower' if lower else 'upper'}_triangular_f32_batch", C.byref(_matf(t)),
                 C.byref(_matf(a)), C.byref(_matf(dst)), t.shape[0], ps, _stream_ptr(stream))
     return None if status is False else status
+
+
+_MAT_DT = {"f32": np.float32, "q31": np.int32, "q15": np.int16, "q7": np.int8}
+
+
+def _mat(kind, x, cmplx=False):
+    """arm_matrix_instance_<kind> over a 2-D numpy array or over the items of a [batch, r, c] tensor; cmplx: the
+    last axis holds interleaved (re, im) words and numCols counts pairs."""
+    p = x.ctypes.data if isinstance(x, np.ndarray) else x.data_ptr()
+    return _abi.MAT_INST[kind](x.shape[-2], x.shape[-1] // (2 if cmplx else 1), C.cast(p, _abi.MAT_PTR[kind]))
+
+
+def _mat_kind(t):
+    import torch
+    return {torch.float32: "f32", torch.int32: "q31", torch.int16: "q15", torch.int8: "q7"}[t.dtype]
+
+
+def _arm_mat_ew(op, kind, a, b):
+    a = np.ascontiguousarray(a, dtype=_MAT_DT[kind])
+    b = np.ascontiguousarray(b, dtype=_MAT_DT[kind])
+    d = np.zeros((a.shape[0], b.shape[1]), dtype=a.dtype)
+    st = getattr(lib, f"arm_mat_{op}_{kind}")(C.byref(_mat(kind, a)), C.byref(_mat(kind, b)), C.byref(_mat(kind, d)))
+    _check_void(f"arm_mat_{op}_{kind}")
+    return st, d
+
+
+def arm_mat_add(kind, a, b):
+    """(status, a + b) through arm_mat_add_f32 / _q31 / _q15 (kind "f32", "q31", "q15"; drop-in, numpy).  dst is
+    [a rows, b cols], as the reference binding sizes it."""
+    return _arm_mat_ew("add", kind, a, b)
+
+
+def arm_mat_sub(kind, a, b):
+    """(status, a - b) through arm_mat_sub_f32 / _q31 / _q15."""
+    return _arm_mat_ew("sub", kind, a, b)
+
+
+def arm_mat_scale(kind, a, scale, shift=0):
+    """(status, dst) through arm_mat_scale_f32 (scale a float) or _q31 / _q15 (scale the scaleFract word, shift
+    -1..30 / -16..15; outside it the status is ARM_MATH_ARGUMENT_ERROR and dst stays zero)."""
+    a = np.ascontiguousarray(a, dtype=_MAT_DT[kind])
+    d = np.zeros_like(a)
+    args = [float(scale)] if kind == "f32" else [int(scale), int(shift)]
+    st = getattr(lib, f"arm_mat_scale_{kind}")(C.byref(_mat(kind, a)), *args, C.byref(_mat(kind, d)))
+    _check_void(f"arm_mat_scale_{kind}")
+    return st, d
+
+
+def arm_mat_trans(kind, a):
+    """(status, a.T) through arm_mat_trans_f32 / _q31 / _q15 / _q7."""
+    a = np.ascontiguousarray(a, dtype=_MAT_DT[kind])
+    d = np.zeros(a.shape[::-1], dtype=a.dtype)
+    st = getattr(lib, f"arm_mat_trans_{kind}")(C.byref(_mat(kind, a)), C.byref(_mat(kind, d)))
+    _check_void(f"arm_mat_trans_{kind}")
+    return st, d
+
+
+def arm_mat_cmplx_trans(kind, a):
+    """(status, dst) through arm_mat_cmplx_trans_f32 / _q31 / _q15: a [R, 2C] holds interleaved (re, im) words,
+    dst is [C, 2R]; no conjugation."""
+    a = np.ascontiguousarray(a, dtype=_MAT_DT[kind])
+    d = np.zeros((a.shape[1] // 2, 2 * a.shape[0]), dtype=a.dtype)
+    st = getattr(lib, f"arm_mat_cmplx_trans_{kind}")(C.byref(_mat(kind, a, True)), C.byref(_mat(kind, d, True)))
+    _check_void(f"arm_mat_cmplx_trans_{kind}")
+    return st, d
+
+
+def arm_mat_vec_mult(kind, m, v):
+    """m [R, C] times v [C] -> [R] through arm_mat_vec_mult_f32 / _q31 / _q15 / _q7."""
+    m = np.ascontiguousarray(m, dtype=_MAT_DT[kind])
+    v = np.ascontiguousarray(v, dtype=_MAT_DT[kind])
+    if v.size < m.shape[1]:
+        raise ValueError(f"arm_mat_vec_mult_{kind}: the vector has {v.size} words, the matrix {m.shape[1]} columns")
+    d = np.zeros(m.shape[0], dtype=m.dtype)
+    getattr(lib, f"arm_mat_vec_mult_{kind}")(C.byref(_mat(kind, m)), v.ctypes.data, d.ctypes.data)
+    _check_void(f"arm_mat_vec_mult_{kind}")
+    return d
+
+
+def _mat_ew_batch(op, a, b, dst, stream):
+    kind = _mat_kind(a)
+    _solve_call(f"arm_mat_{op}_{kind}_batch", C.byref(_mat(kind, a)), C.byref(_mat(kind, b)), C.byref(_mat(kind, dst)),
+                a.shape[0], _stream_ptr(stream))
+
+
+def mat_add_batch(a, b, dst, stream=None):
+    """dst[i] = a[i] + b[i] for contiguous device tensors [batch, R, C] of float32 / int32 (q31) / int16 (q15)
+    (arm_mat_add_*_batch); dst may be a or b."""
+    _mat_ew_batch("add", a, b, dst, stream)
+
+
+def mat_sub_batch(a, b, dst, stream=None):
+    """dst[i] = a[i] - b[i] (arm_mat_sub_*_batch); dst may be a or b."""
+    _mat_ew_batch("sub", a, b, dst, stream)
+
+
+def mat_scale_batch(src, scale, dst, shift=0, stream=None):
+    """dst[i] = src[i] scaled by one scale (fixed point: scaleFract and shift) for the whole batch
+    (arm_mat_scale_*_batch); dst may be src."""
+    kind = _mat_kind(src)
+    args = [float(scale)] if kind == "f32" else [int(scale), int(shift)]
+    _solve_call(f"arm_mat_scale_{kind}_batch", C.byref(_mat(kind, src)), *args, C.byref(_mat(kind, dst)),
+                src.shape[0], _stream_ptr(stream))
+
+
+def mat_trans_batch(src, dst, stream=None):
+    """dst[i] [C, R] = the transpose of src[i] [R, C] (arm_mat_trans_*_batch; float32, int32, int16, int8)."""
+    kind = _mat_kind(src)
+    _solve_call(f"arm_mat_trans_{kind}_batch", C.byref(_mat(kind, src)), C.byref(_mat(kind, dst)), src.shape[0],
+                _stream_ptr(stream))
+
+
+def mat_cmplx_trans_batch(src, dst, stream=None):
+    """dst[i] [C, 2R] = the transpose of src[i] [R, 2C], interleaved (re, im) words
+    (arm_mat_cmplx_trans_*_batch; float32, int32, int16)."""
+    kind = _mat_kind(src)
+    _solve_call(f"arm_mat_cmplx_trans_{kind}_batch", C.byref(_mat(kind, src, True)), C.byref(_mat(kind, dst, True)),
+                src.shape[0], _stream_ptr(stream))
+
+
+def mat_vec_mult_batch(mat, vec, dst, stream=None, mat_stride=None):
+    """dst[i] [R] = mat_i [R, C] times vec[i] [C] for device tensors vec [batch, C], dst [batch, R]
+    (arm_mat_vec_mult_*_batch).  mat [R, C]: one matrix for every item (matStride 0); mat [batch, R, C]: one per
+    item.  mat_stride (elements) overrides the distance between the items' matrices (a padded layout)."""
+    kind = _mat_kind(mat)
+    if mat_stride is None:
+        mat_stride = 0 if mat.dim() == 2 else mat.shape[-2] * mat.shape[-1]
+    _solve_call(f"arm_mat_vec_mult_{kind}_batch", C.byref(_mat(kind, mat)), int(mat_stride),
+                C.c_void_p(vec.data_ptr()), C.c_void_p(dst.data_ptr()), vec.shape[0], _stream_ptr(stream))
 
 
 def mat_mult_batch(a, b, c, stream=None, fast=False):

@@ -362,6 +362,25 @@ MAT_SOLVE = {
     "arm_mat_solve_upper_triangular_f32_batch": (C.c_int, [_MF, _MF, _MF, C.c_uint32, C.c_void_p, C.c_void_p]),
 }
 
+# Element-wise add / sub / scale, the transposes and matrix x vector: 20 drop-ins and their _batch forms.  The
+# product only (tests/golden/mat_basic.npz holds the reference's outputs).
+MAT_INST = {"f32": arm_matrix_instance_f32, "q31": arm_matrix_instance_q31, "q15": arm_matrix_instance_q15,
+            "q7": arm_matrix_instance_q7}
+MAT_PTR = {"f32": c_f32p, "q31": c_i32p, "q15": c_i16p, "q7": c_i8p}
+MAT_SCALAR = {"f32": C.c_float, "q31": C.c_int32, "q15": C.c_int16}
+MAT_BASIC = {}
+for _t, _inst in MAT_INST.items():
+    _pm, _tail = P(_inst), [C.c_uint32, C.c_void_p]
+    if _t != "q7":
+        _sc = [_pm, MAT_SCALAR[_t]] + ([C.c_int32] if _t != "f32" else []) + [_pm]
+        for _n, _a in (("add", [_pm] * 3), ("sub", [_pm] * 3), ("scale", _sc), ("cmplx_trans", [_pm] * 2)):
+            MAT_BASIC[f"arm_mat_{_n}_{_t}"] = (C.c_int, _a)
+            MAT_BASIC[f"arm_mat_{_n}_{_t}_batch"] = (C.c_int, _a + _tail)
+    MAT_BASIC[f"arm_mat_trans_{_t}"] = (C.c_int, [_pm] * 2)
+    MAT_BASIC[f"arm_mat_trans_{_t}_batch"] = (C.c_int, [_pm] * 2 + _tail)
+    MAT_BASIC[f"arm_mat_vec_mult_{_t}"] = (None, [_pm, C.c_void_p, C.c_void_p])
+    MAT_BASIC[f"arm_mat_vec_mult_{_t}_batch"] = (C.c_int, [_pm, C.c_uint32, C.c_void_p, C.c_void_p] + _tail)
+
 # per-length MFCC init functions (the product and the reference build; the oracle has the
 # generic init only)
 MFCC_LEN = {f"arm_mfcc_init_{n}_f32": (C.c_int, [P(arm_mfcc_instance_f32), C.c_uint32, C.c_uint32, C.c_void_p,

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/arm_math.h"
@@ -1332,32 +1333,42 @@ struct SolveBuf {
   bool dev = false;
 };
 
-// launch(st, d_status) -> hipError_t runs one item on the staged operands; returns the item's status.
+// launch(st) -> hipError_t runs on the staged operands (bufs[i].d) between the copies in and out.
 template <typename Launch>
-arm_status mat_solve_sync(SolveBuf* bufs, int nb, const char* what, Launch&& launch) {
+arm_status mat_staged_sync(SolveBuf* bufs, int nb, const char* what, Launch&& launch) {
   hipStream_t st = sync_stream();
-  int32_t* d_status = (int32_t*)scratch(16, nb);
   for (int i = 0; i < nb; ++i) {
     SolveBuf& b = bufs[i];
     b.dev = is_device_ptr(b.p);
     b.d = b.dev ? b.p : scratch(b.bytes + 16, i);
-    for (int j = 0; j < i; ++j)          // exact alias (cholesky in place, solve into a): one staged copy
-      if (!b.dev && bufs[j].p == b.p) b.d = bufs[j].d;
-    if (!b.d) d_status = nullptr;
+    for (int j = 0; j < i; ++j)          // exact alias (add / sub / scale in place): one staged copy
+      if (!b.dev && bufs[j].p == b.p && bufs[j].bytes == b.bytes) b.d = bufs[j].d;
+    if (!b.d) { set_error(hipErrorOutOfMemory, what); return ARM_MATH_ARGUMENT_ERROR; }
   }
-  if (!d_status) { set_error(hipErrorOutOfMemory, what); return ARM_MATH_ARGUMENT_ERROR; }
   HostIO io(st);
-  int32_t status = ARM_MATH_SUCCESS;
   hipError_t e = hipSuccess;
   for (int i = 0; i < nb && e == hipSuccess; ++i)
     if (!bufs[i].dev && bufs[i].in) e = io.in(bufs[i].d, bufs[i].p, bufs[i].bytes);
-  if (e == hipSuccess) e = launch(st, d_status);
+  if (e == hipSuccess) e = launch(st);
   for (int i = 0; i < nb && e == hipSuccess; ++i)
     if (!bufs[i].dev && bufs[i].out) e = io.out(bufs[i].p, bufs[i].d, bufs[i].bytes);
-  if (e == hipSuccess) e = io.out(&status, d_status, sizeof(status));
   if (e == hipSuccess) e = io.finish();
-  if (e != hipSuccess) return batch_status(e, what);
-  return (arm_status)status;
+  return batch_status(e, what);
+}
+
+// launch(st, d_status) -> hipError_t runs one item on the staged operands; returns the item's status, which
+// is staged out like one more operand.
+template <typename Launch>
+arm_status mat_solve_sync(SolveBuf* bufs, int nb, const char* what, Launch&& launch) {
+  int32_t status = ARM_MATH_SUCCESS;
+  SolveBuf all[5];
+  for (int i = 0; i < nb; ++i) all[i] = bufs[i];
+  all[nb] = {&status, sizeof(status), false, true};
+  const arm_status r = mat_staged_sync(all, nb + 1, what, [&](hipStream_t st) {
+    for (int i = 0; i < nb; ++i) bufs[i] = all[i];      // the callers' launches read bufs[i].d
+    return launch(st, (int32_t*)all[nb].d);
+  });
+  return r != ARM_MATH_SUCCESS ? r : (arm_status)status;
 }
 
 bool square(const MatF* m) { return m->numRows == m->numCols; }
@@ -1387,6 +1398,89 @@ arm_status solve_tri_batch(bool lower, const MatF* t, const MatF* a, MatF* dst, 
   if (!t->pData || !a->pData || !dst->pData) return ARM_MATH_ARGUMENT_ERROR;
   return batch_status(mat_solve_tri_f32_launch(lower, t->numRows, a->numCols, t->pData, a->pData, dst->pData, batch,
                                                d_status, (hipStream_t)stream), what);
+}
+
+// ---- add / sub / scale, transposes, matrix x vector (mat_basic.hip) ------------------------------
+// matrix_functions.h groups MatrixAdd, MatrixSub, MatrixScale, MatrixTrans, MatrixComplexTrans and the
+// arm_mat_vec_mult_* of MatrixMult.  The shape rules are the reference's ARM_MATH_MATRIX_CHECK ones, applied
+// always.  sync: the drop-in (operands staged as SolveBuf describes); otherwise the batched form on device
+// pointers, which only enqueues.
+
+template <typename M>
+bool same_shape(const M* a, const M* b) { return a->numRows == b->numRows && a->numCols == b->numCols; }
+
+// op: kMatAdd / kMatSub (b != null) or kMatScale (b == null, scale and shift used).
+template <typename T, typename M>
+arm_status mat_ew(int op, const M* a, const M* b, M* d, T scale, int32_t shift, bool sync, uint32_t batch,
+                  void* stream, const char* what) {
+  const bool two = op != kMatScale;
+  if (!a || (two && !b) || !d) return ARM_MATH_ARGUMENT_ERROR;
+  if (sync && (!a->pData || (two && !b->pData) || !d->pData)) return ARM_MATH_ARGUMENT_ERROR;
+  if (!same_shape(a, d) || (two && !same_shape(a, b))) return ARM_MATH_SIZE_MISMATCH;
+  if (op == kMatScale && !std::is_same<T, float>::value) {
+    // past these the reference shifts by a negative or too large count
+    const int lo = sizeof(T) == 4 ? -1 : -16, hi = sizeof(T) == 4 ? 30 : 15;
+    if (shift < lo || shift > hi) return ARM_MATH_ARGUMENT_ERROR;
+  }
+  const size_t n = (size_t)a->numRows * a->numCols;
+  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
+  if (!sync) {
+    if (!a->pData || (two && !b->pData) || !d->pData) return ARM_MATH_ARGUMENT_ERROR;
+    return batch_status(mat_ew_launch<T>(op, (const T*)a->pData, two ? (const T*)b->pData : nullptr, (T*)d->pData,
+                                         n * batch, scale, shift, (hipStream_t)stream), what);
+  }
+  SolveBuf bufs[3] = {{a->pData, sizeof(T) * n, true, false},
+                      {d->pData, sizeof(T) * n, false, true},
+                      {two ? b->pData : nullptr, sizeof(T) * n, true, false}};
+  return mat_staged_sync(bufs, two ? 3 : 2, what, [&](hipStream_t st) {
+    return mat_ew_launch<T>(op, (const T*)bufs[0].d, (const T*)bufs[2].d, (T*)bufs[1].d, n, scale, shift, st);
+  });
+}
+
+// words: T words per element (2: interleaved complex).
+template <typename T, typename M>
+arm_status mat_trans(const M* s, M* d, int words, bool sync, uint32_t batch, void* stream, const char* what) {
+  if (!s || !d) return ARM_MATH_ARGUMENT_ERROR;
+  if (sync && (!s->pData || !d->pData)) return ARM_MATH_ARGUMENT_ERROR;
+  if (s->numRows != d->numCols || s->numCols != d->numRows) return ARM_MATH_SIZE_MISMATCH;
+  const size_t n = (size_t)s->numRows * s->numCols;
+  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
+  const int eb = (int)sizeof(T) * words;
+  if (!sync) {
+    if (!s->pData || !d->pData) return ARM_MATH_ARGUMENT_ERROR;
+    return batch_status(mat_trans_launch(eb, s->numRows, s->numCols, s->pData, d->pData, batch, (hipStream_t)stream),
+                        what);
+  }
+  SolveBuf bufs[2] = {{s->pData, eb * n, true, false}, {d->pData, eb * n, false, true}};
+  return mat_staged_sync(bufs, 2, what, [&](hipStream_t st) {
+    return mat_trans_launch(eb, s->numRows, s->numCols, bufs[0].d, bufs[1].d, 1, st);
+  });
+}
+
+template <typename T, typename M>
+arm_status mat_vec_mult_batch(const M* m, size_t matStride, const T* d_vec, T* d_dst, uint32_t batch, void* stream,
+                              const char* what) {
+  if (!m) return ARM_MATH_ARGUMENT_ERROR;
+  if (matStride != 0 && matStride < (size_t)m->numRows * m->numCols) return ARM_MATH_ARGUMENT_ERROR;
+  if (batch == 0 || m->numRows == 0) return ARM_MATH_SUCCESS;
+  if (!m->pData || !d_vec || !d_dst) return ARM_MATH_ARGUMENT_ERROR;
+  return batch_status(mat_vec_mult_launch<T>(m->numRows, m->numCols, (const T*)m->pData, matStride, d_vec, d_dst,
+                                             batch, (hipStream_t)stream), what);
+}
+
+template <typename T, typename M>
+void mat_vec_mult_sync(const M* m, const T* pVec, T* pDst, const char* what) {
+  if (!m || !m->pData || !pVec || !pDst) { set_error(hipErrorInvalidValue, what); return; }
+  const size_t rows = m->numRows, cols = m->numCols;
+  if (rows == 0) return;
+  // numCols == 0: every sum is empty and the outputs are zero, as in the reference; no operand word is read
+  SolveBuf bufs[3] = {{m->pData, sizeof(T) * rows * cols, cols != 0, false},
+                      {const_cast<T*>(pVec), sizeof(T) * cols, cols != 0, false},
+                      {pDst, sizeof(T) * rows, false, true}};
+  mat_staged_sync(bufs, 3, what, [&](hipStream_t st) {
+    return mat_vec_mult_launch<T>((int)rows, (int)cols, (const T*)bufs[0].d, 0, (const T*)bufs[1].d, (T*)bufs[2].d, 1,
+                                  st);
+  });
 }
 }  // namespace
 
@@ -1817,6 +1911,82 @@ arm_status arm_mat_solve_upper_triangular_f32_batch(const arm_matrix_instance_f3
                                                     uint32_t batch, int32_t* d_status, void* stream) {
   return solve_tri_batch(false, ut, a, dst, batch, d_status, stream, "arm_mat_solve_upper_triangular_f32_batch");
 }
+
+// ---- add / sub / scale, transposes, matrix x vector; mat_ew and its kin precede the C block ----
+#define MI355X_MAT_EW(SUF, INST, T, CT)                                                                          \
+  arm_status arm_mat_add_##SUF(const INST* pSrcA, const INST* pSrcB, INST* pDst) {                               \
+    return mat_ew<CT>(kMatAdd, pSrcA, pSrcB, pDst, (CT)0, 0, true, 1, nullptr, "arm_mat_add_" #SUF);             \
+  }                                                                                                              \
+  arm_status arm_mat_sub_##SUF(const INST* pSrcA, const INST* pSrcB, INST* pDst) {                               \
+    return mat_ew<CT>(kMatSub, pSrcA, pSrcB, pDst, (CT)0, 0, true, 1, nullptr, "arm_mat_sub_" #SUF);             \
+  }                                                                                                              \
+  arm_status arm_mat_add_##SUF##_batch(const INST* pSrcA, const INST* pSrcB, INST* pDst, uint32_t batch,         \
+                                       void* stream) {                                                           \
+    return mat_ew<CT>(kMatAdd, pSrcA, pSrcB, pDst, (CT)0, 0, false, batch, stream, "arm_mat_add_" #SUF "_batch"); \
+  }                                                                                                              \
+  arm_status arm_mat_sub_##SUF##_batch(const INST* pSrcA, const INST* pSrcB, INST* pDst, uint32_t batch,         \
+                                       void* stream) {                                                           \
+    return mat_ew<CT>(kMatSub, pSrcA, pSrcB, pDst, (CT)0, 0, false, batch, stream, "arm_mat_sub_" #SUF "_batch"); \
+  }
+MI355X_MAT_EW(f32, arm_matrix_instance_f32, float32_t, float)
+MI355X_MAT_EW(q31, arm_matrix_instance_q31, q31_t, int32_t)
+MI355X_MAT_EW(q15, arm_matrix_instance_q15, q15_t, int16_t)
+#undef MI355X_MAT_EW
+
+arm_status arm_mat_scale_f32(const arm_matrix_instance_f32* pSrc, float32_t scale, arm_matrix_instance_f32* pDst) {
+  return mat_ew<float>(kMatScale, pSrc, (const arm_matrix_instance_f32*)nullptr, pDst, scale, 0, true, 1, nullptr,
+                       "arm_mat_scale_f32");
+}
+arm_status arm_mat_scale_f32_batch(const arm_matrix_instance_f32* pSrc, float32_t scale,
+                                   arm_matrix_instance_f32* pDst, uint32_t batch, void* stream) {
+  return mat_ew<float>(kMatScale, pSrc, (const arm_matrix_instance_f32*)nullptr, pDst, scale, 0, false, batch, stream,
+                       "arm_mat_scale_f32_batch");
+}
+#define MI355X_MAT_SCALE(SUF, INST, T, CT)                                                                       \
+  arm_status arm_mat_scale_##SUF(const INST* pSrc, T scaleFract, int32_t shift, INST* pDst) {                    \
+    return mat_ew<CT>(kMatScale, pSrc, (const INST*)nullptr, pDst, scaleFract, shift, true, 1, nullptr,          \
+                      "arm_mat_scale_" #SUF);                                                                    \
+  }                                                                                                              \
+  arm_status arm_mat_scale_##SUF##_batch(const INST* pSrc, T scaleFract, int32_t shift, INST* pDst,              \
+                                         uint32_t batch, void* stream) {                                         \
+    return mat_ew<CT>(kMatScale, pSrc, (const INST*)nullptr, pDst, scaleFract, shift, false, batch, stream,      \
+                      "arm_mat_scale_" #SUF "_batch");                                                           \
+  }
+MI355X_MAT_SCALE(q31, arm_matrix_instance_q31, q31_t, int32_t)
+MI355X_MAT_SCALE(q15, arm_matrix_instance_q15, q15_t, int16_t)
+#undef MI355X_MAT_SCALE
+
+// NAME: trans / cmplx_trans; WORDS: CT words per element
+#define MI355X_MAT_TRANS(NAME, SUF, INST, CT, WORDS)                                                             \
+  arm_status arm_mat_##NAME##_##SUF(const INST* pSrc, INST* pDst) {                                              \
+    return mat_trans<CT>(pSrc, pDst, WORDS, true, 1, nullptr, "arm_mat_" #NAME "_" #SUF);                        \
+  }                                                                                                              \
+  arm_status arm_mat_##NAME##_##SUF##_batch(const INST* pSrc, INST* pDst, uint32_t batch, void* stream) {        \
+    return mat_trans<CT>(pSrc, pDst, WORDS, false, batch, stream, "arm_mat_" #NAME "_" #SUF "_batch");           \
+  }
+MI355X_MAT_TRANS(trans, f32, arm_matrix_instance_f32, float, 1)
+MI355X_MAT_TRANS(trans, q31, arm_matrix_instance_q31, int32_t, 1)
+MI355X_MAT_TRANS(trans, q15, arm_matrix_instance_q15, int16_t, 1)
+MI355X_MAT_TRANS(trans, q7, arm_matrix_instance_q7, int8_t, 1)
+MI355X_MAT_TRANS(cmplx_trans, f32, arm_matrix_instance_f32, float, 2)
+MI355X_MAT_TRANS(cmplx_trans, q31, arm_matrix_instance_q31, int32_t, 2)
+MI355X_MAT_TRANS(cmplx_trans, q15, arm_matrix_instance_q15, int16_t, 2)
+#undef MI355X_MAT_TRANS
+
+#define MI355X_MAT_VEC(SUF, INST, T, CT)                                                                         \
+  void arm_mat_vec_mult_##SUF(const INST* pSrcMat, const T* pVec, T* pDst) {                                     \
+    mat_vec_mult_sync<CT>(pSrcMat, (const CT*)pVec, (CT*)pDst, "arm_mat_vec_mult_" #SUF);                        \
+  }                                                                                                              \
+  arm_status arm_mat_vec_mult_##SUF##_batch(const INST* pSrcMat, uint32_t matStride, const T* d_vec, T* d_dst,   \
+                                            uint32_t batch, void* stream) {                                      \
+    return mat_vec_mult_batch<CT>(pSrcMat, matStride, (const CT*)d_vec, (CT*)d_dst, batch, stream,               \
+                                  "arm_mat_vec_mult_" #SUF "_batch");                                            \
+  }
+MI355X_MAT_VEC(f32, arm_matrix_instance_f32, float32_t, float)
+MI355X_MAT_VEC(q31, arm_matrix_instance_q31, q31_t, int32_t)
+MI355X_MAT_VEC(q15, arm_matrix_instance_q15, q15_t, int16_t)
+MI355X_MAT_VEC(q7, arm_matrix_instance_q7, q7_t, int8_t)
+#undef MI355X_MAT_VEC
 
 // ---- convolution ------------------------------------------------------------------
 #define MI355X_CONV_FULL(NAME, T, CT, OP, VAR)                                                                  \

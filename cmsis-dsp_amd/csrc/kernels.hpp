@@ -275,4 +275,23 @@ hipError_t mat_ldlt_f32_launch(int n, const float* src, float* pl, float* pd, ui
 hipError_t mat_solve_tri_f32_launch(bool lower, int n, int cols, const float* t, const float* a, float* x,
                                     uint32_t batch, int32_t* status, hipStream_t st);
 
+// Element-wise add / sub / scale, the transposes and matrix x vector, bit-exact with the reference's scalar
+// branches (mat_basic.hip); T is float, int32_t (q31), int16_t (q15) and, for vec_mult, int8_t (q7).
+// mat_ew_launch: d[i] = a[i] op b[i] over `count` words (the whole batch as one flat array; b unused by
+// kMatScale, which takes scale and, fixed point only, shift: q31 -1..30, q15 -16..15, else
+// hipErrorInvalidValue).  d may be a or b exactly.
+enum : int { kMatAdd = 0, kMatSub = 1, kMatScale = 2 };
+template <typename T>
+hipError_t mat_ew_launch(int op, const T* a, const T* b, T* d, size_t count, T scale, int shift, hipStream_t st);
+// dst[i] (cols x rows) = transpose of src[i] (rows x cols) for `batch` contiguous items of elemBytes-byte
+// elements (1, 2, 4, 8; a complex element is one (re, im) pair, not conjugated).  src and dst must not overlap.
+hipError_t mat_trans_launch(int elemBytes, int rows, int cols, const void* src, void* dst, uint32_t batch,
+                            hipStream_t st);
+// dst[i] (rows words) = mat_i (rows x cols) x vec[i] (cols words); mat_i = mat + i * matStride elements
+// (0: one matrix for every item).  int16_t and int32_t read row r where the reference's uint16_t offset
+// puts it (mat_basic.hip vm_row_offset), inside the item.
+template <typename T>
+hipError_t mat_vec_mult_launch(int rows, int cols, const T* mat, size_t matStride, const T* vec, T* dst,
+                               uint32_t batch, hipStream_t st);
+
 }  // namespace mi355x

@@ -978,6 +978,55 @@ arm_status arm_mat_solve_lower_triangular_f32(const arm_matrix_instance_f32 *lt,
 arm_status arm_mat_solve_upper_triangular_f32(const arm_matrix_instance_f32 *ut, const arm_matrix_instance_f32 *a,
                                               arm_matrix_instance_f32 *dst);
 
+/* Element-wise add, sub and scale, the transposes and matrix x vector (matrix_functions.h groups MatrixAdd,
+ * MatrixSub, MatrixScale, MatrixTrans, MatrixComplexTrans, and arm_mat_vec_mult_* of MatrixMult), bit-exact
+ * with the reference's scalar branches.  Host or device pData / pVec / pDst, synchronous.
+ *   add / sub   f32: one IEEE operation per word; q31: saturating (__QADD / __QSUB); q15: __SSAT(a +- b, 16).
+ *   scale       f32: x * scale.  q31: in = (q31_t)(((q63_t)x * scaleFract) >> 32), out = in << (shift + 1) with
+ *               saturation; -1 <= shift <= 30.  q15: __SSAT(((q31_t)x * scaleFract) >> (15 - shift), 16);
+ *               -16 <= shift <= 15.  A shift outside these ranges (a negative or too large shift count in the
+ *               reference) returns ARM_MATH_ARGUMENT_ERROR and leaves pDst alone.
+ *   trans / cmplx_trans   pure data movement; the complex forms count (re, im) pairs in numRows / numCols and
+ *               do not conjugate.
+ *   vec_mult    pDst[r] = sum_k pSrcMat[r][k] pVec[k], k ascending.  f32: product and sum rounded separately;
+ *               q31: the sum mod 2^64, >> 31, not saturated; q15: a q63 sum of __SMLALD pairs,
+ *               __SSAT(sum >> 15, 16); q7: __SSAT(sum >> 7, 8).  q15 and q31 keep the reference's uint16_t row
+ *               offset: past 65535 elements into the matrix a row is read from its offset mod 65536
+ *               (INTEGRATION.md).  A null pointer: no work, arm_mi355x_last_error() set.
+ * ARM_MATH_SIZE_MISMATCH on the shapes the reference rejects under ARM_MATH_MATRIX_CHECK (always on here: add /
+ * sub three equal shapes, scale two, a transpose's pDst the swapped shape); ARM_MATH_ARGUMENT_ERROR on a null
+ * pointer; a zero dimension is a successful no-op (vec_mult with numCols == 0 stores the empty sums, zeros, as the
+ * reference does).  pDst->pData of add / sub / scale may equal a source's pData exactly; any other overlap is
+ * undefined (it does not fault). */
+arm_status arm_mat_add_f32(const arm_matrix_instance_f32 *pSrcA, const arm_matrix_instance_f32 *pSrcB,
+                           arm_matrix_instance_f32 *pDst);
+arm_status arm_mat_add_q31(const arm_matrix_instance_q31 *pSrcA, const arm_matrix_instance_q31 *pSrcB,
+                           arm_matrix_instance_q31 *pDst);
+arm_status arm_mat_add_q15(const arm_matrix_instance_q15 *pSrcA, const arm_matrix_instance_q15 *pSrcB,
+                           arm_matrix_instance_q15 *pDst);
+arm_status arm_mat_sub_f32(const arm_matrix_instance_f32 *pSrcA, const arm_matrix_instance_f32 *pSrcB,
+                           arm_matrix_instance_f32 *pDst);
+arm_status arm_mat_sub_q31(const arm_matrix_instance_q31 *pSrcA, const arm_matrix_instance_q31 *pSrcB,
+                           arm_matrix_instance_q31 *pDst);
+arm_status arm_mat_sub_q15(const arm_matrix_instance_q15 *pSrcA, const arm_matrix_instance_q15 *pSrcB,
+                           arm_matrix_instance_q15 *pDst);
+arm_status arm_mat_scale_f32(const arm_matrix_instance_f32 *pSrc, float32_t scale, arm_matrix_instance_f32 *pDst);
+arm_status arm_mat_scale_q31(const arm_matrix_instance_q31 *pSrc, q31_t scaleFract, int32_t shift,
+                             arm_matrix_instance_q31 *pDst);
+arm_status arm_mat_scale_q15(const arm_matrix_instance_q15 *pSrc, q15_t scaleFract, int32_t shift,
+                             arm_matrix_instance_q15 *pDst);
+arm_status arm_mat_trans_f32(const arm_matrix_instance_f32 *pSrc, arm_matrix_instance_f32 *pDst);
+arm_status arm_mat_trans_q31(const arm_matrix_instance_q31 *pSrc, arm_matrix_instance_q31 *pDst);
+arm_status arm_mat_trans_q15(const arm_matrix_instance_q15 *pSrc, arm_matrix_instance_q15 *pDst);
+arm_status arm_mat_trans_q7(const arm_matrix_instance_q7 *pSrc, arm_matrix_instance_q7 *pDst);
+arm_status arm_mat_cmplx_trans_f32(const arm_matrix_instance_f32 *pSrc, arm_matrix_instance_f32 *pDst);
+arm_status arm_mat_cmplx_trans_q31(const arm_matrix_instance_q31 *pSrc, arm_matrix_instance_q31 *pDst);
+arm_status arm_mat_cmplx_trans_q15(const arm_matrix_instance_q15 *pSrc, arm_matrix_instance_q15 *pDst);
+void arm_mat_vec_mult_f32(const arm_matrix_instance_f32 *pSrcMat, const float32_t *pVec, float32_t *pDst);
+void arm_mat_vec_mult_q31(const arm_matrix_instance_q31 *pSrcMat, const q31_t *pVec, q31_t *pDst);
+void arm_mat_vec_mult_q15(const arm_matrix_instance_q15 *pSrcMat, const q15_t *pVec, q15_t *pDst);
+void arm_mat_vec_mult_q7(const arm_matrix_instance_q7 *pSrcMat, const q7_t *pVec, q7_t *pDst);
+
 #ifdef __cplusplus
 }
 #endif

@@ -327,6 +327,53 @@ arm_status arm_mat_solve_upper_triangular_f32_batch(const arm_matrix_instance_f3
                                                     uint32_t batch, int32_t *d_status, void *stream);
 arm_status arm_mat_ldlt_f32_batch(const arm_matrix_instance_f32 *pSrc, arm_matrix_instance_f32 *pl,
                                   arm_matrix_instance_f32 *pd, uint16_t *d_pp, uint32_t batch, void *stream);
+/* Element-wise add, sub and scale, the transposes and matrix x vector over `batch` independent items (per item:
+ * arm_mat_add_*, arm_mat_sub_*, arm_mat_scale_*, arm_mat_trans_*, arm_mat_cmplx_trans_*, arm_mat_vec_mult_*,
+ * bit-exact).  Every pData is a device pointer to `batch` contiguous row-major items of the instance's shape.
+ * Stream-ordered, no host synchronisation.  One scale (and shift) serves the whole batch.  pDst->pData of add /
+ * sub / scale may equal a source's pData exactly; no other overlap is defined.  batch == 0 and a zero dimension
+ * are successful no-ops; shape, shift and null-pointer errors as for the drop-ins.
+ * arm_mat_vec_mult_*_batch: item i multiplies the matrix at pSrcMat->pData + i * matStride (elements) by
+ * d_vec[i] (numCols words) into d_dst[i] (numRows words).  matStride == 0: one matrix shared by every item;
+ * otherwise matStride >= numRows * numCols, or ARM_MATH_ARGUMENT_ERROR.  The uint16_t row offset that _q15
+ * and _q31 keep wraps inside an item; item bases are full-width.  There are no _batch_multi forms. */
+#define MI355X_DECL_MAT_EW(SUF, INST)                                                                          \
+  arm_status arm_mat_add_##SUF##_batch(const INST *pSrcA, const INST *pSrcB, INST *pDst, uint32_t batch,       \
+                                       void *stream);                                                          \
+  arm_status arm_mat_sub_##SUF##_batch(const INST *pSrcA, const INST *pSrcB, INST *pDst, uint32_t batch,       \
+                                       void *stream);
+MI355X_DECL_MAT_EW(f32, arm_matrix_instance_f32)
+MI355X_DECL_MAT_EW(q31, arm_matrix_instance_q31)
+MI355X_DECL_MAT_EW(q15, arm_matrix_instance_q15)
+#undef MI355X_DECL_MAT_EW
+arm_status arm_mat_scale_f32_batch(const arm_matrix_instance_f32 *pSrc, float32_t scale,
+                                   arm_matrix_instance_f32 *pDst, uint32_t batch, void *stream);
+arm_status arm_mat_scale_q31_batch(const arm_matrix_instance_q31 *pSrc, q31_t scaleFract, int32_t shift,
+                                   arm_matrix_instance_q31 *pDst, uint32_t batch, void *stream);
+arm_status arm_mat_scale_q15_batch(const arm_matrix_instance_q15 *pSrc, q15_t scaleFract, int32_t shift,
+                                   arm_matrix_instance_q15 *pDst, uint32_t batch, void *stream);
+arm_status arm_mat_trans_f32_batch(const arm_matrix_instance_f32 *pSrc, arm_matrix_instance_f32 *pDst,
+                                   uint32_t batch, void *stream);
+arm_status arm_mat_trans_q31_batch(const arm_matrix_instance_q31 *pSrc, arm_matrix_instance_q31 *pDst,
+                                   uint32_t batch, void *stream);
+arm_status arm_mat_trans_q15_batch(const arm_matrix_instance_q15 *pSrc, arm_matrix_instance_q15 *pDst,
+                                   uint32_t batch, void *stream);
+arm_status arm_mat_trans_q7_batch(const arm_matrix_instance_q7 *pSrc, arm_matrix_instance_q7 *pDst,
+                                  uint32_t batch, void *stream);
+arm_status arm_mat_cmplx_trans_f32_batch(const arm_matrix_instance_f32 *pSrc, arm_matrix_instance_f32 *pDst,
+                                         uint32_t batch, void *stream);
+arm_status arm_mat_cmplx_trans_q31_batch(const arm_matrix_instance_q31 *pSrc, arm_matrix_instance_q31 *pDst,
+                                         uint32_t batch, void *stream);
+arm_status arm_mat_cmplx_trans_q15_batch(const arm_matrix_instance_q15 *pSrc, arm_matrix_instance_q15 *pDst,
+                                         uint32_t batch, void *stream);
+arm_status arm_mat_vec_mult_f32_batch(const arm_matrix_instance_f32 *pSrcMat, uint32_t matStride,
+                                      const float32_t *d_vec, float32_t *d_dst, uint32_t batch, void *stream);
+arm_status arm_mat_vec_mult_q31_batch(const arm_matrix_instance_q31 *pSrcMat, uint32_t matStride,
+                                      const q31_t *d_vec, q31_t *d_dst, uint32_t batch, void *stream);
+arm_status arm_mat_vec_mult_q15_batch(const arm_matrix_instance_q15 *pSrcMat, uint32_t matStride,
+                                      const q15_t *d_vec, q15_t *d_dst, uint32_t batch, void *stream);
+arm_status arm_mat_vec_mult_q7_batch(const arm_matrix_instance_q7 *pSrcMat, uint32_t matStride,
+                                     const q7_t *d_vec, q7_t *d_dst, uint32_t batch, void *stream);
 
 /* Multi-GPU complex FFT (SURVEY §8b "a multi-GPU entry point"; per item: arm_cfft_f32 /
  * _q31 / _q15, transform_functions.h:456-460).  Shard s of `nshards` is batch[s] contiguous

@@ -19,7 +19,18 @@ on the shrinking src; Cholesky n^3 / 3; LDLT n^3, three operations per word of t
 n^2 cols) and the fraction of 8 TB/s the algorithmic bytes reach.  Yardstick, on the same tensors in the same
 process: torch.linalg.inv, torch.linalg.cholesky, torch.linalg.solve_triangular (LDLT has none that pivots on
 the diagonal and is listed alone).  The first and last item are checked bit for bit against
-tests/mat_solve_ref.py first."""
+tests/mat_solve_ref.py first.
+
+Element-wise add / sub / scale, the transposes and matrix x vector (arm_mat_{add,sub,scale,trans,cmplx_trans,
+vec_mult}_*_batch), each workload with a type argument after a colon (none: every type it has):
+    python tools/bench_matrix.py [add|sub|scale|trans|cmplx_trans|vec_mult][:f32|:q31|:q15|:q7] ... [--gib G]
+n x n items, n in 4, 16, 64, 1024, the batch sized for about G GiB (default 1) of algorithmic traffic: elements
+read and written once (add / sub 3 n^2, scale and the transposes 2 n^2, a complex element two words; vec_mult
+n^2 + 2 n with one matrix per item).  Each line reports items/s and the fraction of 8 TB/s the algorithmic bytes
+reach, the same operation in torch on the same tensors in the same process (torch.add / sub / mul,
+transpose(1, 2).contiguous(), torch.bmm for the f32 vec_mult; the integer matrix-vector products have none) and,
+for the element-wise and transpose workloads, a torch copy of the same byte count (half read, half written).  The
+first and last item are checked bit for bit against tests/mat_basic_ref.py first."""
 import json
 import os
 import sys
@@ -253,6 +264,94 @@ def run_solve(func, n, gib):
     return ok
 
 
+BASIC_OPS = {"add": ("f32", "q31", "q15"), "sub": ("f32", "q31", "q15"), "scale": ("f32", "q31", "q15"),
+             "trans": ("f32", "q31", "q15", "q7"), "cmplx_trans": ("f32", "q31", "q15"),
+             "vec_mult": ("f32", "q31", "q15", "q7")}
+BASIC_SIZES = (4, 16, 64, 1024)
+BASIC_TDT = {"f32": torch.float32, "q31": torch.int32, "q15": torch.int16, "q7": torch.int8}
+BASIC_SCALE = {"f32": 0.75, "q31": 0x60000000, "q15": 0x6000}
+
+
+def run_basic(op, t, n, gib):
+    import mat_basic_ref as mb
+    size = torch.empty(0, dtype=BASIC_TDT[t]).element_size()
+    cw = 2 if op == "cmplx_trans" else 1
+    elems = {"add": 3 * n * n, "sub": 3 * n * n, "vec_mult": n * n + 2 * n}.get(op, 2 * n * n * cw)
+    batch = max(1, int(gib * 2 ** 30 / (size * elems)))
+    gen = torch.Generator(device="cuda").manual_seed(n)
+
+    def rnd(*shape, amp=None):
+        if t == "f32":
+            return torch.rand(shape, generator=gen, device="cuda", dtype=torch.float32) * 2 - 1
+        info = torch.iinfo(BASIC_TDT[t])
+        lo, hi = (info.min, info.max + 1) if amp is None else (-amp, amp + 1)
+        return torch.randint(lo, hi, shape, generator=gen, device="cuda", dtype=BASIC_TDT[t])
+
+    if op == "vec_mult":
+        amp = {"q7": 40 if n <= 64 else 15, "q15": 4000}.get(t)
+        a, b = rnd(batch, n, n, amp=amp), rnd(batch, n, amp=amp)
+        dst = torch.zeros((batch, n), dtype=BASIC_TDT[t], device="cuda")
+        ours = lambda: dsp.mat_vec_mult_batch(a, b, dst)                                 # noqa: E731
+        yard, yname = (lambda: torch.bmm(a, b.unsqueeze(2))), "torch.bmm"               # noqa: E731
+        if t != "f32":
+            yard = None
+        want = lambda i: mb.vec_mult(t, a[i].cpu().numpy(), b[i].cpu().numpy())          # noqa: E731
+    elif op in ("trans", "cmplx_trans"):
+        a = rnd(batch, n, n * cw)
+        dst = torch.zeros_like(a)
+        ours = (lambda: dsp.mat_trans_batch(a, dst)) if cw == 1 else (lambda: dsp.mat_cmplx_trans_batch(a, dst))
+        yard = (lambda: a.transpose(1, 2).contiguous()) if cw == 1 else \
+            (lambda: a.view(batch, n, n, 2).transpose(1, 2).contiguous())
+        yname = "transpose(1, 2).contiguous()"
+        want = lambda i: (mb.trans if cw == 1 else mb.cmplx_trans)(a[i].cpu().numpy())   # noqa: E731
+    else:
+        a, b = rnd(batch, n, n), rnd(batch, n, n) if op != "scale" else None
+        dst, ydst = torch.zeros_like(a), torch.empty_like(a)
+        sc = BASIC_SCALE[t]
+        if op == "scale":
+            ours = lambda: dsp.mat_scale_batch(a, sc, dst, shift=0)                      # noqa: E731
+            yard, yname = (lambda: torch.mul(a, sc if t == "f32" else 3, out=ydst)), "torch.mul"   # noqa: E731
+            want = lambda i: mb.scale(t, a[i].cpu().numpy(), sc, 0)                      # noqa: E731
+        else:
+            ours = (lambda: dsp.mat_add_batch(a, b, dst)) if op == "add" else (lambda: dsp.mat_sub_batch(a, b, dst))
+            yard = (lambda: torch.add(a, b, out=ydst)) if op == "add" else (lambda: torch.sub(a, b, out=ydst))
+            yname = f"torch.{op}"
+            want = lambda i: (mb.add if op == "add" else mb.sub)(t, a[i].cpu().numpy(), b[i].cpu().numpy())  # noqa: E731
+
+    ours()
+    torch.cuda.synchronize()
+    ok = all(dst[i].cpu().numpy().tobytes() == want(i).tobytes() for i in (0, batch - 1))
+
+    def measure(f):
+        settle(f)
+        steps = max(3, min(400, int(np.ceil(SOLVE_WINDOW_MS / max(timed(f, 3), 1e-3)))))
+        ms = [timed(f, steps) for _ in range(REPEATS)]
+        return ms, steps
+
+    ms, steps = measure(ours)
+    best = min(ms)
+    nbytes = size * elems * batch
+    line = {"workload": f"mat_{op}_{t}", "n": n, "batch": batch, "bitexact_first_last": ok,
+            "value": round(batch / (best * 1e-3) * 1e-6, 4), "unit": "M items/s",
+            "roofline": {"bound": "hbm", "bytes": nbytes, "peak_TBps": HBM_TBPS,
+                         "frac": round(nbytes / (best * 1e-3) / (HBM_TBPS * 1e12), 4)},
+            "ms": [round(x, 4) for x in ms], "spread": round((max(ms) - best) / best, 4), "steps": steps,
+            "version": dsp.version()}
+    if yard:
+        yms, ysteps = measure(yard)
+        line["yardstick"] = {"workload": yname, "ms": [round(x, 4) for x in yms], "steps": ysteps}
+        line["ratio_to_yardstick"] = round(min(yms) / best, 3)
+    if op != "vec_mult":
+        half = torch.empty(nbytes // 2, dtype=torch.int8, device="cuda")
+        other = torch.empty_like(half)
+        cms, csteps = measure(lambda: other.copy_(half))
+        line["copy"] = {"workload": "torch copy of the same byte count", "ms": [round(x, 4) for x in cms],
+                        "TBps": round(nbytes / (min(cms) * 1e-3) * 1e-12, 3), "steps": csteps}
+        line["ratio_to_copy"] = round(min(cms) / best, 3)
+    print(json.dumps(line), flush=True)
+    return ok
+
+
 def main():
     args = sys.argv[1:]
     gib = 1.0
@@ -260,6 +359,20 @@ def main():
         i = args.index("--gib")
         gib = float(args[i + 1])
         del args[i:i + 2]
+    basics = [k for k in args if k.split(":")[0] in BASIC_OPS]
+    if basics:
+        bad = []
+        for k in basics:
+            op, _, t = k.partition(":")
+            for ty in ([t] if t else BASIC_OPS[op]):
+                if ty not in BASIC_OPS[op]:
+                    sys.exit(f"{op} has no {ty} form")
+                bad += [f"{op}_{ty} n={n}" for n in BASIC_SIZES if not run_basic(op, ty, n, gib)]
+        if bad:
+            sys.exit(f"not bit-exact: {bad}")
+        args = [k for k in args if k not in basics]
+        if not args:
+            return
     solves = [k for k in args if k in ("inverse", "cholesky", "ldlt", "solve_lower", "solve_upper")]
     if solves:
         bad = [f"{f} n={n}" for f in solves for n in SOLVE_SIZES if not run_solve(f, n, gib)]
