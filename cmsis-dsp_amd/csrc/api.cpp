@@ -39,16 +39,40 @@ struct CfftPrep {
   const void* tw = nullptr;
   const uint16_t* perm = nullptr;
   uint32_t flags = 0;
+  // a 4-byte-aligned copy of a q15 twiddle table that sits on an odd 2-byte boundary (cfft_prepare),
+  // freed in stream order after the launches of the call that holds this
+  void* tw_copy = nullptr;
+  hipStream_t st = nullptr;
+  CfftPrep() = default;
+  CfftPrep(const CfftPrep&) = delete;
+  CfftPrep& operator=(const CfftPrep&) = delete;
+  ~CfftPrep() {
+    if (tw_copy) (void)hipFreeAsync(tw_copy, st);
+  }
 };
 
-// kind: 0 f32, 1 q31, 2 q15
+// kind: 0 f32, 1 q31, 2 q15; st: the stream the call's launches go to
 bool cfft_prepare(uint32_t n, const void* pTwiddle, const uint16_t* pBitRev, uint16_t bitRevLen, int kind,
-                  uint8_t ifftFlag, uint8_t bitReverseFlag, CfftPrep& out) {
+                  uint8_t ifftFlag, uint8_t bitReverseFlag, hipStream_t st, CfftPrep& out) {
   // twiddle words: f32 N complex (twiddleCoef_N[2N]); fixed-point 3N/4 complex
   // (twiddleCoef_N_q31[3N/2], arm_common_tables.h:61-116)
   const size_t twb = kind == 0 ? 8u * n : (kind == 1 ? 4u * 3u * n / 2u : 2u * 3u * n / 2u);
   out.tw = device_table(pTwiddle, twb);
   if (!out.tw) return false;   // device_table recorded the cause
+  // The q15 kernels read a twiddle as one (cos, sin) dword, and the lane-uniform ones (the last
+  // pass of cfft_fx_r16_kernel, stage 5 of cfft_q15_4096_pk_kernel) through the scalar cache, which
+  // drops the low two address bits.  The library's tables and the cache's copies are at least
+  // 4-byte aligned; a q15_t table resident in device memory need not be ("Pointer
+  // alignment contract"): it is copied to an aligned buffer on the call's stream, the kernels and
+  // the aligned path are untouched.
+  if (kind == 2 && ((uintptr_t)out.tw & 3u) != 0) {
+    hipError_t e = hipMallocAsync(&out.tw_copy, twb, st);
+    if (e != hipSuccess) { out.tw_copy = nullptr; set_error(e, "cfft twiddle copy"); return false; }
+    out.st = st;
+    e = hipMemcpyAsync(out.tw_copy, out.tw, twb, hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) { set_error(e, "cfft twiddle copy"); return false; }
+    out.tw = out.tw_copy;
+  }
   out.flags = (ifftFlag == 1u ? kIfft : 0u) | (bitReverseFlag ? kBitrev : 0u);   // arm_cfft_f32.c:1252,1282
   if (bitReverseFlag) {
     bool canon = true, ok = true;
@@ -74,7 +98,7 @@ void cfft_sync(const Inst* S, void* p1, uint8_t ifftFlag, uint8_t bitReverseFlag
   hipStream_t st = sync_stream();
   BlobScope hold(st);
   CfftPrep pr;
-  if (!cfft_prepare(n, S->pTwiddle, S->pBitRevTable, S->bitRevLength, kind, ifftFlag, bitReverseFlag, pr)) return;
+  if (!cfft_prepare(n, S->pTwiddle, S->pBitRevTable, S->bitRevLength, kind, ifftFlag, bitReverseFlag, st, pr)) return;
   const size_t bytes = 2 * word * n;
   if (is_device_ptr(p1)) {
     hipError_t e = cfft_launch(kind, n, p1, 1, pr, st);
@@ -118,7 +142,8 @@ arm_status cfft_batch(const Inst* S, void* d_p1, uint32_t batch, uint8_t ifftFla
   if (!S || (!d_p1 && batch) || !cfft_len_ok(S->fftLen)) return ARM_MATH_ARGUMENT_ERROR;
   BlobScope hold((hipStream_t)stream);
   CfftPrep pr;
-  if (!cfft_prepare(S->fftLen, S->pTwiddle, S->pBitRevTable, S->bitRevLength, kind, ifftFlag, bitReverseFlag, pr))
+  if (!cfft_prepare(S->fftLen, S->pTwiddle, S->pBitRevTable, S->bitRevLength, kind, ifftFlag, bitReverseFlag,
+                    (hipStream_t)stream, pr))
     return ARM_MATH_ARGUMENT_ERROR;
   return batch_status(cfft_launch(kind, S->fftLen, d_p1, batch, pr, (hipStream_t)stream), "arm_cfft_batch");
 }
@@ -163,7 +188,7 @@ arm_status cfft_batch_multi(const Inst* S, uint32_t nshards, const int* devices,
     if (batch[s] && !d_p1[s]) return ARM_MATH_ARGUMENT_ERROR;
   return run_multi(nshards, devices, batch, "arm_cfft_batch_multi", [&](uint32_t s, hipStream_t st) {
     CfftPrep pr;
-    if (!cfft_prepare(S->fftLen, S->pTwiddle, S->pBitRevTable, S->bitRevLength, kind, ifftFlag, bitReverseFlag, pr))
+    if (!cfft_prepare(S->fftLen, S->pTwiddle, S->pBitRevTable, S->bitRevLength, kind, ifftFlag, bitReverseFlag, st, pr))
       return false;
     hipError_t e = cfft_launch(kind, S->fftLen, d_p1[s], batch[s], pr, st);
     if (e != hipSuccess) { set_error(e, "arm_cfft_batch_multi"); return false; }
@@ -185,7 +210,7 @@ bool rfft_run(const arm_rfft_fast_instance_f32* S, float* d_p, float* d_out, uin
   if (!twr) return false;
   CfftPrep pr;
   // the inner CFFT receives ifftFlag unchanged and bitReverseFlag = 1 (:689, :694)
-  if (!cfft_prepare(h, S->Sint.pTwiddle, S->Sint.pBitRevTable, S->Sint.bitRevLength, 0, ifftFlag, 1, pr))
+  if (!cfft_prepare(h, S->Sint.pTwiddle, S->Sint.pBitRevTable, S->Sint.bitRevLength, 0, ifftFlag, 1, st, pr))
     return false;
   if (!pr.perm && ifftFlag <= 1) {   // the reference's own tables: one fused launch
     // (ifftFlag > 1: merge + a FORWARD inner CFFT, arm_cfft_f32.c:1252 -- unfused path)
@@ -217,7 +242,7 @@ bool rfft_fixed_run(const RInst* S, T* d_src, T* d_dst, uint32_t batch, hipStrea
   BlobScope hold(st);
   const bool inv = S->ifftFlagR == 1u;
   CfftPrep pr;
-  if (!cfft_prepare(L, in->pTwiddle, in->pBitRevTable, in->bitRevLength, kind, inv ? 1 : 0, S->bitReverseFlagR, pr))
+  if (!cfft_prepare(L, in->pTwiddle, in->pBitRevTable, in->bitRevLength, kind, inv ? 1 : 0, S->bitReverseFlagR, st, pr))
     return false;
   // forward, the reference's own bit reversal, bitReverseFlag 1: the split runs inside the CFFT
   // launch (cfft_fixed.hip L = 4096 from the tables as they are; cfft_fixed_r16.hip L = 256 .. 2048
@@ -540,7 +565,7 @@ bool mfcc_run(const Inst* S, const MfccFxDev<T>& d, T* x, T* y, T* dst, uint32_t
   BlobScope hold(st);
   CfftPrep pr;
   if (!cfft_prepare(L, in->pTwiddle, in->pBitRevTable, in->bitRevLength, sizeof(T) == 4 ? 1 : 2, 0,
-                    S->rfft.bitReverseFlagR, pr))
+                    S->rfft.bitReverseFlagR, st, pr))
     return false;
   if (MI355X_MFCC_FX_MODE >= 2 && !pr.perm) {    // the whole MFCC in one launch
     hipError_t e;
