@@ -612,6 +612,47 @@ arm_mat_vec_mult_q31 = _mat_basic("arm_mat_vec_mult_q31", "q31", """cmsis_arm_ma
     numRows int32 words; keeps the reference's 16-bit row offset (INTEGRATION.md).""")
 
 
+def _cmplx_math(name, doc):
+    """One of the 26 complex-math and max / min bindings (cmsisdsp_complexf.c, cmsisdsp_statistics.c)."""
+    op, kind = name[len("arm_"):].rsplit("_", 1)
+    dt = _DT[kind]
+    if op in ("max", "min"):
+        def run(pSrc):
+            v, i = getattr(_amd, f"arm_{op}")(kind, _arr(pSrc, dt))
+            return (float(v) if kind == "f32" else int(v)), int(i)
+    elif op == "cmplx_dot_prod":
+        def run(pSrcA, pSrcB):
+            re, im = _amd.arm_cmplx_dot_prod(kind, _arr(pSrcA, dt), _arr(pSrcB, dt))
+            return (float(re), float(im)) if kind == "f32" else (int(re), int(im))
+    elif op in ("cmplx_mult_cmplx", "cmplx_mult_real"):
+        def run(pSrcA, pSrcB):
+            return getattr(_amd, f"arm_{op}")(kind, _arr(pSrcA, dt), _arr(pSrcB, dt))
+    else:
+        def run(pSrc):
+            return getattr(_amd, f"arm_{op}")(kind, _arr(pSrc, dt))
+    run.__name__ = name
+    run.__doc__ = doc
+    return run
+
+
+for _t in ("f32", "q31", "q15"):
+    for _op, _doc in (
+            ("mag", "(pSrc) -> pDst: numSamples = len(pSrc) / 2 magnitudes, one word per complex sample."),
+            ("mag_squared", "(pSrc) -> pDst: len(pSrc) / 2 squared magnitudes."),
+            ("conj", "(pSrc) -> pDst: the conjugates, interleaved, as long as pSrc."),
+            ("mult_cmplx", "(pSrcA, pSrcB) -> pDst: the products, interleaved; numSamples = len(pSrcA) / 2."),
+            ("mult_real", "(pSrcCmplx, pSrcReal) -> pCmplxDst: interleaved; numSamples = len(pSrcCmplx) / 2."),
+            ("dot_prod", "(pSrcA, pSrcB) -> (realResult, imagResult), two Python numbers (f32: float; q31: the two "
+                         "64-bit sums; q15: q31 words).")):
+        _n = f"arm_cmplx_{_op}_{_t}"
+        globals()[_n] = _cmplx_math(_n, f"cmsisdsp_complexf.c cmsis_{_n} {_doc}")
+for _t in ("f32", "q31", "q15", "q7"):
+    for _op in ("max", "min"):
+        _n = f"arm_{_op}_{_t}"
+        globals()[_n] = _cmplx_math(_n, f"cmsisdsp_statistics.c cmsis_{_n} (pSrc) -> (pResult, pIndex): the {_op}imum "
+                                        "and the first index that holds it; blockSize = len(pSrc).")
+
+
 def arm_mat_mult_fast_q31(pSrcA, pSrcB):
     """cmsisdsp_matrix.c cmsis_arm_mat_mult_fast_q31: (status, C)."""
     return _amd.arm_mat_mult_fixed("fast_q31", _arr(pSrcA, _np.int32), _arr(pSrcB, _np.int32))

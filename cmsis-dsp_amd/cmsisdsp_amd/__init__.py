@@ -53,6 +53,7 @@ def _load():
     _abi.bind(lib, _abi.CMPLX_MAT)
     _abi.bind(lib, _abi.MAT_SOLVE)
     _abi.bind(lib, _abi.MAT_BASIC)
+    _abi.bind(lib, _abi.CMPLX_MATH)
     _abi.bind(lib, _abi.BATCHED)
     return lib
 
@@ -893,6 +894,162 @@ def mat_vec_mult_batch(mat, vec, dst, stream=None, mat_stride=None):
         mat_stride = 0 if mat.dim() == 2 else mat.shape[-2] * mat.shape[-1]
     _solve_call(f"arm_mat_vec_mult_{kind}_batch", C.byref(_mat(kind, mat)), int(mat_stride),
                 C.c_void_p(vec.data_ptr()), C.c_void_p(dst.data_ptr()), vec.shape[0], _stream_ptr(stream))
+
+
+# ---- complex math, max / min ------------------------------------------------------------------------------
+_DOT_DT = {"f32": np.float32, "q31": np.int64, "q15": np.int32}
+
+
+def _cm_src(kind, x):
+    return np.ascontiguousarray(x, dtype=_MAT_DT[kind]).reshape(-1)
+
+
+def _arm_cmplx_1(op, kind, src, words):
+    s = _cm_src(kind, src)
+    n = s.size // 2
+    d = np.zeros(n * words, dtype=s.dtype)
+    getattr(lib, f"arm_cmplx_{op}_{kind}")(s.ctypes.data, d.ctypes.data, n)
+    _check_void(f"arm_cmplx_{op}_{kind}")
+    return d
+
+
+def arm_cmplx_mag(kind, src):
+    """|z| of every interleaved (re, im) pair of src through arm_cmplx_mag_f32 / _q31 / _q15 (drop-in, numpy)."""
+    return _arm_cmplx_1("mag", kind, src, 1)
+
+
+def arm_cmplx_mag_squared(kind, src):
+    """re^2 + im^2 of every pair through arm_cmplx_mag_squared_f32 / _q31 / _q15."""
+    return _arm_cmplx_1("mag_squared", kind, src, 1)
+
+
+def arm_cmplx_conj(kind, src):
+    """The conjugate of every pair through arm_cmplx_conj_f32 / _q31 / _q15."""
+    return _arm_cmplx_1("conj", kind, src, 2)
+
+
+def arm_cmplx_mult_cmplx(kind, a, b):
+    """a[k] * b[k] for interleaved complex vectors through arm_cmplx_mult_cmplx_f32 / _q31 / _q15."""
+    a, b = _cm_src(kind, a), _cm_src(kind, b)
+    if b.size < a.size:
+        raise ValueError(f"arm_cmplx_mult_cmplx_{kind}: pSrcB has {b.size} words, pSrcA {a.size}")
+    d = np.zeros(a.size // 2 * 2, dtype=a.dtype)
+    getattr(lib, f"arm_cmplx_mult_cmplx_{kind}")(a.ctypes.data, b.ctypes.data, d.ctypes.data, a.size // 2)
+    _check_void(f"arm_cmplx_mult_cmplx_{kind}")
+    return d
+
+
+def arm_cmplx_mult_real(kind, cmplx, real):
+    """cmplx[k] * real[k] (a complex by a real vector) through arm_cmplx_mult_real_f32 / _q31 / _q15."""
+    a, r = _cm_src(kind, cmplx), _cm_src(kind, real)
+    if r.size < a.size // 2:
+        raise ValueError(f"arm_cmplx_mult_real_{kind}: pSrcReal has {r.size} words, pSrcCmplx {a.size // 2} samples")
+    d = np.zeros(a.size // 2 * 2, dtype=a.dtype)
+    getattr(lib, f"arm_cmplx_mult_real_{kind}")(a.ctypes.data, r.ctypes.data, d.ctypes.data, a.size // 2)
+    _check_void(f"arm_cmplx_mult_real_{kind}")
+    return d
+
+
+def arm_cmplx_dot_prod(kind, a, b):
+    """(real, imag) of sum a[k] * b[k] through arm_cmplx_dot_prod_f32 (float32) / _q31 (int64) / _q15 (int32)."""
+    a, b = _cm_src(kind, a), _cm_src(kind, b)
+    if b.size < a.size:
+        raise ValueError(f"arm_cmplx_dot_prod_{kind}: pSrcB has {b.size} words, pSrcA {a.size}")
+    out = np.zeros(2, dtype=_DOT_DT[kind])
+    getattr(lib, f"arm_cmplx_dot_prod_{kind}")(a.ctypes.data, b.ctypes.data, a.size // 2, out[0:].ctypes.data,
+                                               out[1:].ctypes.data)
+    _check_void(f"arm_cmplx_dot_prod_{kind}")
+    return out[0], out[1]
+
+
+def _arm_search(op, kind, src):
+    s = _cm_src(kind, src)
+    if s.size == 0:
+        raise ValueError(f"arm_{op}_{kind}: an empty vector has no {op}imum")
+    val, idx = np.zeros(1, dtype=s.dtype), np.zeros(1, dtype=np.uint32)
+    getattr(lib, f"arm_{op}_{kind}")(s.ctypes.data, s.size, val.ctypes.data, idx.ctypes.data)
+    _check_void(f"arm_{op}_{kind}")
+    return val[0], idx[0]
+
+
+def arm_max(kind, src):
+    """(value, index) of the maximum, the first index on a tie, through arm_max_f32 / _q31 / _q15 / _q7."""
+    return _arm_search("max", kind, src)
+
+
+def arm_min(kind, src):
+    """(value, index) of the minimum, the first index on a tie, through arm_min_f32 / _q31 / _q15 / _q7."""
+    return _arm_search("min", kind, src)
+
+
+def _cm_ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def _cmplx_1_batch(op, src, dst, stream):
+    kind = _mat_kind(src)
+    _solve_call(f"arm_cmplx_{op}_{kind}_batch", _cm_ptr(src), _cm_ptr(dst), src.shape[-1] // 2, src.shape[0],
+                _stream_ptr(stream))
+
+
+def cmplx_mag_batch(src, dst, stream=None):
+    """dst[i] [N] = |src[i]| for contiguous device tensors src [batch, 2N] of interleaved (re, im) float32 / int32
+    (q31) / int16 (q15) words (arm_cmplx_mag_*_batch).  dst must not overlap src."""
+    _cmplx_1_batch("mag", src, dst, stream)
+
+
+def cmplx_mag_squared_batch(src, dst, stream=None):
+    """dst[i] [N] = re^2 + im^2 of src[i] [2N] (arm_cmplx_mag_squared_*_batch)."""
+    _cmplx_1_batch("mag_squared", src, dst, stream)
+
+
+def cmplx_conj_batch(src, dst, stream=None):
+    """dst[i] [2N] = the conjugate of src[i] [2N] (arm_cmplx_conj_*_batch); dst may be src."""
+    _cmplx_1_batch("conj", src, dst, stream)
+
+
+def cmplx_mult_cmplx_batch(a, b, dst, stream=None):
+    """dst[i] [2N] = a[i] * b[i], element by element (arm_cmplx_mult_cmplx_*_batch); dst may be a or b."""
+    kind = _mat_kind(a)
+    _solve_call(f"arm_cmplx_mult_cmplx_{kind}_batch", _cm_ptr(a), _cm_ptr(b), _cm_ptr(dst), a.shape[-1] // 2,
+                a.shape[0], _stream_ptr(stream))
+
+
+def cmplx_mult_real_batch(cmplx, real, dst, stream=None):
+    """dst[i] [2N] = cmplx[i] [2N] times the real vector real[i] [N] (arm_cmplx_mult_real_*_batch); dst may be
+    cmplx."""
+    kind = _mat_kind(cmplx)
+    _solve_call(f"arm_cmplx_mult_real_{kind}_batch", _cm_ptr(cmplx), _cm_ptr(real), _cm_ptr(dst),
+                cmplx.shape[-1] // 2, cmplx.shape[0], _stream_ptr(stream))
+
+
+def cmplx_dot_prod_batch(a, b, re, im, stream=None, b_stride=None):
+    """re[i], im[i] = sum_k a[i][k] * b_i[k] for a [batch, 2N] (arm_cmplx_dot_prod_*_batch).  b [2N]: one vector for
+    every item (bStride 0); b [batch, 2N]: one per item.  re / im [batch]: float32, int64 (q31) or int32 (q15).
+    b_stride (complex samples) overrides the distance between the items' b vectors."""
+    kind = _mat_kind(a)
+    n = a.shape[-1] // 2
+    if b_stride is None:
+        b_stride = 0 if b.dim() == 1 else b.shape[-1] // 2
+    _solve_call(f"arm_cmplx_dot_prod_{kind}_batch", _cm_ptr(a), _cm_ptr(b), int(b_stride), n, _cm_ptr(re), _cm_ptr(im),
+                a.shape[0], _stream_ptr(stream))
+
+
+def _search_batch(op, src, result, index, stream):
+    kind = _mat_kind(src)
+    _solve_call(f"arm_{op}_{kind}_batch", _cm_ptr(src), src.shape[-1], _cm_ptr(result), _cm_ptr(index), src.shape[0],
+                _stream_ptr(stream))
+
+
+def max_batch(src, result, index, stream=None):
+    """result[i], index[i] = the maximum of src[i] [N] and its first index (arm_max_*_batch; float32, int32, int16,
+    int8).  index is a 32-bit tensor (the words are uint32)."""
+    _search_batch("max", src, result, index, stream)
+
+
+def min_batch(src, result, index, stream=None):
+    """result[i], index[i] = the minimum of src[i] [N] and its first index (arm_min_*_batch)."""
+    _search_batch("min", src, result, index, stream)
 
 
 def mat_mult_batch(a, b, c, stream=None, fast=False):

@@ -381,6 +381,22 @@ for _t, _inst in MAT_INST.items():
     MAT_BASIC[f"arm_mat_vec_mult_{_t}"] = (None, [_pm, C.c_void_p, C.c_void_p])
     MAT_BASIC[f"arm_mat_vec_mult_{_t}_batch"] = (C.c_int, [_pm, C.c_uint32, C.c_void_p, C.c_void_p] + _tail)
 
+# Complex math and max / min: 26 drop-ins (the reference's signatures, all void) and their _batch forms.  The
+# product only (tests/golden/cmplx_math.npz holds the reference's outputs).  Every pointer is a void*.
+CMPLX_MATH = {}
+_vp, _u32 = C.c_void_p, C.c_uint32
+for _t in ("f32", "q31", "q15"):
+    for _n, _a, _b in (("mag", [_vp, _vp, _u32], None), ("mag_squared", [_vp, _vp, _u32], None),
+                       ("conj", [_vp, _vp, _u32], None), ("mult_cmplx", [_vp, _vp, _vp, _u32], None),
+                       ("mult_real", [_vp, _vp, _vp, _u32], None),
+                       ("dot_prod", [_vp, _vp, _u32, _vp, _vp], [_vp, _vp, _u32, _u32, _vp, _vp])):
+        CMPLX_MATH[f"arm_cmplx_{_n}_{_t}"] = (None, _a)
+        CMPLX_MATH[f"arm_cmplx_{_n}_{_t}_batch"] = (C.c_int, (_b or _a) + [_u32, _vp])
+for _t in ("f32", "q31", "q15", "q7"):
+    for _n in ("max", "min"):
+        CMPLX_MATH[f"arm_{_n}_{_t}"] = (None, [_vp, _u32, _vp, _vp])
+        CMPLX_MATH[f"arm_{_n}_{_t}_batch"] = (C.c_int, [_vp, _u32, _vp, _vp, _u32, _vp])
+
 # per-length MFCC init functions (the product and the reference build; the oracle has the
 # generic init only)
 MFCC_LEN = {f"arm_mfcc_init_{n}_f32": (C.c_int, [P(arm_mfcc_instance_f32), C.c_uint32, C.c_uint32, C.c_void_p,

@@ -1507,6 +1507,95 @@ void mat_vec_mult_sync(const M* m, const T* pVec, T* pDst, const char* what) {
                                   st);
   });
 }
+// ---- complex math, max / min (cmplx_math.hip) ---------------------------------------------------
+// complex_math_functions.h and arm_max_* / arm_min_* of statistics_functions.h.  sync: the void drop-in (operands
+// staged as SolveBuf describes, a failure only sets the last error); otherwise the batched form on device
+// pointers, which only enqueues.  On device memory dst may be a source exactly where the kernel allows it
+// (conj: the source; mult_cmplx: either source; mult_real: the complex source); any other overlap of an output
+// with a source is refused.
+
+bool cm_overlaps(const void* d, size_t db, const void* s, size_t sb, bool exactOk) {
+  if (!db || !sb || !s) return false;
+  if (d == s && db == sb && exactOk) return false;
+  const uintptr_t d0 = (uintptr_t)d, s0 = (uintptr_t)s;
+  return d0 < s0 + sb && s0 < d0 + db;
+}
+
+arm_status cm_null(bool sync, const char* what) {
+  if (sync) set_error(hipErrorInvalidValue, what);
+  return ARM_MATH_ARGUMENT_ERROR;
+}
+
+template <typename T>
+arm_status cmplx_ew(int op, const T* a, const T* b, T* d, uint32_t n, bool sync, uint32_t batch, void* stream,
+                    const char* what) {
+  const int wb = op == kCmMultCmplx ? 2 : op == kCmMultReal ? 1 : 0;
+  const int wd = op == kCmMag || op == kCmMagSquared ? 1 : 2;
+  if (sync && (!a || (wb && !b) || !d)) return cm_null(true, what);
+  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
+  if (!a || (wb && !b) || !d) return ARM_MATH_ARGUMENT_ERROR;
+  const size_t count = (size_t)n * batch;
+  const bool lut = op == kCmMag && !std::is_same<T, float>::value;
+  auto run = [&](const T* da, const T* db, T* dd, hipStream_t st) -> hipError_t {
+    if (cm_overlaps(dd, sizeof(T) * wd * count, da, sizeof(T) * 2 * count, wd == 2) ||
+        cm_overlaps(dd, sizeof(T) * wd * count, db, sizeof(T) * wb * count, op == kCmMultCmplx))
+      return hipErrorInvalidValue;
+    const int32_t* dl = lut ? (const int32_t*)device_table(sqrt_initial_lut_q31, sizeof(int32_t) * 32) : nullptr;
+    if (lut && !dl) return hipErrorOutOfMemory;
+    return cmplx_ew_launch<T>(op, da, db, dd, count, dl, st);
+  };
+  if (!sync) return batch_status(run(a, b, d, (hipStream_t)stream), what);
+  SolveBuf bufs[3] = {{const_cast<T*>(a), sizeof(T) * 2 * count, true, false},
+                      {d, sizeof(T) * wd * count, false, true},
+                      {const_cast<T*>(b), sizeof(T) * wb * count, true, false}};
+  return mat_staged_sync(bufs, wb ? 3 : 2, what, [&](hipStream_t st) {
+    return run((const T*)bufs[0].d, wb ? (const T*)bufs[2].d : nullptr, (T*)bufs[1].d, st);
+  });
+}
+
+// bStride (complex samples; the drop-in passes n): 0 shares one b, otherwise >= n.
+template <typename T, typename R>
+arm_status cmplx_dot(const T* a, const T* b, uint32_t bStride, uint32_t n, R* re, R* im, bool sync, uint32_t batch,
+                     void* stream, const char* what) {
+  if (sync && (!a || !b || !re || !im)) return cm_null(true, what);
+  if (bStride != 0 && bStride < n) return ARM_MATH_ARGUMENT_ERROR;
+  if (batch == 0) return ARM_MATH_SUCCESS;
+  if (!a || !b || !re || !im) return ARM_MATH_ARGUMENT_ERROR;
+  const size_t ab = sizeof(T) * 2 * n * batch, ob = sizeof(R) * batch;
+  const size_t bb = sizeof(T) * 2 * ((size_t)bStride * (batch - 1) + n);
+  auto run = [&](const T* da, const T* db, R* dre, R* dim, hipStream_t st) -> hipError_t {
+    if (cm_overlaps(dre, ob, da, ab, false) || cm_overlaps(dre, ob, db, bb, false) ||
+        cm_overlaps(dim, ob, da, ab, false) || cm_overlaps(dim, ob, db, bb, false) || cm_overlaps(dre, ob, dim, ob, false))
+      return hipErrorInvalidValue;
+    return cmplx_dot_launch<T, R>(da, db, bStride, n, dre, dim, batch, st);
+  };
+  if (!sync) return batch_status(run(a, b, re, im, (hipStream_t)stream), what);
+  SolveBuf bufs[4] = {{const_cast<T*>(a), ab, n != 0, false}, {const_cast<T*>(b), bb, n != 0, false},
+                      {re, ob, false, true}, {im, ob, false, true}};
+  return mat_staged_sync(bufs, 4, what, [&](hipStream_t st) {
+    return run((const T*)bufs[0].d, (const T*)bufs[1].d, (R*)bufs[2].d, (R*)bufs[3].d, st);
+  });
+}
+
+template <typename T>
+arm_status cm_search(bool max, const T* src, uint32_t n, T* result, uint32_t* index, bool sync, uint32_t batch,
+                     void* stream, const char* what) {
+  if (sync && (!src || !result || !index)) return cm_null(true, what);
+  if (batch == 0) return ARM_MATH_SUCCESS;
+  if (n == 0) return cm_null(sync, what);                  // the reference reads pSrc[0]
+  if (!src || !result || !index) return ARM_MATH_ARGUMENT_ERROR;
+  const size_t sb = sizeof(T) * n * batch, rb = sizeof(T) * batch, ib = sizeof(uint32_t) * batch;
+  auto run = [&](const T* ds, T* dr, uint32_t* di, hipStream_t st) -> hipError_t {
+    if (cm_overlaps(dr, rb, ds, sb, false) || cm_overlaps(di, ib, ds, sb, false) || cm_overlaps(dr, rb, di, ib, false))
+      return hipErrorInvalidValue;
+    return search_launch<T>(max, ds, n, dr, di, batch, st);
+  };
+  if (!sync) return batch_status(run(src, result, index, (hipStream_t)stream), what);
+  SolveBuf bufs[3] = {{const_cast<T*>(src), sb, true, false}, {result, rb, false, true}, {index, ib, false, true}};
+  return mat_staged_sync(bufs, 3, what, [&](hipStream_t st) {
+    return run((const T*)bufs[0].d, (T*)bufs[1].d, (uint32_t*)bufs[2].d, st);
+  });
+}
 }  // namespace
 
 extern "C" {
@@ -2012,6 +2101,72 @@ MI355X_MAT_VEC(q31, arm_matrix_instance_q31, q31_t, int32_t)
 MI355X_MAT_VEC(q15, arm_matrix_instance_q15, q15_t, int16_t)
 MI355X_MAT_VEC(q7, arm_matrix_instance_q7, q7_t, int8_t)
 #undef MI355X_MAT_VEC
+
+// ---- complex math, max / min; cmplx_ew and its kin precede the C block ----
+// one source: mag, mag_squared, conj
+#define MI355X_CMPLX_1(NAME, OP, SUF, T, CT)                                                                     \
+  void arm_cmplx_##NAME##_##SUF(const T* pSrc, T* pDst, uint32_t numSamples) {                                   \
+    cmplx_ew<CT>(OP, (const CT*)pSrc, (const CT*)nullptr, (CT*)pDst, numSamples, true, 1, nullptr,               \
+                 "arm_cmplx_" #NAME "_" #SUF);                                                                   \
+  }                                                                                                              \
+  arm_status arm_cmplx_##NAME##_##SUF##_batch(const T* d_src, T* d_dst, uint32_t numSamples, uint32_t batch,     \
+                                              void* stream) {                                                    \
+    return cmplx_ew<CT>(OP, (const CT*)d_src, (const CT*)nullptr, (CT*)d_dst, numSamples, false, batch, stream,  \
+                        "arm_cmplx_" #NAME "_" #SUF "_batch");                                                   \
+  }
+// two sources: mult_cmplx (pSrcB complex), mult_real (pSrcB real)
+#define MI355X_CMPLX_2(NAME, OP, SUF, T, CT)                                                                     \
+  void arm_cmplx_##NAME##_##SUF(const T* pSrcA, const T* pSrcB, T* pDst, uint32_t numSamples) {                  \
+    cmplx_ew<CT>(OP, (const CT*)pSrcA, (const CT*)pSrcB, (CT*)pDst, numSamples, true, 1, nullptr,                \
+                 "arm_cmplx_" #NAME "_" #SUF);                                                                   \
+  }                                                                                                              \
+  arm_status arm_cmplx_##NAME##_##SUF##_batch(const T* d_srcA, const T* d_srcB, T* d_dst, uint32_t numSamples,   \
+                                              uint32_t batch, void* stream) {                                    \
+    return cmplx_ew<CT>(OP, (const CT*)d_srcA, (const CT*)d_srcB, (CT*)d_dst, numSamples, false, batch, stream,  \
+                        "arm_cmplx_" #NAME "_" #SUF "_batch");                                                   \
+  }
+#define MI355X_CMPLX_DOT(SUF, T, CT, R, CR)                                                                      \
+  void arm_cmplx_dot_prod_##SUF(const T* pSrcA, const T* pSrcB, uint32_t numSamples, R* realResult,              \
+                                R* imagResult) {                                                                 \
+    cmplx_dot<CT, CR>((const CT*)pSrcA, (const CT*)pSrcB, numSamples, numSamples, (CR*)realResult,               \
+                      (CR*)imagResult, true, 1, nullptr, "arm_cmplx_dot_prod_" #SUF);                            \
+  }                                                                                                              \
+  arm_status arm_cmplx_dot_prod_##SUF##_batch(const T* d_a, const T* d_b, uint32_t bStride, uint32_t numSamples, \
+                                              R* d_re, R* d_im, uint32_t batch, void* stream) {                  \
+    return cmplx_dot<CT, CR>((const CT*)d_a, (const CT*)d_b, bStride, numSamples, (CR*)d_re, (CR*)d_im, false,   \
+                             batch, stream, "arm_cmplx_dot_prod_" #SUF "_batch");                                \
+  }
+#define MI355X_CMPLX_TYPE(SUF, T, CT, R, CR)                   \
+  MI355X_CMPLX_1(mag, kCmMag, SUF, T, CT)                      \
+  MI355X_CMPLX_1(mag_squared, kCmMagSquared, SUF, T, CT)       \
+  MI355X_CMPLX_1(conj, kCmConj, SUF, T, CT)                    \
+  MI355X_CMPLX_2(mult_cmplx, kCmMultCmplx, SUF, T, CT)         \
+  MI355X_CMPLX_2(mult_real, kCmMultReal, SUF, T, CT)           \
+  MI355X_CMPLX_DOT(SUF, T, CT, R, CR)
+MI355X_CMPLX_TYPE(f32, float32_t, float, float32_t, float)
+MI355X_CMPLX_TYPE(q31, q31_t, int32_t, q63_t, int64_t)
+MI355X_CMPLX_TYPE(q15, q15_t, int16_t, q31_t, int32_t)
+#undef MI355X_CMPLX_TYPE
+#undef MI355X_CMPLX_DOT
+#undef MI355X_CMPLX_2
+#undef MI355X_CMPLX_1
+
+#define MI355X_SEARCH(NAME, MAX, SUF, T, CT)                                                                     \
+  void arm_##NAME##_##SUF(const T* pSrc, uint32_t blockSize, T* pResult, uint32_t* pIndex) {                     \
+    cm_search<CT>(MAX, (const CT*)pSrc, blockSize, (CT*)pResult, pIndex, true, 1, nullptr, "arm_" #NAME "_" #SUF); \
+  }                                                                                                              \
+  arm_status arm_##NAME##_##SUF##_batch(const T* d_src, uint32_t blockSize, T* d_result, uint32_t* d_index,      \
+                                        uint32_t batch, void* stream) {                                          \
+    return cm_search<CT>(MAX, (const CT*)d_src, blockSize, (CT*)d_result, d_index, false, batch, stream,         \
+                         "arm_" #NAME "_" #SUF "_batch");                                                        \
+  }
+#define MI355X_SEARCH_TYPE(SUF, T, CT) MI355X_SEARCH(max, true, SUF, T, CT) MI355X_SEARCH(min, false, SUF, T, CT)
+MI355X_SEARCH_TYPE(f32, float32_t, float)
+MI355X_SEARCH_TYPE(q31, q31_t, int32_t)
+MI355X_SEARCH_TYPE(q15, q15_t, int16_t)
+MI355X_SEARCH_TYPE(q7, q7_t, int8_t)
+#undef MI355X_SEARCH_TYPE
+#undef MI355X_SEARCH
 
 // ---- convolution ------------------------------------------------------------------
 #define MI355X_CONV_FULL(NAME, T, CT, OP, VAR)                                                                  \

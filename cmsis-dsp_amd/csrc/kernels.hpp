@@ -294,4 +294,25 @@ template <typename T>
 hipError_t mat_vec_mult_launch(int rows, int cols, const T* mat, size_t matStride, const T* vec, T* dst,
                                uint32_t batch, hipStream_t st);
 
+// Complex math and max / min, bit-exact with the reference's scalar branches (cmplx_math.hip); T is float,
+// int32_t (q31), int16_t (q15) and, for the searches, int8_t (q7).  Complex vectors are interleaved (re, im).
+// cmplx_ew_launch: `count` complex samples (the whole batch as one flat array).  kCmMag / kCmMagSquared write one
+// word per sample, the others two; b is the second complex vector (kCmMultCmplx), the real vector (kCmMultReal)
+// or unused.  d may be a (or b) exactly for kCmConj / kCmMultCmplx / kCmMultReal; no other overlap.  lut: the
+// device copy of sqrt_initial_lut_q31 (read by the q31 / q15 kCmMag only).
+enum : int { kCmMag = 0, kCmMagSquared = 1, kCmConj = 2, kCmMultCmplx = 3, kCmMultReal = 4 };
+template <typename T>
+hipError_t cmplx_ew_launch(int op, const T* a, const T* b, T* d, size_t count, const int32_t* lut, hipStream_t st);
+// re[i], im[i] = the complex dot product of a[i] and b_i (n samples each), b_i = b + i * bStride samples (0: one
+// b for every item).  R: float, int64_t (q31: the two 64-bit sums as they are) or int32_t (q15: >> 6).  n == 0
+// stores zeros.  The float chain is ordered sample by sample.
+template <typename T, typename R>
+hipError_t cmplx_dot_launch(const T* a, const T* b, size_t bStride, uint32_t n, R* re, R* im, uint32_t batch,
+                            hipStream_t st);
+// result[i], index[i] = the maximum (max) or minimum of src[i] (n words, n > 0) and the first index that holds it;
+// NaN as the reference's strict comparisons treat it.
+template <typename T>
+hipError_t search_launch(bool max, const T* src, uint32_t n, T* result, uint32_t* index, uint32_t batch,
+                         hipStream_t st);
+
 }  // namespace mi355x

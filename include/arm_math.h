@@ -1027,6 +1027,50 @@ void arm_mat_vec_mult_q31(const arm_matrix_instance_q31 *pSrcMat, const q31_t *p
 void arm_mat_vec_mult_q15(const arm_matrix_instance_q15 *pSrcMat, const q15_t *pVec, q15_t *pDst);
 void arm_mat_vec_mult_q7(const arm_matrix_instance_q7 *pSrcMat, const q7_t *pVec, q7_t *pDst);
 
+/* Complex math (complex_math_functions.h: ComplexMag, ComplexMagSquared, ComplexConj, CmplxByCmplxMult,
+ * CmplxByRealMult, ComplexDotProduct) and the max / min searches of statistics_functions.h, bit-exact with the
+ * reference's scalar branches.  Complex vectors are interleaved (re, im) words and numSamples counts complex
+ * samples.  Host or device pointers, synchronous.
+ *   mag          f32: arm_sqrt_f32(re*re + im*im): a NaN sum stores +0.0.  q31: arm_sqrt_q31((re*re >> 33) +
+ *                (im*im >> 33)), 2.30.  q15: arm_sqrt_q31((re*re + im*im) >> 1) >> 16, 2.14.
+ *   mag_squared  f32: re*re + im*im.  q31: (re*re >> 33) + (im*im >> 33), 3.29.  q15: (re*re + im*im) >> 17, 3.13.
+ *   conj         the imaginary word negated (fixed point: the minimum maps to the maximum; f32: the sign bit).
+ *   mult_cmplx   (a*c) - (b*d), (a*d) + (b*c); q31: every product >> 33 first (3.29); q15: >> 17 first (3.13).
+ *   mult_real    f32: x * r; q31 / q15: the product >> 31 / >> 15, saturated.
+ *   dot_prod     f32: re = (re + a*c) - b*d, im = (im + a*d) + b*c sample by sample from 0.0f, every product
+ *                rounded on its own.  q31: products >> 14 in two 64-bit sums (16.48).  q15: 64-bit sums of exact
+ *                products, >> 6, stored as q31_t (8.24).  numSamples == 0 stores zeros.
+ *   max / min    the value and the first index that holds it (a strict comparison replaces the running result);
+ *                +0.0 and -0.0 tie; a NaN after pSrc[0] is never selected and a NaN in pSrc[0] never replaced.
+ * Left out: arm_cmplx_mag_fast_q15, the f16 / f64 forms, the _no_idx and absmax / absmin variants.
+ * A null pointer, and blockSize == 0 in max / min (the reference reads pSrc[0]): nothing is written and
+ * arm_mi355x_last_error() is set.  numSamples == 0 writes nothing (dot_prod: zeros).
+ * Aliasing.  pDst may equal a source exactly for conj (pSrc), mult_cmplx (pSrcA or pSrcB) and mult_real
+ * (pSrcCmplx).  With host pointers the operands are staged separately, so any other overlap, mag / mag_squared
+ * into their own source included, behaves as if every source were read before the first store.  With device
+ * pointers any other overlap of an output with a source is refused: nothing is written and
+ * arm_mi355x_last_error() is set. */
+#define MI355X_DECL_CMPLX(SUF, T, R)                                                                            \
+  void arm_cmplx_mag_##SUF(const T *pSrc, T *pDst, uint32_t numSamples);                                        \
+  void arm_cmplx_mag_squared_##SUF(const T *pSrc, T *pDst, uint32_t numSamples);                                \
+  void arm_cmplx_conj_##SUF(const T *pSrc, T *pDst, uint32_t numSamples);                                       \
+  void arm_cmplx_mult_cmplx_##SUF(const T *pSrcA, const T *pSrcB, T *pDst, uint32_t numSamples);                \
+  void arm_cmplx_mult_real_##SUF(const T *pSrcCmplx, const T *pSrcReal, T *pCmplxDst, uint32_t numSamples);     \
+  void arm_cmplx_dot_prod_##SUF(const T *pSrcA, const T *pSrcB, uint32_t numSamples, R *realResult,             \
+                                R *imagResult);
+MI355X_DECL_CMPLX(f32, float32_t, float32_t)
+MI355X_DECL_CMPLX(q31, q31_t, q63_t)
+MI355X_DECL_CMPLX(q15, q15_t, q31_t)
+#undef MI355X_DECL_CMPLX
+void arm_max_f32(const float32_t *pSrc, uint32_t blockSize, float32_t *pResult, uint32_t *pIndex);
+void arm_max_q31(const q31_t *pSrc, uint32_t blockSize, q31_t *pResult, uint32_t *pIndex);
+void arm_max_q15(const q15_t *pSrc, uint32_t blockSize, q15_t *pResult, uint32_t *pIndex);
+void arm_max_q7(const q7_t *pSrc, uint32_t blockSize, q7_t *pResult, uint32_t *pIndex);
+void arm_min_f32(const float32_t *pSrc, uint32_t blockSize, float32_t *pResult, uint32_t *pIndex);
+void arm_min_q31(const q31_t *pSrc, uint32_t blockSize, q31_t *pResult, uint32_t *pIndex);
+void arm_min_q15(const q15_t *pSrc, uint32_t blockSize, q15_t *pResult, uint32_t *pIndex);
+void arm_min_q7(const q7_t *pSrc, uint32_t blockSize, q7_t *pResult, uint32_t *pIndex);
+
 #ifdef __cplusplus
 }
 #endif

@@ -374,6 +374,46 @@ arm_status arm_mat_vec_mult_q15_batch(const arm_matrix_instance_q15 *pSrcMat, ui
                                       const q15_t *d_vec, q15_t *d_dst, uint32_t batch, void *stream);
 arm_status arm_mat_vec_mult_q7_batch(const arm_matrix_instance_q7 *pSrcMat, uint32_t matStride,
                                      const q7_t *d_vec, q7_t *d_dst, uint32_t batch, void *stream);
+/* Complex math and max / min over `batch` independent items (per item: arm_cmplx_mag_*, _mag_squared_*, _conj_*,
+ * _mult_cmplx_*, _mult_real_*, _dot_prod_*, arm_max_*, arm_min_*, bit-exact).  Every pointer is a device pointer
+ * to `batch` contiguous items: numSamples complex samples (interleaved re, im) per item, one word per sample in the
+ * real vector of mult_real and in the output of mag / mag_squared, one result (and one uint32_t index) per item
+ * for dot_prod / max / min.  Stream-ordered, no host synchronisation.
+ * d_dst may equal a source exactly for conj (d_src), mult_cmplx (d_srcA or d_srcB) and mult_real (d_cmplx); any
+ * other overlap of an output with a source returns ARM_MATH_ARGUMENT_ERROR (arm_mi355x_last_error() set).
+ * arm_cmplx_dot_prod_*_batch: item i multiplies d_a[i] by the vector at d_b + i * bStride complex samples.
+ * bStride == 0: one d_b shared by every item (correlation against a template); otherwise bStride >= numSamples,
+ * or ARM_MATH_ARGUMENT_ERROR.  numSamples == 0 stores zeros.
+ * ARM_MATH_ARGUMENT_ERROR on a null pointer; batch == 0, and numSamples == 0 where nothing is to be written, are
+ * successful no-ops; blockSize == 0 with batch > 0 is an ARM_MATH_ARGUMENT_ERROR (the reference reads pSrc[0]).
+ * There are no _batch_multi forms. */
+#define MI355X_DECL_CMPLX_BATCH(SUF, T, R)                                                                     \
+  arm_status arm_cmplx_mag_##SUF##_batch(const T *d_src, T *d_dst, uint32_t numSamples, uint32_t batch,        \
+                                         void *stream);                                                        \
+  arm_status arm_cmplx_mag_squared_##SUF##_batch(const T *d_src, T *d_dst, uint32_t numSamples, uint32_t batch, \
+                                                 void *stream);                                                \
+  arm_status arm_cmplx_conj_##SUF##_batch(const T *d_src, T *d_dst, uint32_t numSamples, uint32_t batch,       \
+                                          void *stream);                                                       \
+  arm_status arm_cmplx_mult_cmplx_##SUF##_batch(const T *d_srcA, const T *d_srcB, T *d_dst, uint32_t numSamples, \
+                                                uint32_t batch, void *stream);                                 \
+  arm_status arm_cmplx_mult_real_##SUF##_batch(const T *d_cmplx, const T *d_real, T *d_dst, uint32_t numSamples, \
+                                               uint32_t batch, void *stream);                                  \
+  arm_status arm_cmplx_dot_prod_##SUF##_batch(const T *d_a, const T *d_b, uint32_t bStride, uint32_t numSamples, \
+                                              R *d_re, R *d_im, uint32_t batch, void *stream);
+MI355X_DECL_CMPLX_BATCH(f32, float32_t, float32_t)
+MI355X_DECL_CMPLX_BATCH(q31, q31_t, q63_t)
+MI355X_DECL_CMPLX_BATCH(q15, q15_t, q31_t)
+#undef MI355X_DECL_CMPLX_BATCH
+#define MI355X_DECL_SEARCH_BATCH(SUF, T)                                                                       \
+  arm_status arm_max_##SUF##_batch(const T *d_src, uint32_t blockSize, T *d_result, uint32_t *d_index,         \
+                                   uint32_t batch, void *stream);                                              \
+  arm_status arm_min_##SUF##_batch(const T *d_src, uint32_t blockSize, T *d_result, uint32_t *d_index,         \
+                                   uint32_t batch, void *stream);
+MI355X_DECL_SEARCH_BATCH(f32, float32_t)
+MI355X_DECL_SEARCH_BATCH(q31, q31_t)
+MI355X_DECL_SEARCH_BATCH(q15, q15_t)
+MI355X_DECL_SEARCH_BATCH(q7, q7_t)
+#undef MI355X_DECL_SEARCH_BATCH
 
 /* Multi-GPU complex FFT (SURVEY §8b "a multi-GPU entry point"; per item: arm_cfft_f32 /
  * _q31 / _q15, transform_functions.h:456-460).  Shard s of `nshards` is batch[s] contiguous
