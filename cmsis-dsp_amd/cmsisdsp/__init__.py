@@ -653,6 +653,57 @@ for _t in ("f32", "q31", "q15", "q7"):
                                         "and the first index that holds it; blockSize = len(pSrc).")
 
 
+def _statistics(name, doc):
+    """One of the statistics bindings (cmsisdsp_statistics.c): a Python number, or (value, index)."""
+    op, kind = name[len("arm_"):].rsplit("_", 1)
+    dt = _DT[kind]
+    num = float if kind == "f32" else int
+    if op in ("absmax", "absmin"):
+        def run(pSrc):
+            v, i = getattr(_amd, f"arm_{op}")(kind, _arr(pSrc, dt))
+            return num(v), int(i)
+    elif op == "mse":
+        def run(pSrcA, pSrcB):
+            return num(_amd.arm_stat(op, kind, _arr(pSrcA, dt), _arr(pSrcB, dt)))
+    else:
+        def run(pSrc):
+            return num(_amd.arm_stat(op, kind, _arr(pSrc, dt)))
+    run.__name__ = name
+    run.__doc__ = doc
+    return run
+
+
+for _t in ("f32", "q31", "q15", "q7"):
+    _ops = [("mean", "(pSrc) -> pResult: the mean, truncated toward zero in fixed point."),
+            ("power", "(pSrc) -> pResult: the sum of squares (f32: float; q31, q15: a 64-bit int; q7: q31)."),
+            ("mse", "(pSrcA, pSrcB) -> pResult: the mean squared error."),
+            ("max_no_idx", "(pSrc) -> pResult: the maximum."), ("min_no_idx", "(pSrc) -> pResult: the minimum."),
+            ("absmax_no_idx", "(pSrc) -> pResult: the maximum of |x|."),
+            ("absmin_no_idx", "(pSrc) -> pResult: the minimum of |x|."),
+            ("absmax", "(pSrc) -> (pResult, pIndex): the maximum of |x| and the first index that holds it."),
+            ("absmin", "(pSrc) -> (pResult, pIndex): the minimum of |x| and the first index that holds it.")]
+    if _t != "q7":
+        _ops += [("rms", "(pSrc) -> pResult: the root mean square."),
+                 ("var", "(pSrc) -> pResult: the unbiased variance."),
+                 ("std", "(pSrc) -> pResult: the standard deviation.")]
+    if _t == "f32":
+        _ops += [("accumulate", "(pSrc) -> pResult: the ordered sum.")]
+    for _op, _doc in _ops:
+        _n = f"arm_{_op}_{_t}"
+        globals()[_n] = _statistics(_n, f"cmsisdsp_statistics.c cmsis_{_n} {_doc}  blockSize = len(pSrc).")
+
+
+def arm_sqrt_q15(x):
+    """cmsisdsp_fastmath.c cmsis_arm_sqrt_q15 (in) -> (status, pOut)."""
+    st, v = _amd.arm_sqrt_q15(x)
+    return int(st), int(v)
+
+
+def arm_cmplx_mag_fast_q15(pSrc):
+    """cmsisdsp_complexf.c cmsis_arm_cmplx_mag_fast_q15 (pSrc) -> pDst: numSamples = len(pSrc) / 2 magnitudes."""
+    return _amd.arm_cmplx_mag_fast_q15(_arr(pSrc, _np.int16))
+
+
 def arm_mat_mult_fast_q31(pSrcA, pSrcB):
     """cmsisdsp_matrix.c cmsis_arm_mat_mult_fast_q31: (status, C)."""
     return _amd.arm_mat_mult_fixed("fast_q31", _arr(pSrcA, _np.int32), _arr(pSrcB, _np.int32))

@@ -54,6 +54,7 @@ def _load():
     _abi.bind(lib, _abi.MAT_SOLVE)
     _abi.bind(lib, _abi.MAT_BASIC)
     _abi.bind(lib, _abi.CMPLX_MATH)
+    _abi.bind(lib, _abi.STATISTICS)
     _abi.bind(lib, _abi.BATCHED)
     return lib
 
@@ -1050,6 +1051,135 @@ def max_batch(src, result, index, stream=None):
 def min_batch(src, result, index, stream=None):
     """result[i], index[i] = the minimum of src[i] [N] and its first index (arm_min_*_batch)."""
     _search_batch("min", src, result, index, stream)
+
+
+# ---- statistics: the sums and level measures, the abs / no-index searches, arm_sqrt_q15 -------------------------
+_POWER_DT = {"f32": np.float32, "q31": np.int64, "q15": np.int64, "q7": np.int32}
+
+
+def arm_stat(op, kind, src, src_b=None):
+    """The one result word of arm_<op>_<kind> (drop-in, numpy): op is mean, power, rms, var, std, accumulate, mse
+    (with src_b) or max_no_idx / min_no_idx / absmax_no_idx / absmin_no_idx.  power returns float32 / int64 / int64
+    / int32, everything else the type of src."""
+    name = f"arm_{op}_{kind}"
+    s = _cm_src(kind, src)
+    out = np.zeros(1, dtype=_POWER_DT[kind] if op == "power" else s.dtype)
+    if op == "mse":
+        b = _cm_src(kind, src_b)
+        if b.size != s.size:
+            raise ValueError(f"{name}: pSrcB has {b.size} words, pSrcA {s.size}")
+        getattr(lib, name)(s.ctypes.data, b.ctypes.data, s.size, out.ctypes.data)
+    else:
+        getattr(lib, name)(s.ctypes.data, s.size, out.ctypes.data)
+    _check_void(name)
+    return out[0]
+
+
+def arm_absmax(kind, src):
+    """(value, index) of the maximum of |x| (saturating), the first index on a tie, through arm_absmax_*."""
+    return _arm_search("absmax", kind, src)
+
+
+def arm_absmin(kind, src):
+    """(value, index) of the minimum of |x| (saturating), the first index on a tie, through arm_absmin_*."""
+    return _arm_search("absmin", kind, src)
+
+
+def arm_sqrt_q15(x):
+    """(status, root) of one q15 word through arm_sqrt_q15: a negative x gives (ARM_MATH_ARGUMENT_ERROR, 0)."""
+    out = np.zeros(1, dtype=np.int16)
+    st = lib.arm_sqrt_q15(int(x), out.ctypes.data)
+    return st, out[0]
+
+
+def arm_cmplx_mag_fast_q15(src):
+    """arm_sqrt_q15((re*re + im*im) >> 17) of every interleaved (re, im) pair through arm_cmplx_mag_fast_q15."""
+    s = _cm_src("q15", src)
+    n = s.size // 2
+    d = np.zeros(n, dtype=np.int16)
+    lib.arm_cmplx_mag_fast_q15(s.ctypes.data, d.ctypes.data, n)
+    _check_void("arm_cmplx_mag_fast_q15")
+    return d
+
+
+def cmplx_mag_fast_batch(src, dst, stream=None):
+    """dst[i] [N] = arm_cmplx_mag_fast_q15 of src[i] [2N] (int16 device tensors); dst must not overlap src."""
+    _solve_call("arm_cmplx_mag_fast_q15_batch", _cm_ptr(src), _cm_ptr(dst), src.shape[-1] // 2, src.shape[0],
+                _stream_ptr(stream))
+
+
+def _stat_batch(op, src, result, stream):
+    kind = _mat_kind(src)
+    _solve_call(f"arm_{op}_{kind}_batch", _cm_ptr(src), src.shape[-1], _cm_ptr(result), src.shape[0],
+                _stream_ptr(stream))
+
+
+def mean_batch(src, result, stream=None):
+    """result[i] = arm_mean_* of src[i] [N] for contiguous device tensors src [batch, N] (float32, int32, int16,
+    int8) and result [batch] of the same type."""
+    _stat_batch("mean", src, result, stream)
+
+
+def power_batch(src, result, stream=None):
+    """result[i] = arm_power_* of src[i] [N]; result is float32, int64 (q31, q15) or int32 (q7)."""
+    _stat_batch("power", src, result, stream)
+
+
+def rms_batch(src, result, stream=None):
+    """result[i] = arm_rms_* of src[i] [N] (float32, int32, int16)."""
+    _stat_batch("rms", src, result, stream)
+
+
+def var_batch(src, result, stream=None):
+    """result[i] = arm_var_* of src[i] [N] (float32, int32, int16): the unbiased variance."""
+    _stat_batch("var", src, result, stream)
+
+
+def std_batch(src, result, stream=None):
+    """result[i] = arm_std_* of src[i] [N] (float32, int32, int16)."""
+    _stat_batch("std", src, result, stream)
+
+
+def accumulate_batch(src, result, stream=None):
+    """result[i] = arm_accumulate_f32 of src[i] [N]: the ordered float32 sum."""
+    _stat_batch("accumulate", src, result, stream)
+
+
+def mse_batch(a, b, result, stream=None):
+    """result[i] = arm_mse_* of a[i] and b[i] [N] (float32, int32, int16, int8)."""
+    kind = _mat_kind(a)
+    _solve_call(f"arm_mse_{kind}_batch", _cm_ptr(a), _cm_ptr(b), a.shape[-1], _cm_ptr(result), a.shape[0],
+                _stream_ptr(stream))
+
+
+def absmax_batch(src, result, index, stream=None):
+    """result[i], index[i] = the maximum of |src[i]| and its first index (arm_absmax_*_batch)."""
+    _search_batch("absmax", src, result, index, stream)
+
+
+def absmin_batch(src, result, index, stream=None):
+    """result[i], index[i] = the minimum of |src[i]| and its first index (arm_absmin_*_batch)."""
+    _search_batch("absmin", src, result, index, stream)
+
+
+def max_no_idx_batch(src, result, stream=None):
+    """result[i] = arm_max_no_idx_* of src[i] [N]."""
+    _stat_batch("max_no_idx", src, result, stream)
+
+
+def min_no_idx_batch(src, result, stream=None):
+    """result[i] = arm_min_no_idx_* of src[i] [N]."""
+    _stat_batch("min_no_idx", src, result, stream)
+
+
+def absmax_no_idx_batch(src, result, stream=None):
+    """result[i] = arm_absmax_no_idx_* of src[i] [N]."""
+    _stat_batch("absmax_no_idx", src, result, stream)
+
+
+def absmin_no_idx_batch(src, result, stream=None):
+    """result[i] = arm_absmin_no_idx_* of src[i] [N]."""
+    _stat_batch("absmin_no_idx", src, result, stream)
 
 
 def mat_mult_batch(a, b, c, stream=None, fast=False):

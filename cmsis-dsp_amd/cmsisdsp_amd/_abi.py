@@ -397,6 +397,25 @@ for _t in ("f32", "q31", "q15", "q7"):
         CMPLX_MATH[f"arm_{_n}_{_t}"] = (None, [_vp, _u32, _vp, _vp])
         CMPLX_MATH[f"arm_{_n}_{_t}_batch"] = (C.c_int, [_vp, _u32, _vp, _vp, _u32, _vp])
 
+# Statistics: 46 drop-ins (the reference's signatures, all void), arm_cmplx_mag_fast_q15 and their _batch forms, and
+# the scalar arm_sqrt_q15.  The product only (tests/golden/statistics.npz holds the reference's outputs).
+STATISTICS = {}
+STAT_TYPES = ("f32", "q31", "q15", "q7")
+for _t in STAT_TYPES:
+    _one = [("mean", 0), ("power", 0), ("max_no_idx", 0), ("min_no_idx", 0), ("absmax_no_idx", 0),
+            ("absmin_no_idx", 0), ("absmax", 1), ("absmin", 1), ("mse", 2)]
+    if _t != "q7":
+        _one += [("rms", 0), ("var", 0), ("std", 0)]
+    if _t == "f32":
+        _one += [("accumulate", 0)]
+    for _n, _k in _one:
+        _a = ([_vp, _u32, _vp], [_vp, _u32, _vp, _vp], [_vp, _vp, _u32, _vp])[_k]
+        STATISTICS[f"arm_{_n}_{_t}"] = (None, _a)
+        STATISTICS[f"arm_{_n}_{_t}_batch"] = (C.c_int, _a + [_u32, _vp])
+STATISTICS["arm_cmplx_mag_fast_q15"] = (None, [_vp, _vp, _u32])
+STATISTICS["arm_cmplx_mag_fast_q15_batch"] = (C.c_int, [_vp, _vp, _u32, _u32, _vp])
+STATISTICS["arm_sqrt_q15"] = (C.c_int, [C.c_int16, _vp])
+
 # per-length MFCC init functions (the product and the reference build; the oracle has the
 # generic init only)
 MFCC_LEN = {f"arm_mfcc_init_{n}_f32": (C.c_int, [P(arm_mfcc_instance_f32), C.c_uint32, C.c_uint32, C.c_void_p,

@@ -1530,7 +1530,7 @@ template <typename T>
 arm_status cmplx_ew(int op, const T* a, const T* b, T* d, uint32_t n, bool sync, uint32_t batch, void* stream,
                     const char* what) {
   const int wb = op == kCmMultCmplx ? 2 : op == kCmMultReal ? 1 : 0;
-  const int wd = op == kCmMag || op == kCmMagSquared ? 1 : 2;
+  const int wd = op == kCmMag || op == kCmMagSquared || op == kCmMagFast ? 1 : 2;
   if (sync && (!a || (wb && !b) || !d)) return cm_null(true, what);
   if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
   if (!a || (wb && !b) || !d) return ARM_MATH_ARGUMENT_ERROR;
@@ -1594,6 +1594,59 @@ arm_status cm_search(bool max, const T* src, uint32_t n, T* result, uint32_t* in
   SolveBuf bufs[3] = {{const_cast<T*>(src), sb, true, false}, {result, rb, false, true}, {index, ib, false, true}};
   return mat_staged_sync(bufs, 3, what, [&](hipStream_t st) {
     return run((const T*)bufs[0].d, (T*)bufs[1].d, (uint32_t*)bufs[2].d, st);
+  });
+}
+
+// ---- statistics (statistics.hip) ------------------------------------------------------------------
+// The sums and level measures of statistics_functions.h (op: kStMean ... kStAccumulate; b: the second source of
+// kStMse) and the abs / no-index searches.  sync and the overlap rule as above.  blockSize == 0: what the
+// reference's empty sums give is stored (power, accumulate: 0; mean_f32, mse_f32: 0 / 0; rms_f32: +0.0; var, std:
+// 0; max / min_no_idx_f32: their start value); where it would divide an integer by zero or read pSrc[0] the call
+// is refused as cm_search refuses it.
+template <typename T, typename R>
+arm_status st_sum(int op, const T* a, const T* b, uint32_t n, R* result, bool sync, uint32_t batch, void* stream,
+                  const char* what) {
+  constexpr bool f32 = std::is_same<T, float>::value;
+  const bool two = op == kStMse;
+  if (sync && (!a || (two && !b) || !result)) return cm_null(true, what);
+  if (batch == 0) return ARM_MATH_SUCCESS;
+  if (n == 0 && !f32 && (op == kStMean || op == kStRms || op == kStMse)) return cm_null(sync, what);
+  if (!a || (two && !b) || !result) return ARM_MATH_ARGUMENT_ERROR;
+  const size_t sb = sizeof(T) * n * batch, rb = sizeof(R) * batch;
+  const bool lut = std::is_same<T, int32_t>::value && (op == kStRms || op == kStStd);
+  auto run = [&](const T* da, const T* db, R* dr, hipStream_t st) -> hipError_t {
+    if (cm_overlaps(dr, rb, da, sb, false) || (two && cm_overlaps(dr, rb, db, sb, false))) return hipErrorInvalidValue;
+    const int32_t* dl = lut ? (const int32_t*)device_table(sqrt_initial_lut_q31, sizeof(int32_t) * 32) : nullptr;
+    if (lut && !dl) return hipErrorOutOfMemory;
+    return stat_sum_launch<T, R>(op, da, db, n, dr, batch, dl, st);
+  };
+  if (!sync) return batch_status(run(a, b, result, (hipStream_t)stream), what);
+  SolveBuf bufs[3] = {{const_cast<T*>(a), sb, n != 0, false}, {result, rb, false, true},
+                      {const_cast<T*>(b), sb, n != 0, false}};
+  return mat_staged_sync(bufs, two ? 3 : 2, what, [&](hipStream_t st) {
+    return run((const T*)bufs[0].d, two ? (const T*)bufs[2].d : nullptr, (R*)bufs[1].d, st);
+  });
+}
+
+// idx false: the _no_idx forms (index unused).
+template <typename T>
+arm_status st_search(bool max, bool abs, bool idx, const T* src, uint32_t n, T* result, uint32_t* index, bool sync,
+                     uint32_t batch, void* stream, const char* what) {
+  if (sync && (!src || !result || (idx && !index))) return cm_null(true, what);
+  if (batch == 0) return ARM_MATH_SUCCESS;
+  const bool fromStart = std::is_same<T, float>::value && !abs && !idx;   // max / min_no_idx_f32 read no pSrc[0]
+  if (n == 0 && !fromStart) return cm_null(sync, what);
+  if (!src || !result || (idx && !index)) return ARM_MATH_ARGUMENT_ERROR;
+  const size_t sb = sizeof(T) * n * batch, rb = sizeof(T) * batch, ib = idx ? sizeof(uint32_t) * batch : 0;
+  auto run = [&](const T* ds, T* dr, uint32_t* di, hipStream_t st) -> hipError_t {
+    if (cm_overlaps(dr, rb, ds, sb, false) || cm_overlaps(di, ib, ds, sb, false) || cm_overlaps(dr, rb, di, ib, false))
+      return hipErrorInvalidValue;
+    return stat_search_launch<T>(max, abs, ds, n, dr, di, batch, st);
+  };
+  if (!sync) return batch_status(run(src, result, idx ? index : nullptr, (hipStream_t)stream), what);
+  SolveBuf bufs[3] = {{const_cast<T*>(src), sb, n != 0, false}, {result, rb, false, true}, {index, ib, false, true}};
+  return mat_staged_sync(bufs, idx ? 3 : 2, what, [&](hipStream_t st) {
+    return run((const T*)bufs[0].d, (T*)bufs[1].d, idx ? (uint32_t*)bufs[2].d : nullptr, st);
   });
 }
 }  // namespace
@@ -2167,6 +2220,101 @@ MI355X_SEARCH_TYPE(q15, q15_t, int16_t)
 MI355X_SEARCH_TYPE(q7, q7_t, int8_t)
 #undef MI355X_SEARCH_TYPE
 #undef MI355X_SEARCH
+
+// arm_cmplx_mag_fast_q15: one more operation of the element-wise kernel
+void arm_cmplx_mag_fast_q15(const q15_t* pSrc, q15_t* pDst, uint32_t numSamples) {
+  cmplx_ew<int16_t>(kCmMagFast, pSrc, (const int16_t*)nullptr, pDst, numSamples, true, 1, nullptr,
+                    "arm_cmplx_mag_fast_q15");
+}
+arm_status arm_cmplx_mag_fast_q15_batch(const q15_t* d_src, q15_t* d_dst, uint32_t numSamples, uint32_t batch,
+                                        void* stream) {
+  return cmplx_ew<int16_t>(kCmMagFast, d_src, (const int16_t*)nullptr, d_dst, numSamples, false, batch, stream,
+                           "arm_cmplx_mag_fast_q15_batch");
+}
+// the scalar of fast_math_functions.h, computed on the host
+arm_status arm_sqrt_q15(q15_t in, q15_t* pOut) {
+  if (!pOut) return ARM_MATH_ARGUMENT_ERROR;
+  *pOut = sqrt_q15_host(in);
+  return in >= 0 ? ARM_MATH_SUCCESS : ARM_MATH_ARGUMENT_ERROR;
+}
+
+// ---- statistics; st_sum and st_search precede the C block ----
+#define MI355X_STAT_1(NAME, OP, SUF, T, CT, R, CR)                                                               \
+  void arm_##NAME##_##SUF(const T* pSrc, uint32_t blockSize, R* pResult) {                                       \
+    st_sum<CT, CR>(OP, (const CT*)pSrc, (const CT*)nullptr, blockSize, (CR*)pResult, true, 1, nullptr,           \
+                   "arm_" #NAME "_" #SUF);                                                                       \
+  }                                                                                                              \
+  arm_status arm_##NAME##_##SUF##_batch(const T* d_src, uint32_t blockSize, R* d_result, uint32_t batch,         \
+                                        void* stream) {                                                          \
+    return st_sum<CT, CR>(OP, (const CT*)d_src, (const CT*)nullptr, blockSize, (CR*)d_result, false, batch,      \
+                          stream, "arm_" #NAME "_" #SUF "_batch");                                               \
+  }
+#define MI355X_STAT_MSE(SUF, T, CT)                                                                              \
+  void arm_mse_##SUF(const T* pSrcA, const T* pSrcB, uint32_t blockSize, T* pResult) {                           \
+    st_sum<CT, CT>(kStMse, (const CT*)pSrcA, (const CT*)pSrcB, blockSize, (CT*)pResult, true, 1, nullptr,        \
+                   "arm_mse_" #SUF);                                                                             \
+  }                                                                                                              \
+  arm_status arm_mse_##SUF##_batch(const T* d_a, const T* d_b, uint32_t blockSize, T* d_result, uint32_t batch,  \
+                                   void* stream) {                                                               \
+    return st_sum<CT, CT>(kStMse, (const CT*)d_a, (const CT*)d_b, blockSize, (CT*)d_result, false, batch,        \
+                          stream, "arm_mse_" #SUF "_batch");                                                     \
+  }
+#define MI355X_STAT_LEVELS(SUF, T, CT)               \
+  MI355X_STAT_1(rms, kStRms, SUF, T, CT, T, CT)      \
+  MI355X_STAT_1(var, kStVar, SUF, T, CT, T, CT)      \
+  MI355X_STAT_1(std, kStStd, SUF, T, CT, T, CT)
+#define MI355X_STAT_TYPE(SUF, T, CT, PR, CPR)        \
+  MI355X_STAT_1(mean, kStMean, SUF, T, CT, T, CT)    \
+  MI355X_STAT_1(power, kStPower, SUF, T, CT, PR, CPR) \
+  MI355X_STAT_MSE(SUF, T, CT)
+MI355X_STAT_TYPE(f32, float32_t, float, float32_t, float)
+MI355X_STAT_TYPE(q31, q31_t, int32_t, q63_t, int64_t)
+MI355X_STAT_TYPE(q15, q15_t, int16_t, q63_t, int64_t)
+MI355X_STAT_TYPE(q7, q7_t, int8_t, q31_t, int32_t)
+MI355X_STAT_LEVELS(f32, float32_t, float)
+MI355X_STAT_LEVELS(q31, q31_t, int32_t)
+MI355X_STAT_LEVELS(q15, q15_t, int16_t)
+MI355X_STAT_1(accumulate, kStAccumulate, f32, float32_t, float, float32_t, float)
+#undef MI355X_STAT_TYPE
+#undef MI355X_STAT_LEVELS
+#undef MI355X_STAT_MSE
+#undef MI355X_STAT_1
+
+// abs searches with the index, and the four searches without it
+#define MI355X_STAT_SEARCH(NAME, MAX, ABS, SUF, T, CT)                                                           \
+  void arm_##NAME##_##SUF(const T* pSrc, uint32_t blockSize, T* pResult, uint32_t* pIndex) {                     \
+    st_search<CT>(MAX, ABS, true, (const CT*)pSrc, blockSize, (CT*)pResult, pIndex, true, 1, nullptr,            \
+                  "arm_" #NAME "_" #SUF);                                                                        \
+  }                                                                                                              \
+  arm_status arm_##NAME##_##SUF##_batch(const T* d_src, uint32_t blockSize, T* d_result, uint32_t* d_index,      \
+                                        uint32_t batch, void* stream) {                                          \
+    return st_search<CT>(MAX, ABS, true, (const CT*)d_src, blockSize, (CT*)d_result, d_index, false, batch,      \
+                         stream, "arm_" #NAME "_" #SUF "_batch");                                                \
+  }
+#define MI355X_STAT_NO_IDX(NAME, MAX, ABS, SUF, T, CT)                                                           \
+  void arm_##NAME##_no_idx_##SUF(const T* pSrc, uint32_t blockSize, T* pResult) {                                \
+    st_search<CT>(MAX, ABS, false, (const CT*)pSrc, blockSize, (CT*)pResult, nullptr, true, 1, nullptr,          \
+                  "arm_" #NAME "_no_idx_" #SUF);                                                                 \
+  }                                                                                                              \
+  arm_status arm_##NAME##_no_idx_##SUF##_batch(const T* d_src, uint32_t blockSize, T* d_result, uint32_t batch,  \
+                                               void* stream) {                                                   \
+    return st_search<CT>(MAX, ABS, false, (const CT*)d_src, blockSize, (CT*)d_result, nullptr, false, batch,     \
+                         stream, "arm_" #NAME "_no_idx_" #SUF "_batch");                                         \
+  }
+#define MI355X_STAT_SEARCH_TYPE(SUF, T, CT)             \
+  MI355X_STAT_SEARCH(absmax, true, true, SUF, T, CT)    \
+  MI355X_STAT_SEARCH(absmin, false, true, SUF, T, CT)   \
+  MI355X_STAT_NO_IDX(max, true, false, SUF, T, CT)      \
+  MI355X_STAT_NO_IDX(min, false, false, SUF, T, CT)     \
+  MI355X_STAT_NO_IDX(absmax, true, true, SUF, T, CT)    \
+  MI355X_STAT_NO_IDX(absmin, false, true, SUF, T, CT)
+MI355X_STAT_SEARCH_TYPE(f32, float32_t, float)
+MI355X_STAT_SEARCH_TYPE(q31, q31_t, int32_t)
+MI355X_STAT_SEARCH_TYPE(q15, q15_t, int16_t)
+MI355X_STAT_SEARCH_TYPE(q7, q7_t, int8_t)
+#undef MI355X_STAT_SEARCH_TYPE
+#undef MI355X_STAT_NO_IDX
+#undef MI355X_STAT_SEARCH
 
 // ---- convolution ------------------------------------------------------------------
 #define MI355X_CONV_FULL(NAME, T, CT, OP, VAR)                                                                  \

@@ -11,9 +11,11 @@
 //                  lane reads its samples before it writes them, so dst may be a source exactly where both have
 //                  the same words per sample (conj, mult_cmplx, mult_real).  The q31 / q15 magnitudes read
 //                  sqrt_initial_lut_q31 from LDS (32 words staged per workgroup): no lane shuffle, so the ragged
-//                  loops may diverge.
-//   integer dot    lanes-per-item = the power of two that leaves a lane about two loads of its item (1 .. 64, or
-//   max / min      the whole workgroup); short items are packed kBlock / lanes-per-item to a workgroup.  16-B
+//                  loops may diverge.  arm_cmplx_mag_fast_q15 is one more operation of this kernel: arm_sqrt_q15 of
+//                  (re*re + im*im) >> 17, its 16 start words in the same LDS array.
+//   integer dot    (mapping and search kernel: reduce_lanes.hpp, shared with statistics.hip)
+//   max / min      lanes-per-item = the power of two that leaves a lane about two loads of its item (1 .. 64, or
+//                  the whole workgroup); short items are packed kBlock / lanes-per-item to a workgroup.  16-B
 //                  loads when every item starts 16-B aligned, one element per load otherwise.  The lanes' partial
 //                  results meet in a butterfly of lane shuffles (and four LDS words for a whole workgroup).
 //                  Integer sums are associative.  max / min combine (value, index) pairs: the better value wins,
@@ -29,35 +31,12 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "mfcc_fixed_ops.hpp"
+#include "reduce_lanes.hpp"
 
 #pragma clang fp contract(off)
 
 namespace mi355x {
 namespace {
-
-// (int32_t)(((int64_t)a * b) >> s) for 0 <= s <= 31: bits s .. s + 31 of the signed product, taken from its two
-// halves with one v_alignbit.  Written out because the compiler builds the 64-bit shifts of arm_sqrt_q31 from
-// about twice as many instructions, and the q15 magnitude is bound by instruction issue.
-__device__ __forceinline__ int32_t mulshr(int32_t a, int32_t b, int s) {
-  return (int32_t)__builtin_amdgcn_alignbit((uint32_t)mulhi(a, b), (uint32_t)a * (uint32_t)b, (uint32_t)s);
-}
-
-// arm_sqrt_q31.c:55-125 with the start value read from lut (LDS): Newton on 1 / sqrt, 3 iterations.
-__device__ __forceinline__ int32_t cm_sqrt_q31(int32_t in, const int32_t* lut) {
-  // branch-free: in <= 0 runs the same arithmetic on a masked table index and selects 0 at the end
-  const int e = ((int)mq_clz((uint32_t)in) - 1) & 30;       // signBits1 rounded down to even
-  const int32_t number = wshl(in, e);
-  int32_t v = lut[((number >> 26) - (0x20000000 >> 26)) & 31];
-#pragma unroll
-  for (int it = 0; it < 3; ++it) {
-    int32_t t = mulshr(v, v, 28);
-    t = mulshr(number, t, 31);
-    t = wsub(0x30000000, t);
-    v = mulshr(v, t, 29);
-  }
-  v = mulshr(number, v, 28);
-  return in > 0 ? v >> (e >> 1) : 0;
-}
 
 // ---- element-wise ------------------------------------------------------------------------------------------
 // One complex sample: a = (a[0], a[1]); b the second operand's sample (mult_cmplx: 2 words, mult_real: 1 word).
@@ -103,6 +82,8 @@ __device__ __forceinline__ void cm_sample(const T* a, const T* b, T* d, const in
     if constexpr (OP == kCmMag) {
       const uint32_t s = ((uint32_t)(x * x) + (uint32_t)(y * y)) >> 1;
       d[0] = (T)(cm_sqrt_q31((int32_t)s, lut) >> 16);
+    } else if constexpr (OP == kCmMagFast) {               // arm_cmplx_mag_fast_q15: lut holds arm_sqrt_q15's table
+      d[0] = (T)cm_sqrt_q15((int16_t)(((int64_t)(x * x) + (int64_t)(y * y)) >> 17), lut);
     } else if constexpr (OP == kCmMagSquared) {
       d[0] = (T)(((int64_t)(x * x) + (int64_t)(y * y)) >> 17);
     } else if constexpr (OP == kCmConj) {
@@ -128,7 +109,7 @@ constexpr int kCmUnroll = 4;   // units per lane and tile
 template <int OP> struct CmShape {
   static constexpr int WA = 2;
   static constexpr int WB = OP == kCmMultCmplx ? 2 : OP == kCmMultReal ? 1 : 0;
-  static constexpr int WD = (OP == kCmMag || OP == kCmMagSquared) ? 1 : 2;
+  static constexpr int WD = (OP == kCmMag || OP == kCmMagSquared || OP == kCmMagFast) ? 1 : 2;
 };
 
 // count: complex samples of the whole batch.  vec: a, b and d are 16-B aligned.
@@ -145,6 +126,10 @@ __global__ __launch_bounds__(kBlock) void cmplx_ew_kernel(const T* a, const T* b
   __shared__ int32_t slut[32];
   if constexpr (kLut) {
     if (threadIdx.x < 32) slut[threadIdx.x] = lut[threadIdx.x];
+    __syncthreads();
+  }
+  if constexpr (OP == kCmMagFast) {
+    if (threadIdx.x < 16) slut[threadIdx.x] = kSqrtLutQ15[threadIdx.x];
     __syncthreads();
   }
   const size_t units = vec ? count / SU : 0;
@@ -212,81 +197,7 @@ hipError_t ew_launch(const T* a, const T* b, T* d, size_t count, const int32_t* 
 }
 
 // ---- lanes-per-item reductions: the integer dot products, max / min --------------------------------------
-// An item of `chunks` loads gets lpi lanes: the power of two that leaves a lane about kRedLoads loads, at most a
-// wave; items of more than kRedWaveMax loads get the whole workgroup.
-constexpr int kRedLoads = 2;
-constexpr uint32_t kRedWaveMax = 64 * 8;
-inline int red_lpi_log(uint64_t chunks) {
-  if (chunks > kRedWaveMax) return 8;
-  int l = 0;
-  while (l < 6 && ((uint64_t)kRedLoads << l) < chunks) ++l;
-  return l;
-}
-
-template <typename T> struct Best {
-  T v;
-  uint32_t i;
-  bool has;
-};
-
-template <bool MAX, typename T>
-__device__ __forceinline__ void best_take(Best<T>& s, T x, uint32_t i) {
-  // a NaN fails x == x and never enters; the scan runs with i ascending, so a tie keeps the earlier index
-  if (x == x && (!s.has || (MAX ? s.v < x : s.v > x))) { s.v = x; s.i = i; s.has = true; }
-}
-template <bool MAX, typename T>
-__device__ __forceinline__ void best_merge(Best<T>& s, const Best<T>& o) {
-  if (o.has && (!s.has || (MAX ? s.v < o.v : s.v > o.v) || (s.v == o.v && o.i < s.i))) s = o;
-}
-template <typename T>
-__device__ __forceinline__ Best<T> best_shfl_xor(const Best<T>& s, int m) {
-  using W = typename std::conditional<std::is_same<T, float>::value, float, int>::type;
-  Best<T> o;
-  o.v = (T)__shfl_xor((W)s.v, m, 64);
-  o.i = (uint32_t)__shfl_xor((int)s.i, m, 64);
-  o.has = __shfl_xor((int)s.has, m, 64) != 0;
-  return o;
-}
-
-// wide: every item starts 16-B aligned and holds a whole number of 16-B packs.
-template <bool MAX, typename T>
-__global__ __launch_bounds__(kBlock) void search_kernel(const T* src, uint32_t n, T* result, uint32_t* index,
-                                                        uint32_t batch, int lpiLog, bool wide) {
-  constexpr int V = 16 / sizeof(T);
-  struct alignas(16) Pack { T v[V]; };
-  __shared__ Best<T> part[kBlock / 64];
-  const uint32_t lpi = 1u << lpiLog, ipw = kBlock >> lpiLog;
-  const uint32_t li = threadIdx.x >> lpiLog, l = threadIdx.x & (lpi - 1);
-  const uint32_t item = blockIdx.x * ipw + li;
-  const bool live = item < batch;
-  const T* s = src + (size_t)(live ? item : 0) * n;
-  Best<T> b{(T)0, 0u, false};
-  if (live) {
-    if (wide) {
-      for (uint64_t c = l; c < n / V; c += lpi) {          // 64-bit: c + lpi may pass 2^32
-        const Pack p = ((const Pack*)s)[c];
-#pragma unroll
-        for (int j = 0; j < V; ++j) best_take<MAX, T>(b, p.v[j], (uint32_t)(c * V + j));
-      }
-    } else {
-      for (uint64_t k = l; k < n; k += lpi) best_take<MAX, T>(b, s[k], (uint32_t)k);
-    }
-  }
-  const int waveLanes = lpiLog < 6 ? lpiLog : 6;
-  for (int m = 1; m < (1 << waveLanes); m <<= 1) best_merge<MAX, T>(b, best_shfl_xor(b, m));
-  if (lpiLog > 6) {            // the whole workgroup on one item
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = b;
-    __syncthreads();
-    if (threadIdx.x == 0)
-      for (int w = 1; w < kBlock / 64; ++w) best_merge<MAX, T>(b, part[w]);
-  }
-  if (live && l == 0) {
-    const T first = s[0];
-    const bool pin = !(first == first) || !b.has;      // word 0 a NaN: it is never replaced
-    result[item] = pin ? first : b.v;
-    index[item] = pin ? 0u : b.i;
-  }
-}
+// The mapping (red_lpi_log) and the search kernel: reduce_lanes.hpp.
 
 // Integer complex dot product of one sample into (re, im).  q31: each product >> 14, sums mod 2^64; q15: exact.
 template <typename T>
@@ -439,6 +350,9 @@ hipError_t cmplx_ew_launch(int op, const T* a, const T* b, T* d, size_t count, c
     case kCmConj: return ew_launch<kCmConj, T>(a, b, d, count, lut, st);
     case kCmMultCmplx: return ew_launch<kCmMultCmplx, T>(a, b, d, count, lut, st);
     case kCmMultReal: return ew_launch<kCmMultReal, T>(a, b, d, count, lut, st);
+    case kCmMagFast:
+      if constexpr (std::is_same<T, int16_t>::value) return ew_launch<kCmMagFast, T>(a, b, d, count, lut, st);
+      break;
   }
   return hipErrorInvalidValue;
 }
@@ -453,19 +367,8 @@ template <typename T>
 hipError_t search_launch(bool max, const T* src, uint32_t n, T* result, uint32_t* index, uint32_t batch,
                          hipStream_t st) {
   if (n == 0 || batch == 0) return hipSuccess;
-  constexpr uint32_t V = 16 / sizeof(T);
-  const bool wide = (((uintptr_t)src | ((size_t)n * sizeof(T))) & 15) == 0;
-  const int lpiLog = red_lpi_log(wide ? n / V : n);
-  const uint32_t ipw = kBlock >> lpiLog;
-  const uint64_t grid = ((uint64_t)batch + ipw - 1) / ipw;
-  if (grid > 0x7fffffffull) return hipErrorInvalidValue;
-  if (max)
-    hipLaunchKernelGGL((search_kernel<true, T>), dim3((uint32_t)grid), dim3(kBlock), 0, st, src, n, result, index,
-                       batch, lpiLog, wide);
-  else
-    hipLaunchKernelGGL((search_kernel<false, T>), dim3((uint32_t)grid), dim3(kBlock), 0, st, src, n, result, index,
-                       batch, lpiLog, wide);
-  return hipGetLastError();
+  return max ? search_run<true, T, MapNone, false>(src, n, result, index, batch, st)
+             : search_run<false, T, MapNone, false>(src, n, result, index, batch, st);
 }
 template hipError_t search_launch<float>(bool, const float*, uint32_t, float*, uint32_t*, uint32_t, hipStream_t);
 template hipError_t search_launch<int32_t>(bool, const int32_t*, uint32_t, int32_t*, uint32_t*, uint32_t, hipStream_t);

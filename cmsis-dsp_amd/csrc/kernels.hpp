@@ -299,8 +299,9 @@ hipError_t mat_vec_mult_launch(int rows, int cols, const T* mat, size_t matStrid
 // cmplx_ew_launch: `count` complex samples (the whole batch as one flat array).  kCmMag / kCmMagSquared write one
 // word per sample, the others two; b is the second complex vector (kCmMultCmplx), the real vector (kCmMultReal)
 // or unused.  d may be a (or b) exactly for kCmConj / kCmMultCmplx / kCmMultReal; no other overlap.  lut: the
-// device copy of sqrt_initial_lut_q31 (read by the q31 / q15 kCmMag only).
-enum : int { kCmMag = 0, kCmMagSquared = 1, kCmConj = 2, kCmMultCmplx = 3, kCmMultReal = 4 };
+// device copy of sqrt_initial_lut_q31 (read by the q31 / q15 kCmMag only).  kCmMagFast (int16_t only) is
+// arm_cmplx_mag_fast_q15: one word per sample, no lut.
+enum : int { kCmMag = 0, kCmMagSquared = 1, kCmConj = 2, kCmMultCmplx = 3, kCmMultReal = 4, kCmMagFast = 5 };
 template <typename T>
 hipError_t cmplx_ew_launch(int op, const T* a, const T* b, T* d, size_t count, const int32_t* lut, hipStream_t st);
 // re[i], im[i] = the complex dot product of a[i] and b_i (n samples each), b_i = b + i * bStride samples (0: one
@@ -314,5 +315,24 @@ hipError_t cmplx_dot_launch(const T* a, const T* b, size_t bStride, uint32_t n, 
 template <typename T>
 hipError_t search_launch(bool max, const T* src, uint32_t n, T* result, uint32_t* index, uint32_t batch,
                          hipStream_t st);
+
+// The statistics functions, bit-exact with the reference's scalar branches (statistics.hip).  One result word per
+// item of n contiguous words; items n words apart.
+// stat_sum_launch: T float, int32_t (q31), int16_t (q15), int8_t (q7); R the reference's result type (as T, but
+// power: float, int64_t, int64_t, int32_t).  b: the second source of kStMse, otherwise unused.  lut: the device copy
+// of sqrt_initial_lut_q31 (read by the q31 kStRms / kStStd only).  n == 0 stores what the empty sums give (the
+// caller refuses the integer forms that would divide by zero).  The float sums are ordered chains.
+enum : int { kStMean = 0, kStPower = 1, kStRms = 2, kStVar = 3, kStStd = 4, kStMse = 5, kStAccumulate = 6 };
+template <typename T, typename R>
+hipError_t stat_sum_launch(int op, const T* a, const T* b, uint32_t n, R* result, uint32_t batch, const int32_t* lut,
+                           hipStream_t st);
+// arm_{max,min,absmax,absmin}[_no_idx]: abs maps every element to (x > 0) ? x : -x (saturating) first; index null:
+// the _no_idx forms, which for float without abs start from -FLT_MAX / FLT_MAX (and accept n == 0) instead of
+// element 0.  Otherwise n > 0.
+template <typename T>
+hipError_t stat_search_launch(bool max, bool abs, const T* src, uint32_t n, T* result, uint32_t* index, uint32_t batch,
+                              hipStream_t st);
+// arm_sqrt_q15 on the host (the scalar drop-in): 0 for in <= 0.
+int16_t sqrt_q15_host(int16_t in);
 
 }  // namespace mi355x

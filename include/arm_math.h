@@ -1042,7 +1042,7 @@ void arm_mat_vec_mult_q7(const arm_matrix_instance_q7 *pSrcMat, const q7_t *pVec
  *                products, >> 6, stored as q31_t (8.24).  numSamples == 0 stores zeros.
  *   max / min    the value and the first index that holds it (a strict comparison replaces the running result);
  *                +0.0 and -0.0 tie; a NaN after pSrc[0] is never selected and a NaN in pSrc[0] never replaced.
- * Left out: arm_cmplx_mag_fast_q15, the f16 / f64 forms, the _no_idx and absmax / absmin variants.
+ * Left out: the f16 / f64 forms (arm_cmplx_mag_fast_q15, the _no_idx and absmax / absmin searches: below).
  * A null pointer, and blockSize == 0 in max / min (the reference reads pSrc[0]): nothing is written and
  * arm_mi355x_last_error() is set.  numSamples == 0 writes nothing (dot_prod: zeros).
  * Aliasing.  pDst may equal a source exactly for conj (pSrc), mult_cmplx (pSrcA or pSrcB) and mult_real
@@ -1070,6 +1070,72 @@ void arm_min_f32(const float32_t *pSrc, uint32_t blockSize, float32_t *pResult, 
 void arm_min_q31(const q31_t *pSrc, uint32_t blockSize, q31_t *pResult, uint32_t *pIndex);
 void arm_min_q15(const q15_t *pSrc, uint32_t blockSize, q15_t *pResult, uint32_t *pIndex);
 void arm_min_q7(const q7_t *pSrc, uint32_t blockSize, q7_t *pResult, uint32_t *pIndex);
+
+/* The level measures and the remaining searches of statistics_functions.h, bit-exact with the reference's scalar
+ * branches (built with ARM_MATH_LOOPUNROLL, no ARM_MATH_DSP), arm_sqrt_q15 of fast_math_functions.h and
+ * arm_cmplx_mag_fast_q15.  Host or device pointers, synchronous; one result word.
+ *   f32          every sum is one chain in element order from 0.0f, each product rounded before its add; divisions
+ *                and square roots correctly rounded.  mean: sum / (float)blockSize.  power: the sum of x*x.  rms:
+ *                arm_sqrt_f32(power / (float)blockSize), which stores +0.0 for a NaN.  mse: the sum of (a-b)*(a-b) over
+ *                (float)blockSize.  var: the mean's chain first, then the chain of (x-mean)*(x-mean) over
+ *                ((float)blockSize - 1.0f); std: arm_sqrt_f32(var).  accumulate: the sum.
+ *   q31          mean: (q31_t)(sum / blockSize), truncated toward zero.  power: the 64-bit sum of x*x >> 14 (16.48).
+ *                rms: arm_sqrt_q31(clip((sum of x*x, unsigned, / blockSize) >> 31)).  mse: halved inputs, a saturating
+ *                difference, d*d >> 14 summed, (q31_t)((sum / blockSize) >> 15).  var: in = x >> 8;
+ *                (sumOfSquares / (blockSize-1) - sum*sum / (uint32_t)(blockSize*(blockSize-1))) >> 15; std: its
+ *                arm_sqrt_q31.
+ *   q15          mean: a 32-bit sum / blockSize.  power: the 64-bit sum of x*x (34.30).  rms: arm_sqrt_q15(sat16((sum /
+ *                blockSize) >> 15)).  mse: halved inputs, saturating difference, sat16((q31_t)(sum / blockSize) >> 13).
+ *                var: a 32-bit sum and 64-bit squares, both quotients cast to q31_t, the difference >> 15; std:
+ *                arm_sqrt_q15 of its saturation to 16 bits.  The divisor blockSize*(blockSize-1) is a uint32_t product
+ *                and wraps from blockSize 65537 on, as in the reference.
+ *   q7           mean: a 32-bit sum / blockSize.  power: a 32-bit sum of x*x (18.14).  mse: sat8((q15_t)(sum / blockSize)
+ *                >> 5).
+ *   absmax / absmin   max / min over (x > 0) ? x : -x, the negation saturating in fixed point (|minimum| is the
+ *                maximum); f32: +0.0 maps to -0.0 and a NaN keeps its place rules (pSrc[0] only) with its sign flipped.
+ *   _no_idx      the same searches without the index.  arm_max_no_idx_f32 / arm_min_no_idx_f32 start from -FLT_MAX /
+ *                FLT_MAX instead of pSrc[0]: a NaN never wins and an all -Inf (+Inf) vector returns -FLT_MAX (FLT_MAX).
+ *   arm_sqrt_q15 Newton on 1 / sqrt, three steps from a 16-word table; in < 0 stores 0 and returns
+ *                ARM_MATH_ARGUMENT_ERROR.  Computed on the host.  arm_cmplx_mag_fast_q15: arm_sqrt_q15((re*re + im*im)
+ *                >> 17), 2.14.
+ * Out of contract, as in the reference (a signed intermediate overflows there, which is undefined in C): a 32-bit sum
+ * leaving its range in mean_q7 (possible from blockSize 2^24 + 1), mean_q15 / var_q15 / std_q15 (from 65537),
+ * power_q7 (from 131072) and mse_q7 (from 133145); the 64-bit sum of power_q31 / mse_q31 (from 32768); in var_q31 /
+ * std_q31 sum * sum reaching 2^63 (from blockSize 363 at full scale) or the sum of squares doing so (from 2^17); in
+ * var_q15 / std_q15 also the 32-bit difference of the two quotients.  Here such a call returns what the low bits of
+ * the exact sums give.
+ * blockSize == 0: power and accumulate store 0, mean_f32 / mse_f32 a NaN (0 / 0), rms_f32 +0.0, var / std 0,
+ * max / min_no_idx_f32 their start value; every other function would divide an integer by zero or read pSrc[0]:
+ * nothing is written and arm_mi355x_last_error() is set, as for a null pointer.  blockSize 1 gives 0 in var / std.
+ * With device pointers a result that overlaps a source, or the index, is refused in the same way.
+ * Left out: arm_entropy_f32, arm_kullback_leibler_f32, arm_logsumexp_f32, arm_logsumexp_dot_prod_f32 (they rest on
+ * the host libm's expf / logf) and every f16 / f64 form. */
+#define MI355X_DECL_STAT(SUF, T, PR)                                                     \
+  void arm_mean_##SUF(const T *pSrc, uint32_t blockSize, T *pResult);                    \
+  void arm_power_##SUF(const T *pSrc, uint32_t blockSize, PR *pResult);                  \
+  void arm_mse_##SUF(const T *pSrcA, const T *pSrcB, uint32_t blockSize, T *pResult);    \
+  void arm_absmax_##SUF(const T *pSrc, uint32_t blockSize, T *pResult, uint32_t *pIndex); \
+  void arm_absmin_##SUF(const T *pSrc, uint32_t blockSize, T *pResult, uint32_t *pIndex); \
+  void arm_max_no_idx_##SUF(const T *pSrc, uint32_t blockSize, T *pResult);              \
+  void arm_min_no_idx_##SUF(const T *pSrc, uint32_t blockSize, T *pResult);              \
+  void arm_absmax_no_idx_##SUF(const T *pSrc, uint32_t blockSize, T *pResult);           \
+  void arm_absmin_no_idx_##SUF(const T *pSrc, uint32_t blockSize, T *pResult);
+#define MI355X_DECL_STAT_LEVELS(SUF, T)                                \
+  void arm_rms_##SUF(const T *pSrc, uint32_t blockSize, T *pResult);   \
+  void arm_var_##SUF(const T *pSrc, uint32_t blockSize, T *pResult);   \
+  void arm_std_##SUF(const T *pSrc, uint32_t blockSize, T *pResult);
+MI355X_DECL_STAT(f32, float32_t, float32_t)
+MI355X_DECL_STAT(q31, q31_t, q63_t)
+MI355X_DECL_STAT(q15, q15_t, q63_t)
+MI355X_DECL_STAT(q7, q7_t, q31_t)
+MI355X_DECL_STAT_LEVELS(f32, float32_t)
+MI355X_DECL_STAT_LEVELS(q31, q31_t)
+MI355X_DECL_STAT_LEVELS(q15, q15_t)
+#undef MI355X_DECL_STAT_LEVELS
+#undef MI355X_DECL_STAT
+void arm_accumulate_f32(const float32_t *pSrc, uint32_t blockSize, float32_t *pResult);
+arm_status arm_sqrt_q15(q15_t in, q15_t *pOut);
+void arm_cmplx_mag_fast_q15(const q15_t *pSrc, q15_t *pDst, uint32_t numSamples);
 
 #ifdef __cplusplus
 }

@@ -415,6 +415,50 @@ MI355X_DECL_SEARCH_BATCH(q15, q15_t)
 MI355X_DECL_SEARCH_BATCH(q7, q7_t)
 #undef MI355X_DECL_SEARCH_BATCH
 
+/* Batched statistics (arm_math.h: "The level measures and the remaining searches"): item i is the blockSize
+ * contiguous words at d_src + i * blockSize (arm_mse_*: of d_a and of d_b), and d_result[i] (d_index[i]) is what
+ * the drop-in stores for it; the result words have the drop-in's result type (arm_power_*: float32_t, q63_t,
+ * q63_t, q31_t).  Device pointers, stream-ordered.  The integer sums and the searches use the lanes-per-item
+ * mapping of arm_max_*_batch; the f32 sums are ordered chains, one wave per item below 4096 items and one lane per
+ * item from there on.  ARM_MATH_ARGUMENT_ERROR on a null pointer, on a result that overlaps a source or the index,
+ * and on blockSize == 0 where the drop-in refuses it; batch == 0 is a successful no-op.
+ * arm_cmplx_mag_fast_q15_batch: as arm_cmplx_mag_q15_batch. */
+#define MI355X_DECL_STAT_BATCH(SUF, T, PR)                                                                      \
+  arm_status arm_mean_##SUF##_batch(const T *d_src, uint32_t blockSize, T *d_result, uint32_t batch, void *stream);  \
+  arm_status arm_power_##SUF##_batch(const T *d_src, uint32_t blockSize, PR *d_result, uint32_t batch,          \
+                                     void *stream);                                                             \
+  arm_status arm_mse_##SUF##_batch(const T *d_a, const T *d_b, uint32_t blockSize, T *d_result, uint32_t batch, \
+                                   void *stream);                                                               \
+  arm_status arm_absmax_##SUF##_batch(const T *d_src, uint32_t blockSize, T *d_result, uint32_t *d_index,       \
+                                      uint32_t batch, void *stream);                                            \
+  arm_status arm_absmin_##SUF##_batch(const T *d_src, uint32_t blockSize, T *d_result, uint32_t *d_index,       \
+                                      uint32_t batch, void *stream);                                            \
+  arm_status arm_max_no_idx_##SUF##_batch(const T *d_src, uint32_t blockSize, T *d_result, uint32_t batch,      \
+                                          void *stream);                                                        \
+  arm_status arm_min_no_idx_##SUF##_batch(const T *d_src, uint32_t blockSize, T *d_result, uint32_t batch,      \
+                                          void *stream);                                                        \
+  arm_status arm_absmax_no_idx_##SUF##_batch(const T *d_src, uint32_t blockSize, T *d_result, uint32_t batch,   \
+                                             void *stream);                                                     \
+  arm_status arm_absmin_no_idx_##SUF##_batch(const T *d_src, uint32_t blockSize, T *d_result, uint32_t batch,   \
+                                             void *stream);
+#define MI355X_DECL_STAT_LEVELS_BATCH(SUF, T)                                                                       \
+  arm_status arm_rms_##SUF##_batch(const T *d_src, uint32_t blockSize, T *d_result, uint32_t batch, void *stream);  \
+  arm_status arm_var_##SUF##_batch(const T *d_src, uint32_t blockSize, T *d_result, uint32_t batch, void *stream);  \
+  arm_status arm_std_##SUF##_batch(const T *d_src, uint32_t blockSize, T *d_result, uint32_t batch, void *stream);
+MI355X_DECL_STAT_BATCH(f32, float32_t, float32_t)
+MI355X_DECL_STAT_BATCH(q31, q31_t, q63_t)
+MI355X_DECL_STAT_BATCH(q15, q15_t, q63_t)
+MI355X_DECL_STAT_BATCH(q7, q7_t, q31_t)
+MI355X_DECL_STAT_LEVELS_BATCH(f32, float32_t)
+MI355X_DECL_STAT_LEVELS_BATCH(q31, q31_t)
+MI355X_DECL_STAT_LEVELS_BATCH(q15, q15_t)
+#undef MI355X_DECL_STAT_LEVELS_BATCH
+#undef MI355X_DECL_STAT_BATCH
+arm_status arm_accumulate_f32_batch(const float32_t *d_src, uint32_t blockSize, float32_t *d_result, uint32_t batch,
+                                    void *stream);
+arm_status arm_cmplx_mag_fast_q15_batch(const q15_t *d_src, q15_t *d_dst, uint32_t numSamples, uint32_t batch,
+                                        void *stream);
+
 /* Multi-GPU complex FFT (SURVEY §8b "a multi-GPU entry point"; per item: arm_cfft_f32 /
  * _q31 / _q15, transform_functions.h:456-460).  Shard s of `nshards` is batch[s] contiguous
  * transforms at DEVICE pointer d_p1[s] on HIP device devices[s] (a device may appear in
