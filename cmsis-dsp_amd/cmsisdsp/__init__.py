@@ -693,6 +693,41 @@ for _t in ("f32", "q31", "q15", "q7"):
         globals()[_n] = _statistics(_n, f"cmsisdsp_statistics.c cmsis_{_n} {_doc}  blockSize = len(pSrc).")
 
 
+def _basic_math(name, doc):
+    """One of the basic math bindings (cmsisdsp_basic.c): an array as long as pSrc, or dot_prod's Python number."""
+    op, kind = name[len("arm_"):].rsplit("_", 1)
+    dt = _amd._BASIC_DT[kind]
+    if op == "dot_prod":
+        def run(pSrcA, pSrcB):
+            return (float if kind == "f32" else int)(_amd.arm_dot_prod(kind, _arr(pSrcA, dt), _arr(pSrcB, dt)))
+    elif op in _amd._BASIC_TWO:
+        def run(pSrcA, pSrcB):
+            return _amd.arm_basic2(op, kind, _arr(pSrcA, dt), _arr(pSrcB, dt))
+    else:
+        def run(pSrc, *scalars):
+            return _amd.arm_basic1(op, kind, _arr(pSrc, dt), *scalars)
+    run.__name__ = name
+    run.__doc__ = doc
+    return run
+
+
+for _t in ("f32", "q31", "q15", "q7"):
+    _ops = [("add", "(pSrcA, pSrcB) -> pDst"), ("sub", "(pSrcA, pSrcB) -> pDst"), ("mult", "(pSrcA, pSrcB) -> pDst"),
+            ("offset", "(pSrc, offset) -> pDst"), ("clip", "(pSrc, low, high) -> pDst"), ("abs", "(pSrc) -> pDst"),
+            ("negate", "(pSrc) -> pDst"),
+            ("scale", "(pSrc, scale) -> pDst" if _t == "f32" else "(pSrc, scaleFract, shift) -> pDst"),
+            ("dot_prod", "(pSrcA, pSrcB) -> result, a Python number (f32: float; q31, q15: a 64-bit int; q7: q31)")]
+    if _t != "f32":
+        _ops += [("shift", "(pSrc, shiftBits) -> pDst")]
+    for _op, _doc in _ops:
+        _n = f"arm_{_op}_{_t}"
+        globals()[_n] = _basic_math(_n, f"cmsisdsp_basic.c cmsis_{_n} {_doc}; blockSize = len(pSrc).")
+for _t in ("u32", "u16", "u8"):
+    for _op, _doc in (("and", "(pSrcA, pSrcB)"), ("or", "(pSrcA, pSrcB)"), ("xor", "(pSrcA, pSrcB)"), ("not", "(pSrc)")):
+        _n = f"arm_{_op}_{_t}"
+        globals()[_n] = _basic_math(_n, f"cmsisdsp_basic.c cmsis_{_n} {_doc} -> pDst; blockSize = len(pSrc).")
+
+
 def arm_sqrt_q15(x):
     """cmsisdsp_fastmath.c cmsis_arm_sqrt_q15 (in) -> (status, pOut)."""
     st, v = _amd.arm_sqrt_q15(x)

@@ -55,6 +55,7 @@ def _load():
     _abi.bind(lib, _abi.MAT_BASIC)
     _abi.bind(lib, _abi.CMPLX_MATH)
     _abi.bind(lib, _abi.STATISTICS)
+    _abi.bind(lib, _abi.BASIC_MATH)
     _abi.bind(lib, _abi.BATCHED)
     return lib
 
@@ -1180,6 +1181,163 @@ def absmax_no_idx_batch(src, result, stream=None):
 def absmin_no_idx_batch(src, result, stream=None):
     """result[i] = arm_absmin_no_idx_* of src[i] [N]."""
     _stat_batch("absmin_no_idx", src, result, stream)
+
+
+# ---- basic math: add .. clip, the bitwise functions, dot_prod ---------------------------------------------------
+_BASIC_DT = dict(_MAT_DT, u32=np.uint32, u16=np.uint16, u8=np.uint8)
+_BASIC_TWO = ("add", "sub", "mult", "and", "or", "xor")
+_DOT_PROD_DT = {"f32": np.float32, "q31": np.int64, "q15": np.int64, "q7": np.int32}
+
+
+def _basic_scalars(op, kind, scalars):
+    """The scalar arguments of arm_<op>_<kind> in the reference's order, as Python numbers."""
+    want = {"offset": 1, "scale": 1 if kind == "f32" else 2, "shift": 1, "clip": 2}.get(op, 0)
+    if len(scalars) != want:
+        raise TypeError(f"arm_{op}_{kind} takes {want} scalar argument(s), got {len(scalars)}")
+    num = float if kind == "f32" else int
+    if op == "shift":
+        return [int(scalars[0])]
+    if op == "scale" and kind != "f32":
+        return [int(scalars[0]), int(scalars[1])]
+    return [num(v) for v in scalars]
+
+
+def _basic_args(op, srcs, dst, scalars, n):
+    """The C argument list: arm_clip_* has the scalars after pDst, the others after pSrc."""
+    if op == "clip":
+        return [*srcs, dst, *scalars, n]
+    return [*srcs, *scalars, dst, n]
+
+
+def arm_basic2(op, kind, a, b):
+    """a op b, element by element, through arm_<op>_<kind> (drop-in, numpy): op add, sub, mult with kind f32, q31,
+    q15, q7 (saturating in fixed point), or and, or, xor with kind u32, u16, u8."""
+    dt = _BASIC_DT[kind]
+    a, b = np.ascontiguousarray(a, dtype=dt).reshape(-1), np.ascontiguousarray(b, dtype=dt).reshape(-1)
+    if b.size != a.size:
+        raise ValueError(f"arm_{op}_{kind}: pSrcB has {b.size} words, pSrcA {a.size}")
+    if op not in _BASIC_TWO:
+        raise ValueError(f"arm_{op}_{kind} does not take two sources")
+    d = np.zeros(a.size, dtype=dt)
+    getattr(lib, f"arm_{op}_{kind}")(a.ctypes.data, b.ctypes.data, d.ctypes.data, a.size)
+    _check_void(f"arm_{op}_{kind}")
+    return d
+
+
+def arm_basic1(op, kind, src, *scalars):
+    """op(src) through arm_<op>_<kind> (drop-in, numpy) with the reference's scalar arguments: offset (offset),
+    scale (scale; fixed point: scaleFract, shift), shift (shiftBits), clip (low, high), abs, negate, not."""
+    dt = _BASIC_DT[kind]
+    s = np.ascontiguousarray(src, dtype=dt).reshape(-1)
+    d = np.zeros(s.size, dtype=dt)
+    getattr(lib, f"arm_{op}_{kind}")(*_basic_args(op, [s.ctypes.data], d.ctypes.data,
+                                                  _basic_scalars(op, kind, scalars), s.size))
+    _check_void(f"arm_{op}_{kind}")
+    return d
+
+
+def arm_dot_prod(kind, a, b):
+    """sum a[k] * b[k] through arm_dot_prod_f32 (float32, one ordered chain) / _q31 (int64, products >> 14) / _q15
+    (int64) / _q7 (int32)."""
+    a, b = _cm_src(kind, a), _cm_src(kind, b)
+    if b.size != a.size:
+        raise ValueError(f"arm_dot_prod_{kind}: pSrcB has {b.size} words, pSrcA {a.size}")
+    out = np.zeros(1, dtype=_DOT_PROD_DT[kind])
+    getattr(lib, f"arm_dot_prod_{kind}")(a.ctypes.data, b.ctypes.data, a.size, out.ctypes.data)
+    _check_void(f"arm_dot_prod_{kind}")
+    return out[0]
+
+
+def _basic_kind(op, t):
+    if op in ("and", "or", "xor", "not"):
+        return {4: "u32", 2: "u16", 1: "u8"}[t.element_size()]
+    return _mat_kind(t)
+
+
+def _basic_batch(op, srcs, dst, scalars, stream):
+    kind = _basic_kind(op, srcs[0])
+    n = srcs[0].shape[-1]
+    batch = srcs[0].numel() // n if n else 0
+    _solve_call(f"arm_{op}_{kind}_batch", *_basic_args(op, [_cm_ptr(x) for x in srcs], _cm_ptr(dst),
+                                                       _basic_scalars(op, kind, scalars), n), batch,
+                _stream_ptr(stream))
+
+
+def add_batch(a, b, dst, stream=None):
+    """dst = a + b for contiguous device tensors [batch, N] of float32 / int32 (q31) / int16 (q15) / int8 (q7)
+    (arm_add_*_batch; saturating in fixed point).  dst may be a or b."""
+    _basic_batch("add", [a, b], dst, (), stream)
+
+
+def sub_batch(a, b, dst, stream=None):
+    """dst = a - b (arm_sub_*_batch); dst may be a or b."""
+    _basic_batch("sub", [a, b], dst, (), stream)
+
+
+def mult_batch(a, b, dst, stream=None):
+    """dst = a * b, element by element (arm_mult_*_batch: a window on a batch of frames); dst may be a or b."""
+    _basic_batch("mult", [a, b], dst, (), stream)
+
+
+def offset_batch(src, offset, dst, stream=None):
+    """dst = src + offset (arm_offset_*_batch); dst may be src."""
+    _basic_batch("offset", [src], dst, (offset,), stream)
+
+
+def scale_batch(src, scale, dst, shift=0, stream=None):
+    """dst = src * scale (arm_scale_*_batch); fixed point: (src * scale) << shift in the reference's formats."""
+    _basic_batch("scale", [src], dst, (scale,) if _mat_kind(src) == "f32" else (scale, shift), stream)
+
+
+def shift_batch(src, shift_bits, dst, stream=None):
+    """dst = src << shift_bits, saturating (negative: an arithmetic right shift) (arm_shift_*_batch)."""
+    _basic_batch("shift", [src], dst, (shift_bits,), stream)
+
+
+def clip_batch(src, low, high, dst, stream=None):
+    """dst = src clipped to [low, high] (arm_clip_*_batch)."""
+    _basic_batch("clip", [src], dst, (low, high), stream)
+
+
+def abs_batch(src, dst, stream=None):
+    """dst = |src|, saturating in fixed point (arm_abs_*_batch)."""
+    _basic_batch("abs", [src], dst, (), stream)
+
+
+def negate_batch(src, dst, stream=None):
+    """dst = -src, saturating in fixed point (arm_negate_*_batch)."""
+    _basic_batch("negate", [src], dst, (), stream)
+
+
+def and_batch(a, b, dst, stream=None):
+    """dst = a & b for integer device tensors of 4-, 2- or 1-byte words (arm_and_u32 / _u16 / _u8_batch)."""
+    _basic_batch("and", [a, b], dst, (), stream)
+
+
+def or_batch(a, b, dst, stream=None):
+    """dst = a | b (arm_or_*_batch)."""
+    _basic_batch("or", [a, b], dst, (), stream)
+
+
+def xor_batch(a, b, dst, stream=None):
+    """dst = a ^ b (arm_xor_*_batch)."""
+    _basic_batch("xor", [a, b], dst, (), stream)
+
+
+def not_batch(src, dst, stream=None):
+    """dst = ~src (arm_not_*_batch)."""
+    _basic_batch("not", [src], dst, (), stream)
+
+
+def dot_prod_batch(a, b, result, stream=None, b_stride=None):
+    """result[i] = sum_k a[i][k] * b_i[k] for a [batch, N] (arm_dot_prod_*_batch).  b [N]: one vector for every item
+    (bStride 0: a bank of signals against one template); b [batch, N]: one per item.  result [batch]: float32, int64
+    (q31, q15) or int32 (q7).  b_stride (words) overrides the distance between the items' b vectors."""
+    kind = _mat_kind(a)
+    if b_stride is None:
+        b_stride = 0 if b.dim() == 1 else b.shape[-1]
+    _solve_call(f"arm_dot_prod_{kind}_batch", _cm_ptr(a), _cm_ptr(b), int(b_stride), a.shape[-1], _cm_ptr(result),
+                a.shape[0], _stream_ptr(stream))
 
 
 def mat_mult_batch(a, b, c, stream=None, fast=False):

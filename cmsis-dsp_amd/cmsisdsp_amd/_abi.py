@@ -416,6 +416,31 @@ STATISTICS["arm_cmplx_mag_fast_q15"] = (None, [_vp, _vp, _u32])
 STATISTICS["arm_cmplx_mag_fast_q15_batch"] = (C.c_int, [_vp, _vp, _u32, _u32, _vp])
 STATISTICS["arm_sqrt_q15"] = (C.c_int, [C.c_int16, _vp])
 
+# Basic math: 51 drop-ins (the reference's signatures, all void) and their _batch forms.  The product only
+# (tests/golden/basic_math.npz holds the reference's outputs).  Scalars have the element's C type; shifts are int8_t.
+BASIC_MATH = {}
+BASIC_TYPES = ("f32", "q31", "q15", "q7")
+BITWISE_TYPES = ("u32", "u16", "u8")
+BASIC_SCALAR = {"f32": C.c_float, "q31": C.c_int32, "q15": C.c_int16, "q7": C.c_int8}
+for _t in BASIC_TYPES:
+    _s = BASIC_SCALAR[_t]
+    _ops = [("add", [_vp, _vp, _vp, _u32]), ("sub", [_vp, _vp, _vp, _u32]), ("mult", [_vp, _vp, _vp, _u32]),
+            ("offset", [_vp, _s, _vp, _u32]), ("clip", [_vp, _vp, _s, _s, _u32]), ("abs", [_vp, _vp, _u32]),
+            ("negate", [_vp, _vp, _u32]),
+            ("scale", [_vp, _s, _vp, _u32] if _t == "f32" else [_vp, _s, C.c_int8, _vp, _u32])]
+    if _t != "f32":
+        _ops += [("shift", [_vp, C.c_int8, _vp, _u32])]
+    for _n, _a in _ops:
+        BASIC_MATH[f"arm_{_n}_{_t}"] = (None, _a)
+        BASIC_MATH[f"arm_{_n}_{_t}_batch"] = (C.c_int, _a + [_u32, _vp])
+    BASIC_MATH[f"arm_dot_prod_{_t}"] = (None, [_vp, _vp, _u32, _vp])
+    BASIC_MATH[f"arm_dot_prod_{_t}_batch"] = (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp])
+for _t in BITWISE_TYPES:
+    for _n, _a in (("and", [_vp, _vp, _vp, _u32]), ("or", [_vp, _vp, _vp, _u32]), ("xor", [_vp, _vp, _vp, _u32]),
+                   ("not", [_vp, _vp, _u32])):
+        BASIC_MATH[f"arm_{_n}_{_t}"] = (None, _a)
+        BASIC_MATH[f"arm_{_n}_{_t}_batch"] = (C.c_int, _a + [_u32, _vp])
+
 # per-length MFCC init functions (the product and the reference build; the oracle has the
 # generic init only)
 MFCC_LEN = {f"arm_mfcc_init_{n}_f32": (C.c_int, [P(arm_mfcc_instance_f32), C.c_uint32, C.c_uint32, C.c_void_p,

@@ -1649,6 +1649,66 @@ arm_status st_search(bool max, bool abs, bool idx, const T* src, uint32_t n, T* 
     return run((const T*)bufs[0].d, (T*)bufs[1].d, idx ? (uint32_t*)bufs[2].d : nullptr, st);
   });
 }
+
+// ---- basic math (basic_math.hip; the dot products: statistics.hip) ---------------------------------
+// basic_math_functions.h.  sync and the null / overlap rules as the complex-math functions: dst may be a source
+// exactly, any other overlap of an output with a source is refused.  One scalar (offset, scale and shift, low and
+// high) serves the whole call.  shift: the counts at which the reference's C is defined (a count below 32 either way
+// on its promoted int operands): arm_shift_* -31 .. 31; arm_scale_q31 -32 .. 30 (kShift = shift + 1), _q15 -16 .. 15
+// (kShift = 15 - shift in 0 .. 31), _q7 -24 .. 7 (kShift = 7 - shift); outside the call is refused.
+bool bm_two(int op) { return op == kBmAdd || op == kBmSub || op == kBmMult || op == kBmAnd || op == kBmOr || op == kBmXor; }
+
+template <typename T>
+arm_status bm_ew(int op, const T* a, const T* b, T* d, uint32_t n, T s0, T s1, int shift, bool sync, uint32_t batch,
+                 void* stream, const char* what) {
+  const bool two = bm_two(op);
+  if (sync && (!a || (two && !b) || !d)) return cm_null(true, what);
+  int sh = 0;
+  if (op == kBmShift) {
+    if (shift < -31 || shift > 31) return cm_null(sync, what);
+    sh = shift;
+  } else if (op == kBmScale && !std::is_same<T, float>::value) {
+    const int lo = sizeof(T) == 4 ? -32 : sizeof(T) == 2 ? -16 : -24, hi = sizeof(T) == 4 ? 30 : sizeof(T) == 2 ? 15 : 7;
+    if (shift < lo || shift > hi) return cm_null(sync, what);
+    sh = sizeof(T) == 4 ? shift + 1 : hi - shift;
+  }
+  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
+  if (!a || (two && !b) || !d) return ARM_MATH_ARGUMENT_ERROR;
+  const size_t count = (size_t)n * batch, bytes = sizeof(T) * count;
+  auto run = [&](const T* da, const T* db, T* dd, hipStream_t st) -> hipError_t {
+    if (cm_overlaps(dd, bytes, da, bytes, true) || (two && cm_overlaps(dd, bytes, db, bytes, true)))
+      return hipErrorInvalidValue;
+    return basic_ew_launch<T>(op, da, db, dd, count, s0, s1, sh, st);
+  };
+  if (!sync) return batch_status(run(a, b, d, (hipStream_t)stream), what);
+  SolveBuf bufs[3] = {{const_cast<T*>(a), bytes, true, false}, {d, bytes, false, true},
+                      {const_cast<T*>(b), bytes, true, false}};
+  return mat_staged_sync(bufs, two ? 3 : 2, what, [&](hipStream_t st) {
+    return run((const T*)bufs[0].d, two ? (const T*)bufs[2].d : nullptr, (T*)bufs[1].d, st);
+  });
+}
+
+// bStride (words; the drop-in passes n): 0 shares one b, otherwise >= n.  n == 0 stores zeros.
+template <typename T, typename R>
+arm_status bm_dot(const T* a, const T* b, uint32_t bStride, uint32_t n, R* result, bool sync, uint32_t batch,
+                  void* stream, const char* what) {
+  if (sync && (!a || !b || !result)) return cm_null(true, what);
+  if (bStride != 0 && bStride < n) return ARM_MATH_ARGUMENT_ERROR;
+  if (batch == 0) return ARM_MATH_SUCCESS;
+  if (!a || !b || !result) return ARM_MATH_ARGUMENT_ERROR;
+  const size_t ab = sizeof(T) * n * batch, rb = sizeof(R) * batch;
+  const size_t bb = sizeof(T) * ((size_t)bStride * (batch - 1) + n);
+  auto run = [&](const T* da, const T* db, R* dr, hipStream_t st) -> hipError_t {
+    if (cm_overlaps(dr, rb, da, ab, false) || cm_overlaps(dr, rb, db, bb, false)) return hipErrorInvalidValue;
+    return dot_prod_launch<T, R>(da, db, bStride, n, dr, batch, st);
+  };
+  if (!sync) return batch_status(run(a, b, result, (hipStream_t)stream), what);
+  SolveBuf bufs[3] = {{const_cast<T*>(a), ab, n != 0, false}, {const_cast<T*>(b), bb, n != 0, false},
+                      {result, rb, false, true}};
+  return mat_staged_sync(bufs, 3, what, [&](hipStream_t st) {
+    return run((const T*)bufs[0].d, (const T*)bufs[1].d, (R*)bufs[2].d, st);
+  });
+}
 }  // namespace
 
 extern "C" {
@@ -2315,6 +2375,115 @@ MI355X_STAT_SEARCH_TYPE(q7, q7_t, int8_t)
 #undef MI355X_STAT_SEARCH_TYPE
 #undef MI355X_STAT_NO_IDX
 #undef MI355X_STAT_SEARCH
+
+// ---- basic math; bm_ew and bm_dot precede the C block ----
+#define MI355X_BM_2(NAME, OP, SUF, T, CT)                                                                        \
+  void arm_##NAME##_##SUF(const T* pSrcA, const T* pSrcB, T* pDst, uint32_t blockSize) {                         \
+    bm_ew<CT>(OP, (const CT*)pSrcA, (const CT*)pSrcB, (CT*)pDst, blockSize, (CT)0, (CT)0, 0, true, 1, nullptr,   \
+              "arm_" #NAME "_" #SUF);                                                                            \
+  }                                                                                                              \
+  arm_status arm_##NAME##_##SUF##_batch(const T* d_srcA, const T* d_srcB, T* d_dst, uint32_t blockSize,          \
+                                        uint32_t batch, void* stream) {                                          \
+    return bm_ew<CT>(OP, (const CT*)d_srcA, (const CT*)d_srcB, (CT*)d_dst, blockSize, (CT)0, (CT)0, 0, false,    \
+                     batch, stream, "arm_" #NAME "_" #SUF "_batch");                                             \
+  }
+#define MI355X_BM_1(NAME, OP, SUF, T, CT)                                                                        \
+  void arm_##NAME##_##SUF(const T* pSrc, T* pDst, uint32_t blockSize) {                                          \
+    bm_ew<CT>(OP, (const CT*)pSrc, (const CT*)nullptr, (CT*)pDst, blockSize, (CT)0, (CT)0, 0, true, 1, nullptr,  \
+              "arm_" #NAME "_" #SUF);                                                                            \
+  }                                                                                                              \
+  arm_status arm_##NAME##_##SUF##_batch(const T* d_src, T* d_dst, uint32_t blockSize, uint32_t batch,            \
+                                        void* stream) {                                                          \
+    return bm_ew<CT>(OP, (const CT*)d_src, (const CT*)nullptr, (CT*)d_dst, blockSize, (CT)0, (CT)0, 0, false,    \
+                     batch, stream, "arm_" #NAME "_" #SUF "_batch");                                             \
+  }
+#define MI355X_BM_OFFSET(NAME, OP, SUF, T, CT)                                                                   \
+  void arm_##NAME##_##SUF(const T* pSrc, T value, T* pDst, uint32_t blockSize) {                                 \
+    bm_ew<CT>(OP, (const CT*)pSrc, (const CT*)nullptr, (CT*)pDst, blockSize, (CT)value, (CT)0, 0, true, 1,       \
+              nullptr, "arm_" #NAME "_" #SUF);                                                                   \
+  }                                                                                                              \
+  arm_status arm_##NAME##_##SUF##_batch(const T* d_src, T value, T* d_dst, uint32_t blockSize, uint32_t batch,   \
+                                        void* stream) {                                                          \
+    return bm_ew<CT>(OP, (const CT*)d_src, (const CT*)nullptr, (CT*)d_dst, blockSize, (CT)value, (CT)0, 0,       \
+                     false, batch, stream, "arm_" #NAME "_" #SUF "_batch");                                      \
+  }
+#define MI355X_BM_SCALE(SUF, T, CT)                                                                              \
+  void arm_scale_##SUF(const T* pSrc, T scaleFract, int8_t shift, T* pDst, uint32_t blockSize) {                 \
+    bm_ew<CT>(kBmScale, (const CT*)pSrc, (const CT*)nullptr, (CT*)pDst, blockSize, (CT)scaleFract, (CT)0, shift, \
+              true, 1, nullptr, "arm_scale_" #SUF);                                                              \
+  }                                                                                                              \
+  arm_status arm_scale_##SUF##_batch(const T* d_src, T scaleFract, int8_t shift, T* d_dst, uint32_t blockSize,   \
+                                     uint32_t batch, void* stream) {                                             \
+    return bm_ew<CT>(kBmScale, (const CT*)d_src, (const CT*)nullptr, (CT*)d_dst, blockSize, (CT)scaleFract,      \
+                     (CT)0, shift, false, batch, stream, "arm_scale_" #SUF "_batch");                            \
+  }
+#define MI355X_BM_SHIFT(SUF, T, CT)                                                                              \
+  void arm_shift_##SUF(const T* pSrc, int8_t shiftBits, T* pDst, uint32_t blockSize) {                           \
+    bm_ew<CT>(kBmShift, (const CT*)pSrc, (const CT*)nullptr, (CT*)pDst, blockSize, (CT)0, (CT)0, shiftBits,      \
+              true, 1, nullptr, "arm_shift_" #SUF);                                                              \
+  }                                                                                                              \
+  arm_status arm_shift_##SUF##_batch(const T* d_src, int8_t shiftBits, T* d_dst, uint32_t blockSize,             \
+                                     uint32_t batch, void* stream) {                                             \
+    return bm_ew<CT>(kBmShift, (const CT*)d_src, (const CT*)nullptr, (CT*)d_dst, blockSize, (CT)0, (CT)0,        \
+                     shiftBits, false, batch, stream, "arm_shift_" #SUF "_batch");                               \
+  }
+#define MI355X_BM_CLIP(SUF, T, CT)                                                                               \
+  void arm_clip_##SUF(const T* pSrc, T* pDst, T low, T high, uint32_t numSamples) {                              \
+    bm_ew<CT>(kBmClip, (const CT*)pSrc, (const CT*)nullptr, (CT*)pDst, numSamples, (CT)low, (CT)high, 0, true,   \
+              1, nullptr, "arm_clip_" #SUF);                                                                     \
+  }                                                                                                              \
+  arm_status arm_clip_##SUF##_batch(const T* d_src, T* d_dst, T low, T high, uint32_t numSamples,                \
+                                    uint32_t batch, void* stream) {                                              \
+    return bm_ew<CT>(kBmClip, (const CT*)d_src, (const CT*)nullptr, (CT*)d_dst, numSamples, (CT)low, (CT)high,   \
+                     0, false, batch, stream, "arm_clip_" #SUF "_batch");                                        \
+  }
+#define MI355X_BM_DOT(SUF, T, CT, R, CR)                                                                         \
+  void arm_dot_prod_##SUF(const T* pSrcA, const T* pSrcB, uint32_t blockSize, R* result) {                       \
+    bm_dot<CT, CR>((const CT*)pSrcA, (const CT*)pSrcB, blockSize, blockSize, (CR*)result, true, 1, nullptr,      \
+                   "arm_dot_prod_" #SUF);                                                                        \
+  }                                                                                                              \
+  arm_status arm_dot_prod_##SUF##_batch(const T* d_a, const T* d_b, uint32_t bStride, uint32_t blockSize,        \
+                                        R* d_result, uint32_t batch, void* stream) {                             \
+    return bm_dot<CT, CR>((const CT*)d_a, (const CT*)d_b, bStride, blockSize, (CR*)d_result, false, batch,       \
+                          stream, "arm_dot_prod_" #SUF "_batch");                                                \
+  }
+#define MI355X_BM_TYPE(SUF, T, CT, R, CR)          \
+  MI355X_BM_2(add, kBmAdd, SUF, T, CT)             \
+  MI355X_BM_2(sub, kBmSub, SUF, T, CT)             \
+  MI355X_BM_2(mult, kBmMult, SUF, T, CT)           \
+  MI355X_BM_OFFSET(offset, kBmOffset, SUF, T, CT)  \
+  MI355X_BM_CLIP(SUF, T, CT)                       \
+  MI355X_BM_1(abs, kBmAbs, SUF, T, CT)             \
+  MI355X_BM_1(negate, kBmNegate, SUF, T, CT)       \
+  MI355X_BM_DOT(SUF, T, CT, R, CR)
+#define MI355X_BM_BITS(SUF, T)                     \
+  MI355X_BM_2(and, kBmAnd, SUF, T, T)              \
+  MI355X_BM_2(or, kBmOr, SUF, T, T)                \
+  MI355X_BM_2(xor, kBmXor, SUF, T, T)              \
+  MI355X_BM_1(not, kBmNot, SUF, T, T)
+MI355X_BM_TYPE(f32, float32_t, float, float32_t, float)
+MI355X_BM_TYPE(q31, q31_t, int32_t, q63_t, int64_t)
+MI355X_BM_TYPE(q15, q15_t, int16_t, q63_t, int64_t)
+MI355X_BM_TYPE(q7, q7_t, int8_t, q31_t, int32_t)
+MI355X_BM_OFFSET(scale, kBmScale, f32, float32_t, float)
+MI355X_BM_SCALE(q31, q31_t, int32_t)
+MI355X_BM_SCALE(q15, q15_t, int16_t)
+MI355X_BM_SCALE(q7, q7_t, int8_t)
+MI355X_BM_SHIFT(q31, q31_t, int32_t)
+MI355X_BM_SHIFT(q15, q15_t, int16_t)
+MI355X_BM_SHIFT(q7, q7_t, int8_t)
+MI355X_BM_BITS(u32, uint32_t)
+MI355X_BM_BITS(u16, uint16_t)
+MI355X_BM_BITS(u8, uint8_t)
+#undef MI355X_BM_BITS
+#undef MI355X_BM_TYPE
+#undef MI355X_BM_DOT
+#undef MI355X_BM_CLIP
+#undef MI355X_BM_SHIFT
+#undef MI355X_BM_SCALE
+#undef MI355X_BM_OFFSET
+#undef MI355X_BM_1
+#undef MI355X_BM_2
 
 // ---- convolution ------------------------------------------------------------------
 #define MI355X_CONV_FULL(NAME, T, CT, OP, VAR)                                                                  \

@@ -322,7 +322,8 @@ hipError_t search_launch(bool max, const T* src, uint32_t n, T* result, uint32_t
 // power: float, int64_t, int64_t, int32_t).  b: the second source of kStMse, otherwise unused.  lut: the device copy
 // of sqrt_initial_lut_q31 (read by the q31 kStRms / kStStd only).  n == 0 stores what the empty sums give (the
 // caller refuses the integer forms that would divide by zero).  The float sums are ordered chains.
-enum : int { kStMean = 0, kStPower = 1, kStRms = 2, kStVar = 3, kStStd = 4, kStMse = 5, kStAccumulate = 6 };
+enum : int { kStMean = 0, kStPower = 1, kStRms = 2, kStVar = 3, kStStd = 4, kStMse = 5, kStAccumulate = 6,
+             kStDot = 7 /* dot_prod_launch only */ };
 template <typename T, typename R>
 hipError_t stat_sum_launch(int op, const T* a, const T* b, uint32_t n, R* result, uint32_t batch, const int32_t* lut,
                            hipStream_t st);
@@ -334,5 +335,25 @@ hipError_t stat_search_launch(bool max, bool abs, const T* src, uint32_t n, T* r
                               hipStream_t st);
 // arm_sqrt_q15 on the host (the scalar drop-in): 0 for in <= 0.
 int16_t sqrt_q15_host(int16_t in);
+
+// The basic math functions, bit-exact with the reference's scalar branches (basic_math.hip).
+// basic_ew_launch: d[i] = op(a[i], b[i]) over `count` words (the whole batch as one flat array).  T is float,
+// int32_t (q31), int16_t (q15), int8_t (q7) for kBmAdd .. kBmNegate (kBmShift: fixed point only) and uint32_t,
+// uint16_t, uint8_t for kBmAnd .. kBmNot; anything else is hipErrorInvalidValue.  b: the second source of add, sub,
+// mult, and, or, xor, otherwise unused.  s0: the offset, the scale or clip's low; s1: clip's high.  sh: kBmShift:
+// shiftBits, -31 .. 31; kBmScale: the reference's kShift, q31 shift + 1 (-31 .. 31, negative: a right shift), q15
+// 15 - shift and q7 7 - shift (0 .. 31).  The caller checks the ranges.  d may be a or b exactly.
+enum : int {
+  kBmAdd = 0, kBmSub, kBmMult, kBmOffset, kBmScale, kBmShift, kBmClip, kBmAbs, kBmNegate, kBmAnd, kBmOr, kBmXor,
+  kBmNot
+};
+template <typename T>
+hipError_t basic_ew_launch(int op, const T* a, const T* b, T* d, size_t count, T s0, T s1, int sh, hipStream_t st);
+// result[i] = arm_dot_prod_* of a[i] and b_i (n words each), b_i = b + i * bStride words (0: one b for every item).
+// R: float, int64_t (q31: every product >> 14; q15: exact products) or int32_t (q7).  n == 0 stores zeros.  The
+// float sum is one ordered chain sum + a*b.  An operation of the sum kernels of statistics.hip.
+template <typename T, typename R>
+hipError_t dot_prod_launch(const T* a, const T* b, size_t bStride, uint32_t n, R* result, uint32_t batch,
+                           hipStream_t st);
 
 }  // namespace mi355x

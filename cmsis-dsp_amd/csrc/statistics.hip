@@ -21,6 +21,9 @@
 //                  run the mean's chain first and then the chain of (x - mean)^2: the wave form keeps an item
 //                  of up to kVarKeep words in LDS for the second pass and reads a longer one again; the lane form
 //                  always reads it again.
+//   dot products   arm_dot_prod_* (kStDot) are one more operation of these kernels: the term is a*b (q31: >> 14), the
+//                  second source's items are bStride words apart (0: one for every item, which the lane form stages
+//                  once per row all the same; mse passes the item length).
 #include <type_traits>
 
 #include "common.hpp"
@@ -34,6 +37,7 @@ namespace {
 
 template <typename T> constexpr bool kIsQ31 = std::is_same<T, int32_t>::value;
 template <int OP> constexpr bool kIsVar = OP == kStVar || OP == kStStd;
+template <int OP> constexpr bool kTwoSources = OP == kStMse || OP == kStDot;   // kStDot: arm_dot_prod_*
 
 __device__ __forceinline__ int32_t ssat8(int32_t v) { return v > 127 ? 127 : (v < -128 ? -128 : v); }
 
@@ -48,6 +52,7 @@ __device__ __forceinline__ auto sum_term0(T a, T b) {
     else if constexpr (OP == kStPower) return ((int64_t)x * x) >> 14;
     else if constexpr (OP == kStRms) return (int64_t)x * x;
     else if constexpr (kIsVar<OP>) return (int64_t)(x >> 8);
+    else if constexpr (OP == kStDot) return ((int64_t)x * y) >> 14;
     else {                                                  // mse: __QSUB of the halves
       int64_t d = (int64_t)(x >> 1) - (int64_t)(y >> 1);
       d = d > INT32_MAX ? INT32_MAX : (d < INT32_MIN ? INT32_MIN : d);
@@ -56,6 +61,7 @@ __device__ __forceinline__ auto sum_term0(T a, T b) {
   } else {
     if constexpr (OP == kStMean || kIsVar<OP>) return x;
     else if constexpr (OP == kStPower || OP == kStRms) return x * x;
+    else if constexpr (OP == kStDot) return x * y;
     else {
       const int32_t d = sizeof(T) == 2 ? ssat16((x >> 1) - (y >> 1)) : ssat8((x >> 1) - (y >> 1));
       return d * d;
@@ -80,15 +86,16 @@ __device__ __forceinline__ void sum_take(uint64_t& s0, uint64_t& s1, T a, T b) {
 }
 
 // One 16-B pack.  q7 / q15: groups of G terms are summed in 32 bits first: every element when the terms are the
-// elements themselves or q7 squares (16 x 2^14), pairs of q15 squares (2 x 2^30 < 2^32).
+// elements themselves or q7 squares (16 x 2^14), pairs of q15 squares (2 x 2^30 < 2^32).  The dot products' terms are
+// signed: 16 q7 products fit 32 bits, two q15 products (min * min twice: 2^31) do not.
 template <int OP, typename T, int V>
 __device__ __forceinline__ void sum_take_pack(uint64_t& s0, uint64_t& s1, const T* x, const T* y) {
   if constexpr (kIsQ31<T>) {
 #pragma unroll
     for (int j = 0; j < V; ++j) sum_take<OP, T>(s0, s1, x[j], y[j]);
   } else {
-    constexpr bool kPlain = OP == kStMean || kIsVar<OP>;     // signed terms: the elements
-    constexpr int G0 = (kPlain || sizeof(T) == 1) ? V : 2;
+    constexpr bool kPlain = OP == kStMean || kIsVar<OP> || OP == kStDot;   // signed terms
+    constexpr int G0 = OP == kStDot ? (sizeof(T) == 1 ? V : 1) : (kPlain || sizeof(T) == 1) ? V : 2;
 #pragma unroll
     for (int g = 0; g < V; g += G0) {
       uint32_t p = 0;
@@ -110,7 +117,7 @@ __device__ __forceinline__ int32_t div_q31(int32_t s, int32_t d) { return d == -
 // The reference's epilogue on the item's sums.  lut: sqrt_initial_lut_q31 in LDS (q31 rms / std).
 template <int OP, typename T, typename R>
 __device__ __forceinline__ R sum_finish(uint64_t s0, uint64_t s1, uint32_t n, const int32_t* lut) {
-  if constexpr (OP == kStPower) {
+  if constexpr (OP == kStPower || OP == kStDot) {
     return (R)(int64_t)s0;                                  // q7: the low 32 bits
   } else if constexpr (kIsVar<OP>) {
     if (n <= 1u) return (R)0;
@@ -144,12 +151,14 @@ __device__ __forceinline__ R sum_finish(uint64_t s0, uint64_t s1, uint32_t n, co
   }
 }
 
-// wide: every item of a (and b) starts 16-B aligned and holds a whole number of 16-B packs.
+// wide: every item of a (and b) starts 16-B aligned and holds a whole number of 16-B packs.  bStride: words between
+// the items' second sources (0: one for every item).
 template <int OP, typename T, typename R>
-__global__ __launch_bounds__(kBlock) void sum_int_kernel(const T* pa, const T* pb, uint32_t n, R* result,
-                                                         uint32_t batch, int lpiLog, bool wide, const int32_t* lut) {
+__global__ __launch_bounds__(kBlock) void sum_int_kernel(const T* pa, const T* pb, size_t bStride, uint32_t n,
+                                                         R* result, uint32_t batch, int lpiLog, bool wide,
+                                                         const int32_t* lut) {
   constexpr int V = 16 / sizeof(T);
-  constexpr bool kTwoSrc = OP == kStMse;
+  constexpr bool kTwoSrc = kTwoSources<OP>;
   constexpr bool kLut = kIsQ31<T> && (OP == kStRms || OP == kStStd);
   struct alignas(16) Pack { T v[V]; };
   __shared__ uint64_t part[kBlock / 64][2];
@@ -163,7 +172,7 @@ __global__ __launch_bounds__(kBlock) void sum_int_kernel(const T* pa, const T* p
   const uint32_t item = blockIdx.x * ipw + li;
   const bool live = item < batch;
   const T* a = pa + (size_t)(live ? item : 0) * n;
-  const T* b = kTwoSrc ? pb + (size_t)(live ? item : 0) * n : a;
+  const T* b = kTwoSrc ? pb + (size_t)(live ? item : 0) * bStride : a;
   uint64_t s0 = 0, s1 = 0;
   if (live) {
     if (wide) {
@@ -204,6 +213,8 @@ __device__ __forceinline__ float chain_term(float x, float y) {
   } else if constexpr (OP == kStMse) {
     const float d = x - y;
     return d * d;
+  } else if constexpr (OP == kStDot) {
+    return x * y;
   } else {
     return x;                                               // mean, accumulate, the mean pass of var / std
   }
@@ -218,7 +229,7 @@ __device__ __forceinline__ float chain_finish(float sum, uint32_t n) {
   else if constexpr (OP == kStRms) return sqrt_or_zero(sum / (float)n);
   else if constexpr (OP == kStVar) return sum / (float)((float)n - 1.0f);
   else if constexpr (OP == kStStd) return sqrt_or_zero(sum / (float)((float)n - 1.0f));
-  else return sum;                                          // power, accumulate
+  else return sum;                                          // power, accumulate, dot_prod
 }
 
 // sum + t[0] + t[1] + ... + t[cnt - 1], lane j holding t[j], in that order.
@@ -235,8 +246,8 @@ __device__ __forceinline__ float chain_lanes(float sum, float t, uint32_t cnt) {
 
 // One wave per item.
 template <int OP>
-__global__ __launch_bounds__(kBlock) void sum_f32_wave_kernel(const float* pa, const float* pb, uint32_t n,
-                                                              float* result, uint32_t batch) {
+__global__ __launch_bounds__(kBlock) void sum_f32_wave_kernel(const float* pa, const float* pb, size_t bStride,
+                                                              uint32_t n, float* result, uint32_t batch) {
   __shared__ float keep[kIsVar<OP> ? kBlock / 64 : 1][kIsVar<OP> ? kVarKeep : 1];
   const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const uint32_t item = blockIdx.x * (uint32_t)(kBlock / 64) + w;
@@ -246,7 +257,7 @@ __global__ __launch_bounds__(kBlock) void sum_f32_wave_kernel(const float* pa, c
     return;
   }
   const float* a = pa + (size_t)item * n;
-  const float* b = OP == kStMse ? pb + (size_t)item * n : a;
+  const float* b = kTwoSources<OP> ? pb + (size_t)item * bStride : a;
   const bool kept = kIsVar<OP> && n <= kVarKeep;
   float sum = 0.0f;
   for (uint64_t k0 = 0; k0 < n; k0 += 64) {
@@ -254,7 +265,7 @@ __global__ __launch_bounds__(kBlock) void sum_f32_wave_kernel(const float* pa, c
     float x = 0.0f, y = 0.0f;
     if (lane < cnt) {
       x = a[k0 + lane];
-      if constexpr (OP == kStMse) y = b[k0 + lane];
+      if constexpr (kTwoSources<OP>) y = b[k0 + lane];
       if constexpr (kIsVar<OP>)
         if (kept) keep[w][k0 + lane] = x;                  // read back by this lane only
     }
@@ -276,10 +287,10 @@ __global__ __launch_bounds__(kBlock) void sum_f32_wave_kernel(const float* pa, c
 
 // One lane per item.  LDS rows of kSumChunk + 1 words: a lane walks its own row, 17 words from its neighbour's.
 template <int OP>
-__global__ __launch_bounds__(kBlock) void sum_f32_lane_kernel(const float* pa, const float* pb, uint32_t n,
-                                                              float* result, uint32_t batch) {
+__global__ __launch_bounds__(kBlock) void sum_f32_lane_kernel(const float* pa, const float* pb, size_t bStride,
+                                                              uint32_t n, float* result, uint32_t batch) {
   constexpr int KW = kSumChunk, LD = KW + 1;
-  constexpr bool kTwoSrc = OP == kStMse;
+  constexpr bool kTwoSrc = kTwoSources<OP>;
   __shared__ float am[kBlock * LD];
   __shared__ float bm[kTwoSrc ? kBlock * LD : 1];
   const uint32_t item0 = blockIdx.x * (uint32_t)kBlock, item = item0 + threadIdx.x;
@@ -295,7 +306,7 @@ __global__ __launch_bounds__(kBlock) void sum_f32_lane_kernel(const float* pa, c
         const uint32_t r = idx / KW, wd = idx % KW, it = item0 + r;
         if (wd < kc && it < batch) {
           am[r * LD + wd] = pa[(size_t)it * n + k0 + wd];
-          if constexpr (kTwoSrc) bm[r * LD + wd] = pb[(size_t)it * n + k0 + wd];
+          if constexpr (kTwoSrc) bm[r * LD + wd] = pb[(size_t)it * bStride + k0 + wd];
         }
       }
       __syncthreads();
@@ -324,11 +335,11 @@ template <> struct PowerResult<int32_t> { using type = int64_t; };
 template <> struct PowerResult<int16_t> { using type = int64_t; };
 template <> struct PowerResult<int8_t> { using type = int32_t; };
 
-// The (operation, type, result type) triples the reference has.
+// The (operation, type, result type) triples the reference has (dot_prod's result types are power's).
 template <int OP, typename T, typename R>
 constexpr bool stat_sum_exists() {
   constexpr bool f32 = std::is_same<T, float>::value, q7 = std::is_same<T, int8_t>::value;
-  if (OP == kStPower) return std::is_same<R, typename PowerResult<T>::type>::value;
+  if (OP == kStPower || OP == kStDot) return std::is_same<R, typename PowerResult<T>::type>::value;
   if (!std::is_same<R, T>::value) return false;
   if (OP == kStAccumulate) return f32;
   if (OP == kStRms || OP == kStVar || OP == kStStd) return !q7;
@@ -336,27 +347,29 @@ constexpr bool stat_sum_exists() {
 }
 
 template <int OP, typename T, typename R>
-hipError_t sum_run(const T* a, const T* b, uint32_t n, R* result, uint32_t batch, const int32_t* lut, hipStream_t st) {
+hipError_t sum_run(const T* a, const T* b, size_t bStride, uint32_t n, R* result, uint32_t batch, const int32_t* lut,
+                   hipStream_t st) {
   if constexpr (!stat_sum_exists<OP, T, R>()) {
     return hipErrorInvalidValue;
   } else if constexpr (std::is_same<T, float>::value) {
     if (batch >= kSumLaneMinBatch) {
       const dim3 grid((batch + kBlock - 1) / kBlock);
-      hipLaunchKernelGGL((sum_f32_lane_kernel<OP>), grid, dim3(kBlock), 0, st, a, b, n, result, batch);
+      hipLaunchKernelGGL((sum_f32_lane_kernel<OP>), grid, dim3(kBlock), 0, st, a, b, bStride, n, result, batch);
     } else {
       const dim3 grid((batch + kBlock / 64 - 1) / (kBlock / 64));
-      hipLaunchKernelGGL((sum_f32_wave_kernel<OP>), grid, dim3(kBlock), 0, st, a, b, n, result, batch);
+      hipLaunchKernelGGL((sum_f32_wave_kernel<OP>), grid, dim3(kBlock), 0, st, a, b, bStride, n, result, batch);
     }
     return hipGetLastError();
   } else {
     constexpr uint32_t V = 16 / sizeof(T);
-    const bool wide = (((uintptr_t)a | (uintptr_t)(OP == kStMse ? b : a) | ((size_t)n * sizeof(T))) & 15) == 0;
+    const bool wide = (((uintptr_t)a | (uintptr_t)(kTwoSources<OP> ? b : a) | ((size_t)n * sizeof(T)) |
+                        (kTwoSources<OP> ? bStride * sizeof(T) : 0)) & 15) == 0;
     const int lpiLog = red_lpi_log(wide ? n / V : n);
     const uint32_t ipw = kBlock >> lpiLog;
     const uint64_t grid = ((uint64_t)batch + ipw - 1) / ipw;
     if (grid > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((sum_int_kernel<OP, T, R>), dim3((uint32_t)grid), dim3(kBlock), 0, st, a, b, n, result, batch,
-                       lpiLog, wide, lut);
+    hipLaunchKernelGGL((sum_int_kernel<OP, T, R>), dim3((uint32_t)grid), dim3(kBlock), 0, st, a, b, bStride, n, result,
+                       batch, lpiLog, wide, lut);
     return hipGetLastError();
   }
 }
@@ -368,13 +381,13 @@ hipError_t stat_sum_launch(int op, const T* a, const T* b, uint32_t n, R* result
                            hipStream_t st) {
   if (batch == 0) return hipSuccess;
   switch (op) {
-    case kStMean: return sum_run<kStMean, T, R>(a, b, n, result, batch, lut, st);
-    case kStPower: return sum_run<kStPower, T, R>(a, b, n, result, batch, lut, st);
-    case kStRms: return sum_run<kStRms, T, R>(a, b, n, result, batch, lut, st);
-    case kStVar: return sum_run<kStVar, T, R>(a, b, n, result, batch, lut, st);
-    case kStStd: return sum_run<kStStd, T, R>(a, b, n, result, batch, lut, st);
-    case kStMse: return sum_run<kStMse, T, R>(a, b, n, result, batch, lut, st);
-    case kStAccumulate: return sum_run<kStAccumulate, T, R>(a, b, n, result, batch, lut, st);
+    case kStMean: return sum_run<kStMean, T, R>(a, b, n, n, result, batch, lut, st);
+    case kStPower: return sum_run<kStPower, T, R>(a, b, n, n, result, batch, lut, st);
+    case kStRms: return sum_run<kStRms, T, R>(a, b, n, n, result, batch, lut, st);
+    case kStVar: return sum_run<kStVar, T, R>(a, b, n, n, result, batch, lut, st);
+    case kStStd: return sum_run<kStStd, T, R>(a, b, n, n, result, batch, lut, st);
+    case kStMse: return sum_run<kStMse, T, R>(a, b, n, n, result, batch, lut, st);
+    case kStAccumulate: return sum_run<kStAccumulate, T, R>(a, b, n, n, result, batch, lut, st);
   }
   return hipErrorInvalidValue;
 }
@@ -389,6 +402,21 @@ MI355X_STAT_SUM(int16_t, int64_t)
 MI355X_STAT_SUM(int8_t, int8_t)
 MI355X_STAT_SUM(int8_t, int32_t)
 #undef MI355X_STAT_SUM
+
+template <typename T, typename R>
+hipError_t dot_prod_launch(const T* a, const T* b, size_t bStride, uint32_t n, R* result, uint32_t batch,
+                           hipStream_t st) {
+  if (batch == 0) return hipSuccess;
+  return sum_run<kStDot, T, R>(a, b, bStride, n, result, batch, nullptr, st);
+}
+template hipError_t dot_prod_launch<float, float>(const float*, const float*, size_t, uint32_t, float*, uint32_t,
+                                                  hipStream_t);
+template hipError_t dot_prod_launch<int32_t, int64_t>(const int32_t*, const int32_t*, size_t, uint32_t, int64_t*,
+                                                      uint32_t, hipStream_t);
+template hipError_t dot_prod_launch<int16_t, int64_t>(const int16_t*, const int16_t*, size_t, uint32_t, int64_t*,
+                                                      uint32_t, hipStream_t);
+template hipError_t dot_prod_launch<int8_t, int32_t>(const int8_t*, const int8_t*, size_t, uint32_t, int32_t*,
+                                                     uint32_t, hipStream_t);
 
 template <typename T>
 hipError_t stat_search_launch(bool max, bool abs, const T* src, uint32_t n, T* result, uint32_t* index, uint32_t batch,

@@ -1137,6 +1137,62 @@ void arm_accumulate_f32(const float32_t *pSrc, uint32_t blockSize, float32_t *pR
 arm_status arm_sqrt_q15(q15_t in, q15_t *pOut);
 void arm_cmplx_mag_fast_q15(const q15_t *pSrc, q15_t *pDst, uint32_t numSamples);
 
+/* The basic math functions of basic_math_functions.h (BasicAdd, BasicSub, BasicMult, BasicOffset, BasicScale,
+ * BasicShift, BasicClip, BasicAbs, BasicNegate, BasicDotProd, And, Or, Xor, Not), bit-exact with the reference's
+ * scalar branches (built with ARM_MATH_LOOPUNROLL, no ARM_MATH_DSP).  Host or device pointers, synchronous; pDst may
+ * be a source exactly.
+ *   f32   a + b, a - b, a * b, x + offset, x * scale, each rounded once; abs clears the sign bit (-0.0 -> +0.0),
+ *         negate flips it; dot_prod is one ordered chain sum = sum + a*b from 0.0f, the product rounded before the add.
+ *   q31   add / sub / offset saturate to 32 bits.  mult: __SSAT((a*b) >> 32, 31) << 1 (the low bit is 0).  scale:
+ *         in = (x * scaleFract) >> 32, then in << (shift + 1) saturated (0x7FFFFFFF ^ (in >> 31) when bits are lost),
+ *         or an arithmetic in >> -(shift + 1).  shift: the same on x with shiftBits.  dot_prod: every product >> 14
+ *         summed into 64 bits (16.48), mod 2^64.
+ *   q15   __SSAT(.., 16) of a + b, a - b, (a*b) >> 15, x + offset, (x * scaleFract) >> (15 - shift).  shift left:
+ *         __SSAT((q31_t)x << shiftBits, 16), the 32-bit shift wrapping first (counts above 16 show it); right:
+ *         arithmetic.  dot_prod: the exact products summed into 64 bits (34.30).
+ *   q7    as q15 with 8 bits: (a*b) >> 7, (x * scaleFract) >> (7 - shift).  dot_prod: a 32-bit sum (18.14), in range
+ *         up to 131071 words at full scale.
+ *   abs / negate of the most negative word give the most positive.  clip: x > high ? high : x < low ? low : x; a NaN
+ *         passes through, and with low > high the first comparison wins.
+ *   and / or / xor / not on uint32_t, uint16_t, uint8_t words.
+ * Shift counts: the ones at which the reference's C is defined (a count below 32 either way on its promoted int
+ * operands): arm_shift_* -31 .. 31, arm_scale_q31 -32 .. 30, arm_scale_q15 -16 .. 15, arm_scale_q7 -24 .. 7.  Outside,
+ * and for a null pointer, nothing is written and arm_mi355x_last_error() is set.  With device pointers an output
+ * that overlaps a source other than exactly is refused in the same way.  blockSize == 0 writes nothing (dot_prod
+ * stores 0).
+ * Left out: the f16 / f64 forms. */
+#define MI355X_DECL_BASIC(SUF, T, DR)                                                        \
+  void arm_add_##SUF(const T *pSrcA, const T *pSrcB, T *pDst, uint32_t blockSize);           \
+  void arm_sub_##SUF(const T *pSrcA, const T *pSrcB, T *pDst, uint32_t blockSize);           \
+  void arm_mult_##SUF(const T *pSrcA, const T *pSrcB, T *pDst, uint32_t blockSize);          \
+  void arm_offset_##SUF(const T *pSrc, T offset, T *pDst, uint32_t blockSize);               \
+  void arm_clip_##SUF(const T *pSrc, T *pDst, T low, T high, uint32_t numSamples);           \
+  void arm_abs_##SUF(const T *pSrc, T *pDst, uint32_t blockSize);                            \
+  void arm_negate_##SUF(const T *pSrc, T *pDst, uint32_t blockSize);                         \
+  void arm_dot_prod_##SUF(const T *pSrcA, const T *pSrcB, uint32_t blockSize, DR *result);
+#define MI355X_DECL_BASIC_FIXED(SUF, T)                                                              \
+  void arm_scale_##SUF(const T *pSrc, T scaleFract, int8_t shift, T *pDst, uint32_t blockSize);      \
+  void arm_shift_##SUF(const T *pSrc, int8_t shiftBits, T *pDst, uint32_t blockSize);
+#define MI355X_DECL_BITWISE(SUF, T)                                                          \
+  void arm_and_##SUF(const T *pSrcA, const T *pSrcB, T *pDst, uint32_t blockSize);           \
+  void arm_or_##SUF(const T *pSrcA, const T *pSrcB, T *pDst, uint32_t blockSize);            \
+  void arm_xor_##SUF(const T *pSrcA, const T *pSrcB, T *pDst, uint32_t blockSize);           \
+  void arm_not_##SUF(const T *pSrc, T *pDst, uint32_t blockSize);
+MI355X_DECL_BASIC(f32, float32_t, float32_t)
+MI355X_DECL_BASIC(q31, q31_t, q63_t)
+MI355X_DECL_BASIC(q15, q15_t, q63_t)
+MI355X_DECL_BASIC(q7, q7_t, q31_t)
+MI355X_DECL_BASIC_FIXED(q31, q31_t)
+MI355X_DECL_BASIC_FIXED(q15, q15_t)
+MI355X_DECL_BASIC_FIXED(q7, q7_t)
+MI355X_DECL_BITWISE(u32, uint32_t)
+MI355X_DECL_BITWISE(u16, uint16_t)
+MI355X_DECL_BITWISE(u8, uint8_t)
+#undef MI355X_DECL_BITWISE
+#undef MI355X_DECL_BASIC_FIXED
+#undef MI355X_DECL_BASIC
+void arm_scale_f32(const float32_t *pSrc, float32_t scale, float32_t *pDst, uint32_t blockSize);
+
 #ifdef __cplusplus
 }
 #endif

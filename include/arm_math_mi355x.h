@@ -459,6 +459,61 @@ arm_status arm_accumulate_f32_batch(const float32_t *d_src, uint32_t blockSize, 
 arm_status arm_cmplx_mag_fast_q15_batch(const q15_t *d_src, q15_t *d_dst, uint32_t numSamples, uint32_t batch,
                                         void *stream);
 
+/* Batched basic math (arm_math.h: "The basic math functions").  Element-wise: item i is the blockSize contiguous
+ * words at d_src + i * blockSize and d_dst + i * blockSize, so the call runs over batch * blockSize words as one
+ * flat array (16-byte loads and stores when every pointer is 16-byte aligned, single elements otherwise); one scalar
+ * (offset, scale and shift, low and high) serves the whole call.  Device pointers, stream-ordered.
+ * arm_dot_prod_*_batch: d_result[i] = the dot product of d_a + i * blockSize and d_b + i * bStride (words); bStride
+ * 0 means one d_b for every item (a bank of signals against one template), otherwise bStride >= blockSize;
+ * blockSize == 0 stores zeros.  The integer forms use the lanes-per-item mapping of arm_mse_*_batch, the f32 form
+ * the ordered chains of arm_mse_f32_batch (one wave per item below 4096 items, one lane per item from there on).
+ * ARM_MATH_ARGUMENT_ERROR on a null pointer, on a shift outside the drop-in's range, on bStride < blockSize, and on
+ * an output that overlaps a source (d_dst may equal a source exactly); batch == 0 is a successful no-op. */
+#define MI355X_DECL_BASIC_BATCH(SUF, T, DR)                                                                      \
+  arm_status arm_add_##SUF##_batch(const T *d_srcA, const T *d_srcB, T *d_dst, uint32_t blockSize, uint32_t batch, \
+                                   void *stream);                                                                \
+  arm_status arm_sub_##SUF##_batch(const T *d_srcA, const T *d_srcB, T *d_dst, uint32_t blockSize, uint32_t batch, \
+                                   void *stream);                                                                \
+  arm_status arm_mult_##SUF##_batch(const T *d_srcA, const T *d_srcB, T *d_dst, uint32_t blockSize,              \
+                                    uint32_t batch, void *stream);                                               \
+  arm_status arm_offset_##SUF##_batch(const T *d_src, T offset, T *d_dst, uint32_t blockSize, uint32_t batch,    \
+                                      void *stream);                                                             \
+  arm_status arm_clip_##SUF##_batch(const T *d_src, T *d_dst, T low, T high, uint32_t numSamples, uint32_t batch, \
+                                    void *stream);                                                               \
+  arm_status arm_abs_##SUF##_batch(const T *d_src, T *d_dst, uint32_t blockSize, uint32_t batch, void *stream);  \
+  arm_status arm_negate_##SUF##_batch(const T *d_src, T *d_dst, uint32_t blockSize, uint32_t batch,              \
+                                      void *stream);                                                             \
+  arm_status arm_dot_prod_##SUF##_batch(const T *d_a, const T *d_b, uint32_t bStride, uint32_t blockSize,        \
+                                        DR *d_result, uint32_t batch, void *stream);
+#define MI355X_DECL_BASIC_FIXED_BATCH(SUF, T)                                                                    \
+  arm_status arm_scale_##SUF##_batch(const T *d_src, T scaleFract, int8_t shift, T *d_dst, uint32_t blockSize,   \
+                                     uint32_t batch, void *stream);                                              \
+  arm_status arm_shift_##SUF##_batch(const T *d_src, int8_t shiftBits, T *d_dst, uint32_t blockSize,             \
+                                     uint32_t batch, void *stream);
+#define MI355X_DECL_BITWISE_BATCH(SUF, T)                                                                        \
+  arm_status arm_and_##SUF##_batch(const T *d_srcA, const T *d_srcB, T *d_dst, uint32_t blockSize, uint32_t batch, \
+                                   void *stream);                                                                \
+  arm_status arm_or_##SUF##_batch(const T *d_srcA, const T *d_srcB, T *d_dst, uint32_t blockSize, uint32_t batch, \
+                                  void *stream);                                                                 \
+  arm_status arm_xor_##SUF##_batch(const T *d_srcA, const T *d_srcB, T *d_dst, uint32_t blockSize, uint32_t batch, \
+                                   void *stream);                                                                \
+  arm_status arm_not_##SUF##_batch(const T *d_src, T *d_dst, uint32_t blockSize, uint32_t batch, void *stream);
+MI355X_DECL_BASIC_BATCH(f32, float32_t, float32_t)
+MI355X_DECL_BASIC_BATCH(q31, q31_t, q63_t)
+MI355X_DECL_BASIC_BATCH(q15, q15_t, q63_t)
+MI355X_DECL_BASIC_BATCH(q7, q7_t, q31_t)
+MI355X_DECL_BASIC_FIXED_BATCH(q31, q31_t)
+MI355X_DECL_BASIC_FIXED_BATCH(q15, q15_t)
+MI355X_DECL_BASIC_FIXED_BATCH(q7, q7_t)
+MI355X_DECL_BITWISE_BATCH(u32, uint32_t)
+MI355X_DECL_BITWISE_BATCH(u16, uint16_t)
+MI355X_DECL_BITWISE_BATCH(u8, uint8_t)
+#undef MI355X_DECL_BITWISE_BATCH
+#undef MI355X_DECL_BASIC_FIXED_BATCH
+#undef MI355X_DECL_BASIC_BATCH
+arm_status arm_scale_f32_batch(const float32_t *d_src, float32_t scale, float32_t *d_dst, uint32_t blockSize,
+                               uint32_t batch, void *stream);
+
 /* Multi-GPU complex FFT (SURVEY §8b "a multi-GPU entry point"; per item: arm_cfft_f32 /
  * _q31 / _q15, transform_functions.h:456-460).  Shard s of `nshards` is batch[s] contiguous
  * transforms at DEVICE pointer d_p1[s] on HIP device devices[s] (a device may appear in
