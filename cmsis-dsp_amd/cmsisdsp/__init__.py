@@ -728,6 +728,59 @@ for _t in ("u32", "u16", "u8"):
         globals()[_n] = _basic_math(_n, f"cmsisdsp_basic.c cmsis_{_n} {_doc} -> pDst; blockSize = len(pSrc).")
 
 
+# ------------------------------------------------------------------ support functions (cmsisdsp_support.c)
+class arm_sort_instance_f32(_Instance):
+    """cmsisdsp_support.c arm_sort_instance_f32(alg=0, dir=0) with the accessors alg() and dir()."""
+    _struct = _abi.arm_sort_instance_f32
+
+    def __init__(self, alg=0, dir=0):
+        super().__init__()
+        self._s.alg, self._s.dir = int(alg), int(dir)
+
+
+def arm_sort_init_f32(S, alg, dir):
+    """cmsisdsp_support.c cmsis_arm_sort_init_f32 (S, alg, dir)."""
+    _amd.arm_sort_init_f32(S._s, alg, dir)
+
+
+def arm_sort_f32(S, pSrc):
+    """cmsisdsp_support.c cmsis_arm_sort_f32 (S, pSrc) -> pDst; blockSize = len(pSrc)."""
+    return _amd.arm_sort_f32(S._s, _arr(pSrc, _np.float32))
+
+
+def _support_convert(name, src, dst):
+    def run(pSrc):
+        return _amd.arm_convert(src, dst, _arr(pSrc, _DT[src]))
+    run.__name__ = name
+    run.__doc__ = f"cmsisdsp_support.c cmsis_{name} (pSrc) -> pDst; blockSize = len(pSrc)."
+    return run
+
+
+def _support_fill(kind):
+    def run(value, blockSize):
+        return _amd.arm_fill(kind, value, blockSize)
+    run.__name__ = f"arm_fill_{kind}"
+    run.__doc__ = f"cmsisdsp_support.c cmsis_arm_fill_{kind} (value, blockSize) -> pDst."
+    return run
+
+
+for _s in ("f32", "q31", "q15", "q7"):
+    for _d in ("f32", "q31", "q15", "q7"):
+        _n = _amd._support_name(_s, _d)
+        globals()[_n] = _support_convert(_n, _s, _d)
+    globals()[f"arm_fill_{_s}"] = _support_fill(_s)
+
+
+def arm_weighted_average_f32(pSrcA, pSrcB):
+    """cmsisdsp_support.c cmsis_arm_weighted_average_f32 (in, weights) -> a Python float; blockSize = len(in)."""
+    return float(_amd.arm_weighted_average_f32(_arr(pSrcA, _np.float32), _arr(pSrcB, _np.float32)))
+
+
+def arm_barycenter_f32(pSrcA, pSrcB, nbVectors, vecDim):
+    """cmsisdsp_support.c cmsis_arm_barycenter_f32 (in, weights, nbVectors, vecDim) -> out [vecDim]."""
+    return _amd.arm_barycenter_f32(_arr(pSrcA, _np.float32), _arr(pSrcB, _np.float32), int(nbVectors), int(vecDim))
+
+
 def arm_sqrt_q15(x):
     """cmsisdsp_fastmath.c cmsis_arm_sqrt_q15 (in) -> (status, pOut)."""
     st, v = _amd.arm_sqrt_q15(x)

@@ -25,6 +25,7 @@ from ._abi import (arm_cfft_instance_f32, arm_cfft_instance_q15, arm_cfft_instan
                    arm_matrix_instance_q15, arm_matrix_instance_q7,
                    arm_matrix_instance_q31, arm_rfft_instance_q31, arm_rfft_instance_q15, ARM_MATH_SUCCESS,
                    ARM_MATH_ARGUMENT_ERROR, ARM_MATH_SIZE_MISMATCH)
+from ._abi import arm_sort_instance_f32, arm_merge_sort_instance_f32  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CMSISDSP_MI355X_LIB",
@@ -56,6 +57,7 @@ def _load():
     _abi.bind(lib, _abi.CMPLX_MATH)
     _abi.bind(lib, _abi.STATISTICS)
     _abi.bind(lib, _abi.BASIC_MATH)
+    _abi.bind(lib, _abi.SUPPORT)
     _abi.bind(lib, _abi.BATCHED)
     return lib
 
@@ -1338,6 +1340,133 @@ def dot_prod_batch(a, b, result, stream=None, b_stride=None):
         b_stride = 0 if b.dim() == 1 else b.shape[-1]
     _solve_call(f"arm_dot_prod_{kind}_batch", _cm_ptr(a), _cm_ptr(b), int(b_stride), a.shape[-1], _cm_ptr(result),
                 a.shape[0], _stream_ptr(stream))
+
+
+# ---- support functions: conversions, copy, fill, sort, weighted average, barycenter -----------------------------
+ARM_SORT_BITONIC, ARM_SORT_BUBBLE, ARM_SORT_HEAP, ARM_SORT_INSERTION, ARM_SORT_QUICK, ARM_SORT_SELECTION = range(6)
+ARM_SORT_DESCENDING, ARM_SORT_ASCENDING = 0, 1
+
+
+def _support_name(src_kind, dst_kind):
+    if src_kind == dst_kind:
+        return f"arm_copy_{src_kind}"
+    return f"arm_{_abi.SUPPORT_NAMES[src_kind]}_to_{_abi.SUPPORT_NAMES[dst_kind]}"
+
+
+def arm_convert(src_kind, dst_kind, src):
+    """arm_<src>_to_<dst> (kinds f32, q31, q15, q7; equal kinds: arm_copy_<kind>) of a numpy vector (drop-in)."""
+    name = _support_name(src_kind, dst_kind)
+    s = _cm_src(src_kind, src)
+    d = np.zeros(s.size, dtype=_MAT_DT[dst_kind])
+    getattr(lib, name)(s.ctypes.data, d.ctypes.data, s.size)
+    _check_void(name)
+    return d
+
+
+def arm_fill(kind, value, block_size):
+    """arm_fill_<kind>: block_size words of value (drop-in, numpy)."""
+    d = np.zeros(int(block_size), dtype=_MAT_DT[kind])
+    getattr(lib, f"arm_fill_{kind}")((float if kind == "f32" else int)(value), d.ctypes.data, d.size)
+    _check_void(f"arm_fill_{kind}")
+    return d
+
+
+def arm_sort_init_f32(S, alg, dir):
+    lib.arm_sort_init_f32(C.byref(S), int(alg), int(dir))
+
+
+def arm_merge_sort_init_f32(S, dir, buffer=None):
+    """buffer: a float32 numpy array the caller keeps alive, or None; the sort neither reads nor writes it."""
+    lib.arm_merge_sort_init_f32(C.byref(S), int(dir), None if buffer is None else buffer.ctypes.data)
+
+
+def _arm_sort(name, S, src):
+    s = _cm_src("f32", src)
+    d = np.zeros(s.size, dtype=np.float32)
+    getattr(lib, name)(C.byref(S), s.ctypes.data, d.ctypes.data, s.size)
+    _check_void(name)
+    return d
+
+
+def arm_sort_f32(S, src):
+    """The float32 vector sorted in S.dir by the IEEE total order (arm_sort_f32; S.alg only selects among equal
+    results)."""
+    return _arm_sort("arm_sort_f32", S, src)
+
+
+def arm_merge_sort_f32(S, src):
+    """As arm_sort_f32 through arm_merge_sort_f32; S.buffer is not used."""
+    return _arm_sort("arm_merge_sort_f32", S, src)
+
+
+def arm_weighted_average_f32(src, weights):
+    """sum(src * weights) / sum(weights) in float32, two ordered chains (arm_weighted_average_f32)."""
+    a, w = _cm_src("f32", src), _cm_src("f32", weights)
+    if w.size != a.size:
+        raise ValueError(f"arm_weighted_average_f32: weights has {w.size} words, in {a.size}")
+    r = lib.arm_weighted_average_f32(a.ctypes.data, w.ctypes.data, a.size)
+    _check_void("arm_weighted_average_f32")
+    return np.float32(r)
+
+
+def arm_barycenter_f32(src, weights, nb_vectors, vec_dim):
+    """The barycenter [vec_dim] of nb_vectors vectors (rows of src) under weights (arm_barycenter_f32)."""
+    a, w = _cm_src("f32", src), _cm_src("f32", weights)
+    if a.size != nb_vectors * vec_dim or w.size != nb_vectors:
+        raise ValueError("arm_barycenter_f32: in holds nbVectors * vecDim words and weights nbVectors")
+    d = np.zeros(vec_dim, dtype=np.float32)
+    lib.arm_barycenter_f32(a.ctypes.data, w.ctypes.data, d.ctypes.data, nb_vectors, vec_dim)
+    _check_void("arm_barycenter_f32")
+    return d
+
+
+def convert_batch(src, dst, stream=None):
+    """dst = src converted between float32 / int32 (q31) / int16 (q15) / int8 (q7) for contiguous device tensors
+    [batch, N] (arm_<a>_to_<b>_batch; equal types: arm_copy_*_batch).  dst may be src where the widths are equal."""
+    n = src.shape[-1]
+    _solve_call(_support_name(_mat_kind(src), _mat_kind(dst)) + "_batch", _cm_ptr(src), _cm_ptr(dst), n,
+                src.numel() // n if n else 0, _stream_ptr(stream))
+
+
+def copy_batch(src, dst, stream=None):
+    """dst = src (arm_copy_*_batch)."""
+    if src.dtype != dst.dtype:
+        raise TypeError("copy_batch: src and dst differ in type")
+    convert_batch(src, dst, stream)
+
+
+def fill_batch(value, dst, stream=None):
+    """Every word of dst [batch, N] = value (arm_fill_*_batch)."""
+    kind = _mat_kind(dst)
+    n = dst.shape[-1]
+    _solve_call(f"arm_fill_{kind}_batch", (float if kind == "f32" else int)(value), _cm_ptr(dst), n,
+                dst.numel() // n if n else 0, _stream_ptr(stream))
+
+
+def sort_batch(src, dst, dir=ARM_SORT_ASCENDING, stream=None, merge=False):
+    """dst[i] = src[i] sorted in dir by the IEEE total order, for contiguous float32 device tensors [batch, N]
+    (arm_sort_f32_batch; merge=True: arm_merge_sort_f32_batch, the same kernels).  dst may be src."""
+    n = src.shape[-1]
+    _solve_call("arm_merge_sort_f32_batch" if merge else "arm_sort_f32_batch", _cm_ptr(src), _cm_ptr(dst), n,
+                int(dir), src.numel() // n if n else 0, _stream_ptr(stream))
+
+
+def weighted_average_batch(src, weights, result, stream=None, w_stride=None):
+    """result[i] = arm_weighted_average_f32 of src[i] [N] under weights [N] (one for every item) or [batch, N].
+    w_stride (words) overrides the distance between the items' weight vectors."""
+    if w_stride is None:
+        w_stride = 0 if weights.dim() == 1 else weights.shape[-1]
+    _solve_call("arm_weighted_average_f32_batch", _cm_ptr(src), _cm_ptr(weights), int(w_stride), src.shape[-1],
+                _cm_ptr(result), src.shape[0], _stream_ptr(stream))
+
+
+def barycenter_batch(src, weights, out, stream=None, w_stride=None):
+    """out[i] [vecDim] = the barycenter of src[i] [nbVectors, vecDim] under weights [nbVectors] (one for every item)
+    or [batch, nbVectors] (arm_barycenter_f32_batch)."""
+    if w_stride is None:
+        w_stride = 0 if weights.dim() == 1 else weights.shape[-1]
+    _solve_call("arm_barycenter_f32_batch", _cm_ptr(src), _cm_ptr(weights), int(w_stride), _cm_ptr(out),
+                src.shape[1], src.shape[2], src.shape[0], _stream_ptr(stream))
 
 
 def mat_mult_batch(a, b, c, stream=None, fast=False):

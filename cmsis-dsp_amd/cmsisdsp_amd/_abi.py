@@ -441,6 +441,39 @@ for _t in BITWISE_TYPES:
         BASIC_MATH[f"arm_{_n}_{_t}"] = (None, _a)
         BASIC_MATH[f"arm_{_n}_{_t}_batch"] = (C.c_int, _a + [_u32, _vp])
 
+# Support functions: 24 drop-ins with their _batch forms and the two sort inits.  The product only
+# (tests/golden/support.npz holds the reference's outputs).  arm_sort_alg / arm_sort_dir are C enums (int).
+class arm_sort_instance_f32(C.Structure):
+    _fields_ = [("alg", C.c_int), ("dir", C.c_int)]
+
+
+class arm_merge_sort_instance_f32(C.Structure):
+    _fields_ = [("dir", C.c_int), ("buffer", C.c_void_p)]
+
+
+SUPPORT = {}
+SUPPORT_NAMES = {"f32": "float", "q31": "q31", "q15": "q15", "q7": "q7"}      # the type's name in arm_<a>_to_<b>
+for _s in BASIC_TYPES:
+    for _d in BASIC_TYPES:
+        if _s != _d:
+            _n = f"arm_{SUPPORT_NAMES[_s]}_to_{SUPPORT_NAMES[_d]}"
+            SUPPORT[_n] = (None, [_vp, _vp, _u32])
+            SUPPORT[_n + "_batch"] = (C.c_int, [_vp, _vp, _u32, _u32, _vp])
+    SUPPORT[f"arm_copy_{_s}"] = (None, [_vp, _vp, _u32])
+    SUPPORT[f"arm_copy_{_s}_batch"] = (C.c_int, [_vp, _vp, _u32, _u32, _vp])
+    SUPPORT[f"arm_fill_{_s}"] = (None, [BASIC_SCALAR[_s], _vp, _u32])
+    SUPPORT[f"arm_fill_{_s}_batch"] = (C.c_int, [BASIC_SCALAR[_s], _vp, _u32, _u32, _vp])
+SUPPORT["arm_sort_init_f32"] = (None, [P(arm_sort_instance_f32), C.c_int, C.c_int])
+SUPPORT["arm_sort_f32"] = (None, [P(arm_sort_instance_f32), _vp, _vp, _u32])
+SUPPORT["arm_merge_sort_init_f32"] = (None, [P(arm_merge_sort_instance_f32), C.c_int, _vp])
+SUPPORT["arm_merge_sort_f32"] = (None, [P(arm_merge_sort_instance_f32), _vp, _vp, _u32])
+SUPPORT["arm_sort_f32_batch"] = (C.c_int, [_vp, _vp, _u32, C.c_int, _u32, _vp])
+SUPPORT["arm_merge_sort_f32_batch"] = (C.c_int, [_vp, _vp, _u32, C.c_int, _u32, _vp])
+SUPPORT["arm_weighted_average_f32"] = (C.c_float, [_vp, _vp, _u32])
+SUPPORT["arm_weighted_average_f32_batch"] = (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp])
+SUPPORT["arm_barycenter_f32"] = (None, [_vp, _vp, _vp, _u32, _u32])
+SUPPORT["arm_barycenter_f32_batch"] = (C.c_int, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp])
+
 # per-length MFCC init functions (the product and the reference build; the oracle has the
 # generic init only)
 MFCC_LEN = {f"arm_mfcc_init_{n}_f32": (C.c_int, [P(arm_mfcc_instance_f32), C.c_uint32, C.c_uint32, C.c_void_p,

@@ -1709,6 +1709,96 @@ arm_status bm_dot(const T* a, const T* b, uint32_t bStride, uint32_t n, R* resul
     return run((const T*)bufs[0].d, (const T*)bufs[1].d, (R*)bufs[2].d, st);
   });
 }
+
+// ---- support functions (support.hip, sort.hip; the weighted average: statistics.hip) --------------
+// support_functions.h.  sync and the null / overlap rules as the basic math functions; dst may be src exactly where
+// both element widths are equal (float_to_q31, q31_to_float, copy) and in the sorts.
+template <typename S, typename D>
+arm_status sp_convert(const S* s, D* d, uint32_t n, bool sync, uint32_t batch, void* stream, const char* what) {
+  if (sync && (!s || !d)) return cm_null(true, what);
+  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
+  if (!s || !d) return ARM_MATH_ARGUMENT_ERROR;
+  const size_t count = (size_t)n * batch, sb = sizeof(S) * count, db = sizeof(D) * count;
+  auto run = [&](const S* ds, D* dd, hipStream_t st) -> hipError_t {
+    if (cm_overlaps(dd, db, ds, sb, sizeof(S) == sizeof(D))) return hipErrorInvalidValue;
+    return support_convert_launch<S, D>(ds, dd, count, st);
+  };
+  if (!sync) return batch_status(run(s, d, (hipStream_t)stream), what);
+  SolveBuf bufs[2] = {{const_cast<S*>(s), sb, true, false}, {d, db, false, true}};
+  return mat_staged_sync(bufs, 2, what, [&](hipStream_t st) { return run((const S*)bufs[0].d, (D*)bufs[1].d, st); });
+}
+
+template <typename T>
+arm_status sp_fill(T value, T* d, uint32_t n, bool sync, uint32_t batch, void* stream, const char* what) {
+  if (sync && !d) return cm_null(true, what);
+  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
+  if (!d) return ARM_MATH_ARGUMENT_ERROR;
+  const size_t count = (size_t)n * batch;
+  if (!sync) return batch_status(support_fill_launch<T>(value, d, count, (hipStream_t)stream), what);
+  SolveBuf bufs[1] = {{d, sizeof(T) * count, false, true}};
+  return mat_staged_sync(bufs, 1, what,
+                         [&](hipStream_t st) { return support_fill_launch<T>(value, (T*)bufs[0].d, count, st); });
+}
+
+// dir: ARM_SORT_DESCENDING (0) or ARM_SORT_ASCENDING (1), anything else is refused.
+arm_status sp_sort(int dir, const float* src, float* dst, uint32_t n, bool sync, uint32_t batch, void* stream,
+                   const char* what) {
+  if (sync && (!src || !dst)) return cm_null(true, what);
+  if ((dir != 0 && dir != 1) || n > 0x80000000u) return cm_null(sync, what);
+  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
+  if (!src || !dst) return ARM_MATH_ARGUMENT_ERROR;
+  const size_t bytes = sizeof(float) * n * batch;
+  auto run = [&](const float* ds, float* dd, hipStream_t st) -> hipError_t {
+    if (cm_overlaps(dd, bytes, ds, bytes, true)) return hipErrorInvalidValue;
+    return sort_launch((const uint32_t*)ds, (uint32_t*)dd, n, dir == 1, batch, st);
+  };
+  if (!sync) return batch_status(run(src, dst, (hipStream_t)stream), what);
+  SolveBuf bufs[2] = {{const_cast<float*>(src), bytes, true, false}, {dst, bytes, false, true}};
+  return mat_staged_sync(bufs, 2, what,
+                         [&](hipStream_t st) { return run((const float*)bufs[0].d, (float*)bufs[1].d, st); });
+}
+
+// wStride (words; the drop-in passes n): 0 shares one weight vector, otherwise >= n.  n == 0 stores 0 / 0.
+arm_status sp_wavg(const float* a, const float* w, uint32_t wStride, uint32_t n, float* result, bool sync,
+                   uint32_t batch, void* stream, const char* what) {
+  if (sync && (!a || !w || !result)) return cm_null(true, what);
+  if (wStride != 0 && wStride < n) return cm_null(sync, what);
+  if (batch == 0) return ARM_MATH_SUCCESS;
+  if (!a || !w || !result) return ARM_MATH_ARGUMENT_ERROR;
+  const size_t ab = sizeof(float) * n * batch, rb = sizeof(float) * batch;
+  const size_t wb = sizeof(float) * ((size_t)wStride * (batch - 1) + n);
+  auto run = [&](const float* da, const float* dw, float* dr, hipStream_t st) -> hipError_t {
+    if (cm_overlaps(dr, rb, da, ab, false) || cm_overlaps(dr, rb, dw, wb, false)) return hipErrorInvalidValue;
+    return weighted_average_launch(da, dw, wStride, n, dr, batch, st);
+  };
+  if (!sync) return batch_status(run(a, w, result, (hipStream_t)stream), what);
+  SolveBuf bufs[3] = {{const_cast<float*>(a), ab, n != 0, false}, {const_cast<float*>(w), wb, n != 0, false},
+                      {result, rb, false, true}};
+  return mat_staged_sync(bufs, 3, what, [&](hipStream_t st) {
+    return run((const float*)bufs[0].d, (const float*)bufs[1].d, (float*)bufs[2].d, st);
+  });
+}
+
+// wStride as sp_wavg against nbVectors.  vecDim == 0 writes nothing; nbVectors == 0 stores 0 / 0.
+arm_status sp_barycenter(const float* in, const float* w, uint32_t wStride, float* out, uint32_t nv, uint32_t dim,
+                         bool sync, uint32_t batch, void* stream, const char* what) {
+  if (sync && (!in || !w || !out)) return cm_null(true, what);
+  if (wStride != 0 && wStride < nv) return cm_null(sync, what);
+  if (batch == 0 || dim == 0) return ARM_MATH_SUCCESS;
+  if (!in || !w || !out) return ARM_MATH_ARGUMENT_ERROR;
+  const size_t ib = sizeof(float) * nv * dim * batch, ob = sizeof(float) * dim * batch;
+  const size_t wb = sizeof(float) * ((size_t)wStride * (batch - 1) + nv);
+  auto run = [&](const float* di, const float* dw, float* dout, hipStream_t st) -> hipError_t {
+    if (cm_overlaps(dout, ob, di, ib, false) || cm_overlaps(dout, ob, dw, wb, false)) return hipErrorInvalidValue;
+    return barycenter_launch(di, dw, wStride, dout, nv, dim, batch, st);
+  };
+  if (!sync) return batch_status(run(in, w, out, (hipStream_t)stream), what);
+  SolveBuf bufs[3] = {{const_cast<float*>(in), ib, nv != 0, false}, {const_cast<float*>(w), wb, nv != 0, false},
+                      {out, ob, false, true}};
+  return mat_staged_sync(bufs, 3, what, [&](hipStream_t st) {
+    return run((const float*)bufs[0].d, (const float*)bufs[1].d, (float*)bufs[2].d, st);
+  });
+}
 }  // namespace
 
 extern "C" {
@@ -2484,6 +2574,91 @@ MI355X_BM_BITS(u8, uint8_t)
 #undef MI355X_BM_OFFSET
 #undef MI355X_BM_1
 #undef MI355X_BM_2
+
+// ---- support functions; sp_convert .. sp_barycenter precede the C block ----
+#define MI355X_SP_TO(SN, ST, SCT, DN, DT, DCT)                                                                   \
+  void arm_##SN##_to_##DN(const ST* pSrc, DT* pDst, uint32_t blockSize) {                                        \
+    sp_convert<SCT, DCT>((const SCT*)pSrc, (DCT*)pDst, blockSize, true, 1, nullptr, "arm_" #SN "_to_" #DN);      \
+  }                                                                                                              \
+  arm_status arm_##SN##_to_##DN##_batch(const ST* d_src, DT* d_dst, uint32_t blockSize, uint32_t batch,          \
+                                        void* stream) {                                                          \
+    return sp_convert<SCT, DCT>((const SCT*)d_src, (DCT*)d_dst, blockSize, false, batch, stream,                 \
+                                "arm_" #SN "_to_" #DN "_batch");                                                 \
+  }
+#define MI355X_SP_COPY(SUF, T, CT)                                                                               \
+  void arm_copy_##SUF(const T* pSrc, T* pDst, uint32_t blockSize) {                                              \
+    sp_convert<CT, CT>((const CT*)pSrc, (CT*)pDst, blockSize, true, 1, nullptr, "arm_copy_" #SUF);               \
+  }                                                                                                              \
+  arm_status arm_copy_##SUF##_batch(const T* d_src, T* d_dst, uint32_t blockSize, uint32_t batch, void* stream) { \
+    return sp_convert<CT, CT>((const CT*)d_src, (CT*)d_dst, blockSize, false, batch, stream,                     \
+                              "arm_copy_" #SUF "_batch");                                                        \
+  }                                                                                                              \
+  void arm_fill_##SUF(T value, T* pDst, uint32_t blockSize) {                                                    \
+    sp_fill<CT>((CT)value, (CT*)pDst, blockSize, true, 1, nullptr, "arm_fill_" #SUF);                            \
+  }                                                                                                              \
+  arm_status arm_fill_##SUF##_batch(T value, T* d_dst, uint32_t blockSize, uint32_t batch, void* stream) {       \
+    return sp_fill<CT>((CT)value, (CT*)d_dst, blockSize, false, batch, stream, "arm_fill_" #SUF "_batch");       \
+  }
+MI355X_SP_TO(float, float32_t, float, q31, q31_t, int32_t)
+MI355X_SP_TO(float, float32_t, float, q15, q15_t, int16_t)
+MI355X_SP_TO(float, float32_t, float, q7, q7_t, int8_t)
+MI355X_SP_TO(q31, q31_t, int32_t, float, float32_t, float)
+MI355X_SP_TO(q31, q31_t, int32_t, q15, q15_t, int16_t)
+MI355X_SP_TO(q31, q31_t, int32_t, q7, q7_t, int8_t)
+MI355X_SP_TO(q15, q15_t, int16_t, float, float32_t, float)
+MI355X_SP_TO(q15, q15_t, int16_t, q31, q31_t, int32_t)
+MI355X_SP_TO(q15, q15_t, int16_t, q7, q7_t, int8_t)
+MI355X_SP_TO(q7, q7_t, int8_t, float, float32_t, float)
+MI355X_SP_TO(q7, q7_t, int8_t, q31, q31_t, int32_t)
+MI355X_SP_TO(q7, q7_t, int8_t, q15, q15_t, int16_t)
+MI355X_SP_COPY(f32, float32_t, float)
+MI355X_SP_COPY(q31, q31_t, int32_t)
+MI355X_SP_COPY(q15, q15_t, int16_t)
+MI355X_SP_COPY(q7, q7_t, int8_t)
+#undef MI355X_SP_COPY
+#undef MI355X_SP_TO
+
+// S->alg selects among equal results: a value of arm_sort_alg sorts, any other is the no-op of the reference's switch.
+void arm_sort_f32(const arm_sort_instance_f32* S, float32_t* pSrc, float32_t* pDst, uint32_t blockSize) {
+  if (!S) { cm_null(true, "arm_sort_f32"); return; }
+  if ((int)S->alg < (int)ARM_SORT_BITONIC || (int)S->alg > (int)ARM_SORT_SELECTION) return;
+  sp_sort((int)S->dir, pSrc, pDst, blockSize, true, 1, nullptr, "arm_sort_f32");
+}
+// S->buffer is neither read nor written.
+void arm_merge_sort_f32(const arm_merge_sort_instance_f32* S, float32_t* pSrc, float32_t* pDst, uint32_t blockSize) {
+  if (!S) { cm_null(true, "arm_merge_sort_f32"); return; }
+  sp_sort((int)S->dir, pSrc, pDst, blockSize, true, 1, nullptr, "arm_merge_sort_f32");
+}
+arm_status arm_sort_f32_batch(const float32_t* d_src, float32_t* d_dst, uint32_t blockSize, arm_sort_dir dir,
+                              uint32_t batch, void* stream) {
+  return sp_sort((int)dir, d_src, d_dst, blockSize, false, batch, stream, "arm_sort_f32_batch");
+}
+arm_status arm_merge_sort_f32_batch(const float32_t* d_src, float32_t* d_dst, uint32_t blockSize, arm_sort_dir dir,
+                                    uint32_t batch, void* stream) {
+  return sp_sort((int)dir, d_src, d_dst, blockSize, false, batch, stream, "arm_merge_sort_f32_batch");
+}
+float32_t arm_weighted_average_f32(const float32_t* in, const float32_t* weights, uint32_t blockSize) {
+  float32_t r = 0.0f;
+  if (sp_wavg(in, weights, blockSize, blockSize, &r, true, 1, nullptr, "arm_weighted_average_f32") !=
+      ARM_MATH_SUCCESS)
+    return __builtin_nanf("");
+  return r;
+}
+arm_status arm_weighted_average_f32_batch(const float32_t* d_in, const float32_t* d_weights, uint32_t wStride,
+                                          uint32_t blockSize, float32_t* d_result, uint32_t batch, void* stream) {
+  return sp_wavg(d_in, d_weights, wStride, blockSize, d_result, false, batch, stream,
+                 "arm_weighted_average_f32_batch");
+}
+void arm_barycenter_f32(const float32_t* in, const float32_t* weights, float32_t* out, uint32_t nbVectors,
+                        uint32_t vecDim) {
+  sp_barycenter(in, weights, nbVectors, out, nbVectors, vecDim, true, 1, nullptr, "arm_barycenter_f32");
+}
+arm_status arm_barycenter_f32_batch(const float32_t* d_in, const float32_t* d_weights, uint32_t wStride,
+                                    float32_t* d_out, uint32_t nbVectors, uint32_t vecDim, uint32_t batch,
+                                    void* stream) {
+  return sp_barycenter(d_in, d_weights, wStride, d_out, nbVectors, vecDim, false, batch, stream,
+                       "arm_barycenter_f32_batch");
+}
 
 // ---- convolution ------------------------------------------------------------------
 #define MI355X_CONV_FULL(NAME, T, CT, OP, VAR)                                                                  \

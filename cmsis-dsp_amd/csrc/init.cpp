@@ -297,4 +297,14 @@ void arm_mat_init_f32(arm_matrix_instance_f32* S, uint16_t nRows, uint16_t nColu
   S->pData = pData;
 }
 
+// ---- sort init (arm_sort_init_f32.c, arm_merge_sort_init_f32.c)
+void arm_sort_init_f32(arm_sort_instance_f32* S, arm_sort_alg alg, arm_sort_dir dir) {
+  S->alg = alg;
+  S->dir = dir;
+}
+void arm_merge_sort_init_f32(arm_merge_sort_instance_f32* S, arm_sort_dir dir, float32_t* buffer) {
+  S->dir = dir;
+  S->buffer = buffer;
+}
+
 }  // extern "C"

@@ -323,7 +323,7 @@ hipError_t search_launch(bool max, const T* src, uint32_t n, T* result, uint32_t
 // of sqrt_initial_lut_q31 (read by the q31 kStRms / kStStd only).  n == 0 stores what the empty sums give (the
 // caller refuses the integer forms that would divide by zero).  The float sums are ordered chains.
 enum : int { kStMean = 0, kStPower = 1, kStRms = 2, kStVar = 3, kStStd = 4, kStMse = 5, kStAccumulate = 6,
-             kStDot = 7 /* dot_prod_launch only */ };
+             kStDot = 7 /* dot_prod_launch only */, kStWavg = 8 /* weighted_average_launch only */ };
 template <typename T, typename R>
 hipError_t stat_sum_launch(int op, const T* a, const T* b, uint32_t n, R* result, uint32_t batch, const int32_t* lut,
                            hipStream_t st);
@@ -355,5 +355,31 @@ hipError_t basic_ew_launch(int op, const T* a, const T* b, T* d, size_t count, T
 template <typename T, typename R>
 hipError_t dot_prod_launch(const T* a, const T* b, size_t bStride, uint32_t n, R* result, uint32_t batch,
                            hipStream_t st);
+
+// The support functions, bit-exact with the reference's scalar branches (support.hip, sort.hip).
+// support_convert_launch<S, D>: d[i] = the reference's arm_<S>_to_<D> of s[i] over `count` words (the whole batch as
+// one flat array); S == D is arm_copy_*.  S, D: float, int32_t (q31), int16_t (q15), int8_t (q7).  d may equal s
+// exactly where the element widths are equal.  float -> q outside the range where the reference's C is defined
+// saturates by sign, NaN gives 0.
+template <typename S, typename D>
+hipError_t support_convert_launch(const S* s, D* d, size_t count, hipStream_t st);
+// d[i] = value over `count` words (arm_fill_*).
+template <typename T>
+hipError_t support_fill_launch(T value, T* d, size_t count, hipStream_t st);
+// out[i][d] = (sum_v in[i][v][d] * w_i[v]) / (sum_v w_i[v]), both sums ordered chains over v from 0.0f, the product
+// rounded before the add; w_i = w + i * wStride words (0: one weight vector for every item).
+hipError_t barycenter_launch(const float* in, const float* w, size_t wStride, float* out, uint32_t nbVectors,
+                             uint32_t vecDim, uint32_t batch, hipStream_t st);
+// result[i] = (sum_k a[i][k] * w_i[k]) / (sum_k w_i[k]): two ordered chains and one division (n == 0: 0 / 0).  An
+// operation (kStWavg) of the f32 chain kernels of statistics.hip.
+hipError_t weighted_average_launch(const float* a, const float* w, size_t wStride, uint32_t n, float* result,
+                                   uint32_t batch, hipStream_t st);
+// Sorts each of `batch` items of n 32-bit words (items n words apart) by the IEEE total order of the words read as
+// float32 (ascending: negative NaNs, -Inf .. -0.0, +0.0 .. +Inf, positive NaNs; descending: the reverse).  dst may
+// equal src exactly; otherwise src is only read.  n <= 2^31.
+constexpr uint32_t kSortWaveMax = 256;     // padded length up to which one wave sorts an item in registers
+constexpr uint32_t kSortLdsMax = 16384;    // padded length up to which one workgroup sorts an item in LDS (64 KiB)
+hipError_t sort_launch(const uint32_t* src, uint32_t* dst, uint32_t n, bool ascending, uint32_t batch,
+                       hipStream_t st);
 
 }  // namespace mi355x

@@ -24,6 +24,8 @@
 //   dot products   arm_dot_prod_* (kStDot) are one more operation of these kernels: the term is a*b (q31: >> 14), the
 //                  second source's items are bStride words apart (0: one for every item, which the lane form stages
 //                  once per row all the same; mse passes the item length).
+//   weighted mean  arm_weighted_average_f32 (kStWavg): the dot product's chain of in*w beside a second chain of w in
+//                  the same element order, then one IEEE division sum / wsum (blockSize 0: 0 / 0).
 #include <type_traits>
 
 #include "common.hpp"
@@ -37,7 +39,8 @@ namespace {
 
 template <typename T> constexpr bool kIsQ31 = std::is_same<T, int32_t>::value;
 template <int OP> constexpr bool kIsVar = OP == kStVar || OP == kStStd;
-template <int OP> constexpr bool kTwoSources = OP == kStMse || OP == kStDot;   // kStDot: arm_dot_prod_*
+// kStDot: arm_dot_prod_*, kStWavg: arm_weighted_average_f32
+template <int OP> constexpr bool kTwoSources = OP == kStMse || OP == kStDot || OP == kStWavg;
 
 __device__ __forceinline__ int32_t ssat8(int32_t v) { return v > 127 ? 127 : (v < -128 ? -128 : v); }
 
@@ -213,7 +216,7 @@ __device__ __forceinline__ float chain_term(float x, float y) {
   } else if constexpr (OP == kStMse) {
     const float d = x - y;
     return d * d;
-  } else if constexpr (OP == kStDot) {
+  } else if constexpr (OP == kStDot || OP == kStWavg) {
     return x * y;
   } else {
     return x;                                               // mean, accumulate, the mean pass of var / std
@@ -259,7 +262,7 @@ __global__ __launch_bounds__(kBlock) void sum_f32_wave_kernel(const float* pa, c
   const float* a = pa + (size_t)item * n;
   const float* b = kTwoSources<OP> ? pb + (size_t)item * bStride : a;
   const bool kept = kIsVar<OP> && n <= kVarKeep;
-  float sum = 0.0f;
+  float sum = 0.0f, wsum = 0.0f;                           // wsum: the weights' chain of kStWavg
   for (uint64_t k0 = 0; k0 < n; k0 += 64) {
     const uint32_t cnt = (uint32_t)min((uint64_t)64, n - k0);
     float x = 0.0f, y = 0.0f;
@@ -270,6 +273,11 @@ __global__ __launch_bounds__(kBlock) void sum_f32_wave_kernel(const float* pa, c
         if (kept) keep[w][k0 + lane] = x;                  // read back by this lane only
     }
     sum = chain_lanes(sum, chain_term<OP>(x, y), cnt);
+    if constexpr (OP == kStWavg) wsum = chain_lanes(wsum, y, cnt);
+  }
+  if constexpr (OP == kStWavg) {
+    if (lane == 0) result[item] = sum / wsum;
+    return;
   }
   if constexpr (kIsVar<OP>) {
     const float mean = sum / (float)n;
@@ -296,7 +304,7 @@ __global__ __launch_bounds__(kBlock) void sum_f32_lane_kernel(const float* pa, c
   const uint32_t item0 = blockIdx.x * (uint32_t)kBlock, item = item0 + threadIdx.x;
   const float* arow = am + threadIdx.x * LD;
   const float* brow = kTwoSrc ? bm + threadIdx.x * LD : arow;
-  float sum = 0.0f, mean = 0.0f;
+  float sum = 0.0f, mean = 0.0f, wsum = 0.0f;              // wsum: the weights' chain of kStWavg
 #pragma unroll
   for (int pass = 0; pass < (kIsVar<OP> ? 2 : 1); ++pass) {
     float acc = 0.0f;
@@ -320,12 +328,17 @@ __global__ __launch_bounds__(kBlock) void sum_f32_lane_kernel(const float* pa, c
             t = d * d;
           }
           acc = acc + t;
+          if constexpr (OP == kStWavg) wsum = wsum + brow[k];
         }
       }
       __syncthreads();
     }
     if (kIsVar<OP> && pass == 0) mean = acc / (float)n;
     sum = acc;
+  }
+  if constexpr (OP == kStWavg) {
+    if (item < batch) result[item] = sum / wsum;
+    return;
   }
   if (item < batch) result[item] = (kIsVar<OP> && n <= 1u) ? 0.0f : chain_finish<OP>(sum, n);
 }
@@ -341,7 +354,7 @@ constexpr bool stat_sum_exists() {
   constexpr bool f32 = std::is_same<T, float>::value, q7 = std::is_same<T, int8_t>::value;
   if (OP == kStPower || OP == kStDot) return std::is_same<R, typename PowerResult<T>::type>::value;
   if (!std::is_same<R, T>::value) return false;
-  if (OP == kStAccumulate) return f32;
+  if (OP == kStAccumulate || OP == kStWavg) return f32;
   if (OP == kStRms || OP == kStVar || OP == kStStd) return !q7;
   return OP == kStMean || OP == kStMse;
 }
@@ -417,6 +430,12 @@ template hipError_t dot_prod_launch<int16_t, int64_t>(const int16_t*, const int1
                                                       uint32_t, hipStream_t);
 template hipError_t dot_prod_launch<int8_t, int32_t>(const int8_t*, const int8_t*, size_t, uint32_t, int32_t*,
                                                      uint32_t, hipStream_t);
+
+hipError_t weighted_average_launch(const float* a, const float* w, size_t wStride, uint32_t n, float* result,
+                                   uint32_t batch, hipStream_t st) {
+  if (batch == 0) return hipSuccess;
+  return sum_run<kStWavg, float, float>(a, w, wStride, n, result, batch, nullptr, st);
+}
 
 template <typename T>
 hipError_t stat_search_launch(bool max, bool abs, const T* src, uint32_t n, T* result, uint32_t* index, uint32_t batch,

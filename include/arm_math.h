@@ -1193,6 +1193,76 @@ MI355X_DECL_BITWISE(u8, uint8_t)
 #undef MI355X_DECL_BASIC
 void arm_scale_f32(const float32_t *pSrc, float32_t scale, float32_t *pDst, uint32_t blockSize);
 
+/* The support functions of support_functions.h (float_to_x, q31_to_x, q15_to_x, q7_to_x, copy, Fill, Sorting,
+ * weightedaverage, barycenter).  Host or device pointers, synchronous.  Every word of the conversions, copy, fill,
+ * arm_weighted_average_f32 and arm_barycenter_f32 equals the reference's scalar branches (ARM_MATH_LOOPUNROLL, no
+ * ARM_MATH_ROUNDING, no ARM_MATH_DSP).
+ *   float -> q   the f32 product x * 2^31 / 2^15 / 2^7 (subnormals kept), truncated toward zero, then clipped to 32
+ *                bits or __SSAT to 16 / 8 bits.  The reference's C cast is undefined for NaN and outside |x| < 2^32
+ *                (q31), 65536 (q15), 2^24 (q7); there these functions saturate by sign and turn NaN into 0.
+ *   q -> float   (float)x / 2^31 / 2^15 / 2^7; q31 words above 2^24 round to nearest even (0x7FFFFFFF gives 1.0f).
+ *   q -> q       << 16, << 24, << 8 widening; arithmetic >> 16, >> 24, >> 8 narrowing.
+ *   pDst may equal pSrc exactly where both element widths are equal (float_to_q31, q31_to_float, copy); with device
+ *   pointers any other overlap is refused.  A refusal or a null pointer writes nothing and sets
+ *   arm_mi355x_last_error().  blockSize == 0 writes nothing.
+ *   sort         arm_sort_f32 and arm_merge_sort_f32 both run one bitonic network on the IEEE total order of the
+ *                words: ascending is negative NaNs, -Inf .. -0.0, +0.0 .. +Inf, positive NaNs; descending the reverse.
+ *                Without NaNs and without both signs of zero every output word equals the reference's (with both
+ *                zeros: equal as values and as multisets of words).  S->alg only selects among equal results (a value
+ *                outside arm_sort_alg is a no-op, as in the reference's switch); unlike the reference,
+ *                ARM_SORT_BITONIC also sorts when blockSize is no power of two and when dir is ARM_SORT_DESCENDING.
+ *                arm_merge_sort_f32 neither reads nor writes S->buffer.  pSrc is unchanged unless it is pDst.
+ *   arm_weighted_average_f32   sum(in * w) / sum(w): two ordered f32 chains from 0.0f, the product rounded before its
+ *                add, one division (blockSize 0: 0 / 0, a NaN; a failure also returns a NaN and sets the last error).
+ *   arm_barycenter_f32         out[d] = (sum_v in[v][d] * w[v]) / (sum_v w[v]), chains over v in order, a division.
+ * Left out: the f16 / f64 forms. */
+typedef enum {
+  ARM_SORT_BITONIC = 0,
+  ARM_SORT_BUBBLE = 1,
+  ARM_SORT_HEAP = 2,
+  ARM_SORT_INSERTION = 3,
+  ARM_SORT_QUICK = 4,
+  ARM_SORT_SELECTION = 5
+} arm_sort_alg;
+typedef enum { ARM_SORT_DESCENDING = 0, ARM_SORT_ASCENDING = 1 } arm_sort_dir;
+typedef struct {
+  arm_sort_alg alg;
+  arm_sort_dir dir;
+} arm_sort_instance_f32;
+typedef struct {
+  arm_sort_dir dir;
+  float32_t *buffer;
+} arm_merge_sort_instance_f32;
+void arm_sort_init_f32(arm_sort_instance_f32 *S, arm_sort_alg alg, arm_sort_dir dir);
+void arm_sort_f32(const arm_sort_instance_f32 *S, float32_t *pSrc, float32_t *pDst, uint32_t blockSize);
+void arm_merge_sort_init_f32(arm_merge_sort_instance_f32 *S, arm_sort_dir dir, float32_t *buffer);
+void arm_merge_sort_f32(const arm_merge_sort_instance_f32 *S, float32_t *pSrc, float32_t *pDst, uint32_t blockSize);
+float32_t arm_weighted_average_f32(const float32_t *in, const float32_t *weights, uint32_t blockSize);
+void arm_barycenter_f32(const float32_t *in, const float32_t *weights, float32_t *out, uint32_t nbVectors,
+                        uint32_t vecDim);
+#define MI355X_DECL_SUPPORT_TO(SN, ST, DN, DT) void arm_##SN##_to_##DN(const ST *pSrc, DT *pDst, uint32_t blockSize);
+MI355X_DECL_SUPPORT_TO(float, float32_t, q31, q31_t)
+MI355X_DECL_SUPPORT_TO(float, float32_t, q15, q15_t)
+MI355X_DECL_SUPPORT_TO(float, float32_t, q7, q7_t)
+MI355X_DECL_SUPPORT_TO(q31, q31_t, float, float32_t)
+MI355X_DECL_SUPPORT_TO(q31, q31_t, q15, q15_t)
+MI355X_DECL_SUPPORT_TO(q31, q31_t, q7, q7_t)
+MI355X_DECL_SUPPORT_TO(q15, q15_t, float, float32_t)
+MI355X_DECL_SUPPORT_TO(q15, q15_t, q31, q31_t)
+MI355X_DECL_SUPPORT_TO(q15, q15_t, q7, q7_t)
+MI355X_DECL_SUPPORT_TO(q7, q7_t, float, float32_t)
+MI355X_DECL_SUPPORT_TO(q7, q7_t, q31, q31_t)
+MI355X_DECL_SUPPORT_TO(q7, q7_t, q15, q15_t)
+#undef MI355X_DECL_SUPPORT_TO
+#define MI355X_DECL_SUPPORT_COPY(SUF, T)                          \
+  void arm_copy_##SUF(const T *pSrc, T *pDst, uint32_t blockSize); \
+  void arm_fill_##SUF(T value, T *pDst, uint32_t blockSize);
+MI355X_DECL_SUPPORT_COPY(f32, float32_t)
+MI355X_DECL_SUPPORT_COPY(q31, q31_t)
+MI355X_DECL_SUPPORT_COPY(q15, q15_t)
+MI355X_DECL_SUPPORT_COPY(q7, q7_t)
+#undef MI355X_DECL_SUPPORT_COPY
+
 #ifdef __cplusplus
 }
 #endif

@@ -514,6 +514,54 @@ MI355X_DECL_BITWISE_BATCH(u8, uint8_t)
 arm_status arm_scale_f32_batch(const float32_t *d_src, float32_t scale, float32_t *d_dst, uint32_t blockSize,
                                uint32_t batch, void *stream);
 
+/* Batched support functions (arm_math.h: "The support functions").  Device pointers, stream-ordered.
+ * Conversions, copy, fill: item i is the blockSize contiguous words at d_src + i * blockSize and d_dst + i *
+ * blockSize, so the call runs over batch * blockSize words as one flat array (16-byte loads and stores on both
+ * streams when both pointers are 16-byte aligned, single elements otherwise).  d_dst may equal d_src exactly where
+ * both element widths are equal; any other overlap is refused.
+ * arm_sort_f32_batch / arm_merge_sort_f32_batch (the same kernels): every item of blockSize words is sorted on its
+ * own in the IEEE total order, dir ARM_SORT_ASCENDING or ARM_SORT_DESCENDING; d_dst may equal d_src exactly,
+ * otherwise d_src is only read.  blockSize <= 2^31.  Padded lengths up to 256 take one wave per item, up to 16384 one
+ * workgroup per item, longer items several launches in stream order.
+ * arm_weighted_average_f32_batch: d_result[i] = the weighted average of d_in + i * blockSize under the weights at
+ * d_weights + i * wStride (words); arm_barycenter_f32_batch: d_out + i * vecDim = the barycenter of the nbVectors
+ * vectors at d_in + i * nbVectors * vecDim under the weights at d_weights + i * wStride.  wStride 0 means one weight
+ * vector for every item, otherwise wStride >= the item's weight count (blockSize, nbVectors).
+ * ARM_MATH_ARGUMENT_ERROR on a null pointer, an unknown dir, a wStride below the weight count and a refused
+ * overlap; batch == 0 is a successful no-op. */
+#define MI355X_DECL_SUPPORT_TO_BATCH(SN, ST, DN, DT)                                                             \
+  arm_status arm_##SN##_to_##DN##_batch(const ST *d_src, DT *d_dst, uint32_t blockSize, uint32_t batch, void *stream);
+MI355X_DECL_SUPPORT_TO_BATCH(float, float32_t, q31, q31_t)
+MI355X_DECL_SUPPORT_TO_BATCH(float, float32_t, q15, q15_t)
+MI355X_DECL_SUPPORT_TO_BATCH(float, float32_t, q7, q7_t)
+MI355X_DECL_SUPPORT_TO_BATCH(q31, q31_t, float, float32_t)
+MI355X_DECL_SUPPORT_TO_BATCH(q31, q31_t, q15, q15_t)
+MI355X_DECL_SUPPORT_TO_BATCH(q31, q31_t, q7, q7_t)
+MI355X_DECL_SUPPORT_TO_BATCH(q15, q15_t, float, float32_t)
+MI355X_DECL_SUPPORT_TO_BATCH(q15, q15_t, q31, q31_t)
+MI355X_DECL_SUPPORT_TO_BATCH(q15, q15_t, q7, q7_t)
+MI355X_DECL_SUPPORT_TO_BATCH(q7, q7_t, float, float32_t)
+MI355X_DECL_SUPPORT_TO_BATCH(q7, q7_t, q31, q31_t)
+MI355X_DECL_SUPPORT_TO_BATCH(q7, q7_t, q15, q15_t)
+#undef MI355X_DECL_SUPPORT_TO_BATCH
+#define MI355X_DECL_SUPPORT_COPY_BATCH(SUF, T)                                                                   \
+  arm_status arm_copy_##SUF##_batch(const T *d_src, T *d_dst, uint32_t blockSize, uint32_t batch, void *stream); \
+  arm_status arm_fill_##SUF##_batch(T value, T *d_dst, uint32_t blockSize, uint32_t batch, void *stream);
+MI355X_DECL_SUPPORT_COPY_BATCH(f32, float32_t)
+MI355X_DECL_SUPPORT_COPY_BATCH(q31, q31_t)
+MI355X_DECL_SUPPORT_COPY_BATCH(q15, q15_t)
+MI355X_DECL_SUPPORT_COPY_BATCH(q7, q7_t)
+#undef MI355X_DECL_SUPPORT_COPY_BATCH
+arm_status arm_sort_f32_batch(const float32_t *d_src, float32_t *d_dst, uint32_t blockSize, arm_sort_dir dir,
+                              uint32_t batch, void *stream);
+arm_status arm_merge_sort_f32_batch(const float32_t *d_src, float32_t *d_dst, uint32_t blockSize, arm_sort_dir dir,
+                                    uint32_t batch, void *stream);
+arm_status arm_weighted_average_f32_batch(const float32_t *d_in, const float32_t *d_weights, uint32_t wStride,
+                                          uint32_t blockSize, float32_t *d_result, uint32_t batch, void *stream);
+arm_status arm_barycenter_f32_batch(const float32_t *d_in, const float32_t *d_weights, uint32_t wStride,
+                                    float32_t *d_out, uint32_t nbVectors, uint32_t vecDim, uint32_t batch,
+                                    void *stream);
+
 /* Multi-GPU complex FFT (SURVEY §8b "a multi-GPU entry point"; per item: arm_cfft_f32 /
  * _q31 / _q15, transform_functions.h:456-460).  Shard s of `nshards` is batch[s] contiguous
  * transforms at DEVICE pointer d_p1[s] on HIP device devices[s] (a device may appear in
