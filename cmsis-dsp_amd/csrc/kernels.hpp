@@ -5,6 +5,13 @@
 
 namespace mi355x {
 
+// The largest 1-D grid the launches use.  Batches go on grid x (grid y and z stop at 65,535); a call
+// whose workgroup count exceeds this is refused: grid_limit_error records which product it was, the
+// error channel's next message carries it ("... > 2147483647 workgroups"), and the entry point
+// returns ARM_MATH_ARGUMENT_ERROR.
+constexpr uint64_t kMaxGridX = 0x7fffffffull;
+hipError_t grid_limit_error(const char* product);   // runtime.cpp; returns hipErrorInvalidValue
+
 // Grid of a persistent kernel: every CU filled to the occupancy the compiled kernel allows
 // (hipOccupancyMaxActiveBlocksPerMultiprocessor x CU count), never more blocks than items.
 // The CU count is per device (cached for the first 16 ordinals).

@@ -35,12 +35,14 @@ __global__ __launch_bounds__(256) void mat_mult_f32_kernel(const float* __restri
 
   const int tilesN = (N + kBN - 1) / kBN, tilesM = (M + kBM - 1) / kBM;
   const int ntiles = tilesN * tilesM;
-  // XCD-aware bijective remap of the linear tile id (cdna_hip_programming.md §5 'XCD swizzle')
-  const int orig = blockIdx.x;
+  // 1-D grid of ntiles * batch workgroups (grid y / z stop at 65,535): the matrix is blockIdx.x /
+  // ntiles, kept in 64-bit address arithmetic.  Within the matrix, the XCD-aware bijective remap of
+  // the linear tile id (cdna_hip_programming.md §5 'XCD swizzle')
+  const int orig = (int)(blockIdx.x % (uint32_t)ntiles);
   const int q = ntiles / 8, r = ntiles % 8, xcd = orig % 8;
   const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
   const int tm = tile / tilesN, tn = tile % tilesN;
-  const size_t bz = blockIdx.z;
+  const size_t bz = blockIdx.x / (uint32_t)ntiles;
   A += bz * (size_t)M * K;
   B += bz * (size_t)(CX ? K / 2 : K) * N;
   C += bz * (size_t)M * N;
@@ -139,8 +141,8 @@ __global__ __launch_bounds__(256) void mat_mult_f32_kernel(const float* __restri
 // transposed into a k-major LDS tile whose row pitch of 130 words puts each 32-lane group of
 // the transposing ds_write_b32 on 32 distinct banks, B written with ds_write_b128.  Half the
 // registers of the general kernel, so four workgroups fit per CU (LDS- and VGPR-wise).
-// Tile order (MI355X_MATF32_XCD): 0 = the 8 column tiles of one row band on one XCD (grid z =
-// matrix); 1 = each XCD takes a contiguous run of (matrix, tile) pairs (1-D grid), so the 64 tiles
+// Tile order (MI355X_MATF32_XCD): 0 = the 8 column tiles of one row band on one XCD (matrix =
+// blockIdx.x / ntiles); 1 = each XCD takes a contiguous run of (matrix, tile) pairs (1-D grid), so the 64 tiles
 // of a 1024^2 matrix run together on one XCD and read its A / B panels through that XCD's L2.
 #ifndef MI355X_MATF32_XCD
 #define MI355X_MATF32_XCD 1
@@ -164,10 +166,10 @@ __global__ __launch_bounds__(256) void mat_mult_f32_full_kernel(const float* __r
   const int tile = (int)(lin % (uint32_t)ntiles);
   const size_t bz = lin / (uint32_t)ntiles;
 #else
-  const int orig = blockIdx.x;
+  const int orig = (int)(blockIdx.x % (uint32_t)ntiles);
   const int q = ntiles / 8, r = ntiles % 8, xcd = orig % 8;
   const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
-  const size_t bz = blockIdx.z;
+  const size_t bz = blockIdx.x / (uint32_t)ntiles;
 #endif
   const int tm = tile / tilesN, tn = tile % tilesN;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -262,12 +264,11 @@ static hipError_t launch_f32(int m, int k, int n, const float* a, const float* b
   const int tiles = ((m + kBM - 1) / kBM) * ((n + kBN - 1) / kBN);
   const bool full = m % kBM == 0 && n % kBN == 0 && k % kBK == 0 &&
                     ((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0;
-  if (full && (!MI355X_MATF32_XCD || (uint64_t)tiles * batch <= 0x7fffffffull)) {
-    const dim3 grid = MI355X_MATF32_XCD ? dim3((uint32_t)((uint64_t)tiles * batch)) : dim3(tiles, 1, batch);
-    hipLaunchKernelGGL(mat_mult_f32_full_kernel<CX>, grid, dim3(256), 0, st, a, b, c, m, k, n);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL(mat_mult_f32_kernel<CX>, dim3(tiles, 1, batch), dim3(256), 0, st, a, b, c, m, k, n);
+  // both kernels: one workgroup per (matrix, tile) on grid x
+  const uint64_t blocks = (uint64_t)tiles * batch;
+  if (blocks > kMaxGridX) return grid_limit_error("tiles x batch");
+  if (full) hipLaunchKernelGGL(mat_mult_f32_full_kernel<CX>, dim3((uint32_t)blocks), dim3(256), 0, st, a, b, c, m, k, n);
+  else hipLaunchKernelGGL(mat_mult_f32_kernel<CX>, dim3((uint32_t)blocks), dim3(256), 0, st, a, b, c, m, k, n);
   return hipGetLastError();
 }
 

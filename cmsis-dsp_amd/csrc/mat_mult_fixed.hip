@@ -724,8 +724,10 @@ template <typename T>
 __global__ __launch_bounds__(256) void mat_mult_fixed_valu_kernel(const T* __restrict__ A, const T* __restrict__ B,
                                                                   T* __restrict__ C, int M, int K, int N,
                                                                   int fast) {
-  const size_t bz = blockIdx.z;
-  const int i = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+  // grid x = batch * M * ceil(N / 256) (grid y / z stop at 65,535)
+  const uint32_t nb = (uint32_t)(N + 255) / 256, per = (uint32_t)M * nb, in = blockIdx.x % per;
+  const size_t bz = blockIdx.x / per;
+  const int i = (int)(in / nb), j = (int)(in % nb) * 256 + threadIdx.x;
   if (j >= N) return;
   const T* a = A + bz * (size_t)M * K + (size_t)i * K;
   const T* b = B + bz * (size_t)K * N + j;
@@ -743,8 +745,9 @@ template <typename T>
 __global__ __launch_bounds__(256) void mat_cmplx_mult_fixed_valu_kernel(const T* __restrict__ A,
                                                                         const T* __restrict__ B, T* __restrict__ C,
                                                                         int M, int K, int N) {
-  const size_t bz = blockIdx.z;
-  const int i = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+  const uint32_t nb = (uint32_t)(N + 255) / 256, per = (uint32_t)M * nb, in = blockIdx.x % per;
+  const size_t bz = blockIdx.x / per;
+  const int i = (int)(in / nb), j = (int)(in % nb) * 256 + threadIdx.x;
   if (j >= N) return;
   const T* a = A + bz * (size_t)M * K + (size_t)i * K;
   const T* b = B + bz * (size_t)(K / 2) * N + (j & ~1);
@@ -770,17 +773,20 @@ static hipError_t launch_fixed(int m, int k, int n, const T* a, const T* b, T* c
     const bool full = m % G::BM == 0 && n % G::BN == 0 && k % G::KT == 0 &&
                       ((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0 && (k * sizeof(T)) % 16 == 0 &&
                       (n * sizeof(T)) % 16 == 0 && ((uintptr_t)c & 15) == 0;
+    const uint64_t blocks = (uint64_t)tiles * batch;
+    if (blocks > kMaxGridX) return grid_limit_error("tiles x batch");
     auto go = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(tiles * batch), dim3(kNT2), 0, st, a, b, c, m, k, n, fast);
+      hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(kNT2), 0, st, a, b, c, m, k, n, fast);
     };
     if constexpr (sizeof(T) == 2) full ? go(mat_mult_i8v2_kernel<true, CX>) : go(mat_mult_i8v2_kernel<false, CX>);
     else full ? go(mat_mult_i8v3_kernel<true, CX>) : go(mat_mult_i8v3_kernel<false, CX>);
-  } else if (CX) {
-    hipLaunchKernelGGL(mat_cmplx_mult_fixed_valu_kernel<T>, dim3((n + 255) / 256, m, batch), dim3(256), 0, st, a, b,
-                       c, m, k, n);
   } else {
-    hipLaunchKernelGGL(mat_mult_fixed_valu_kernel<T>, dim3((n + 255) / 256, m, batch), dim3(256), 0, st, a, b, c,
-                       m, k, n, fast);
+    const uint64_t blocks = (uint64_t)((n + 255) / 256) * m * batch;
+    if (blocks > kMaxGridX) return grid_limit_error("row blocks x batch");
+    if (CX)
+      hipLaunchKernelGGL(mat_cmplx_mult_fixed_valu_kernel<T>, dim3((uint32_t)blocks), dim3(256), 0, st, a, b, c, m, k, n);
+    else
+      hipLaunchKernelGGL(mat_mult_fixed_valu_kernel<T>, dim3((uint32_t)blocks), dim3(256), 0, st, a, b, c, m, k, n, fast);
   }
   return hipGetLastError();
 }
@@ -800,8 +806,10 @@ __global__ __launch_bounds__(256) void mat_mult_fast_q31_kernel(const int32_t* _
   __shared__ __attribute__((aligned(16))) int32_t As[kFQ_K][kFQ_T + 4];
   __shared__ __attribute__((aligned(16))) int32_t Bs[kFQ_K][kFQ_T + 4];
   const int tid = threadIdx.x;
-  const size_t bz = blockIdx.y;
-  const int row0 = (blockIdx.x / tiles_n) * kFQ_T, col0 = (blockIdx.x % tiles_n) * kFQ_T;
+  // grid x = batch * tiles (grid y / z stop at 65,535)
+  const uint32_t tiles = (uint32_t)tiles_n * (uint32_t)((M + kFQ_T - 1) / kFQ_T), tile = blockIdx.x % tiles;
+  const size_t bz = blockIdx.x / tiles;
+  const int row0 = (int)(tile / tiles_n) * kFQ_T, col0 = (int)(tile % tiles_n) * kFQ_T;
   const int32_t* a = A + bz * (size_t)M * K;
   const int32_t* b = B + bz * (size_t)K * N;
   const int tr = (tid / 16) * 4, tc = (tid % 16) * 4;
@@ -844,8 +852,9 @@ hipError_t mat_mult_fast_q31_launch(int m, int k, int n, const int32_t* a, const
                                     uint32_t batch, hipStream_t st) {
   if (batch == 0 || m == 0 || n == 0) return hipSuccess;
   const int tn = (n + kFQ_T - 1) / kFQ_T, tm = (m + kFQ_T - 1) / kFQ_T;
-  if (batch > 65535) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(mat_mult_fast_q31_kernel, dim3(tm * tn, batch), dim3(256), 0, st, a, b, c, m, k, n, tn);
+  const uint64_t blocks = (uint64_t)tm * tn * batch;
+  if (blocks > kMaxGridX) return grid_limit_error("tiles x batch");
+  hipLaunchKernelGGL(mat_mult_fast_q31_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, a, b, c, m, k, n, tn);
   return hipGetLastError();
 }
 hipError_t mat_mult_fast_q15_launch(int m, int k, int n, const int16_t* a, const int16_t* b, int16_t* c,

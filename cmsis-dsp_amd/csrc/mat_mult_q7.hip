@@ -776,7 +776,7 @@ hipError_t mat_mult_q7_launch(int m, int k, int n, const int8_t* a, const int8_t
   if (batch == 0 || m == 0 || n == 0) return hipSuccess;
   if (k == 0) return hipMemsetAsync(c, 0, (size_t)m * n * batch, st);   // __SSAT(0 >> 7, 8) = 0
   const uint64_t tiles = (uint64_t)((m + kQ7BM - 1) / kQ7BM) * ((n + kQ7BN - 1) / kQ7BN);
-  if (tiles * batch > 0x7fffffffull) return hipErrorInvalidValue;
+  if (tiles * batch > kMaxGridX) return grid_limit_error("tiles x batch");
   if (m % 256 == 0 && n % 256 == 0 && k % 64 == 0 && ((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0 &&
       ((uintptr_t)c & 15) == 0) {
     // one persistent workgroup per CU (128 KiB of LDS each), a multiple of 8 so every XCD gets

@@ -33,6 +33,7 @@ namespace mi355x {
 namespace {
 thread_local int g_err = 0;
 thread_local std::string g_err_msg;
+thread_local std::string g_err_note;   // grid_limit_error: appended to the next message
 
 std::mutex g_table_mu;
 std::map<std::tuple<int, const void*, size_t>, void*> g_tables;
@@ -269,8 +270,14 @@ int fixed_src(int n, int k) {
 void set_error(hipError_t e, const char* where) {
   g_err = (int)e;
   g_err_msg = std::string(where) + ": " + hipGetErrorString(e);
+  if (!g_err_note.empty()) g_err_msg += " (" + g_err_note + ")";
+  g_err_note.clear();
 }
-void clear_error() { g_err = 0; g_err_msg.clear(); }
+hipError_t grid_limit_error(const char* product) {
+  g_err_note = std::string(product) + " > 2147483647 workgroups";
+  return hipErrorInvalidValue;
+}
+void clear_error() { g_err = 0; g_err_msg.clear(); g_err_note.clear(); }
 
 bool is_device_ptr(const void* p) {
   if (!p) return false;

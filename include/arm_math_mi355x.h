@@ -13,6 +13,12 @@
  *     DESIGN.md §mat_mult and "complex matrix multiply");
  *   - return ARM_MATH_SUCCESS, ARM_MATH_ARGUMENT_ERROR (unsupported length, NULL pointer,
  *     launch failure; details in arm_mi355x_last_error_string()).
+ * Batch counts: `batch` rides on grid x, which takes 2,147,483,647 workgroups; no entry point has
+ * a limit at 65,535 items.  batch == 0 returns ARM_MATH_SUCCESS and writes nothing.  A call whose
+ * workgroup count would exceed the limit (matrix multiplies: tiles x batch; beyond K = 32,704
+ * ceil(N / 256) x M x batch; convolutions: chunks x batch; the other families at most one per item)
+ * launches nothing and returns ARM_MATH_ARGUMENT_ERROR; arm_mi355x_last_error_string() then names the
+ * entry point and, for the matrix multiplies, the product ("tiles x batch > 2147483647 workgroups").
  * Instance structs are the reference's own (arm_math.h).  Tables and coefficients they point
  * to: a device pointer is used in place; the library's own CommonTables are uploaded once per
  * device and cached by address; any other host table is cached by CONTENT (hash + compare) in
