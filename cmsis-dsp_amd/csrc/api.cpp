@@ -10,6 +10,7 @@
 
 #include "../../include/arm_math.h"
 #include "../../include/arm_math_mi355x.h"
+#include "api_status.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
 #include "runtime.hpp"
@@ -27,13 +28,6 @@ bool cfft_len_ok(uint32_t n) {
     hipError_t e_ = (expr);                          \
     if (e_ != hipSuccess) { set_error(e_, where); return false; } \
   } while (0)
-
-// status of a batched entry point whose last step returned e; a failure is recorded under `what`
-arm_status batch_status(hipError_t e, const char* what) {
-  if (e == hipSuccess) return ARM_MATH_SUCCESS;
-  set_error(e, what);
-  return ARM_MATH_ARGUMENT_ERROR;
-}
 
 struct CfftPrep {
   const void* tw = nullptr;
@@ -1341,466 +1335,6 @@ arm_status mfcc_batch(const Inst* S, T* d_src, T* d_dst, T* d_tmp, uint32_t batc
 }
 }  // namespace
 
-// ---- inverse, Cholesky, LDLT, triangular solves (f32) ---------------------------------
-// matrix_functions.h:659-777; kernels and the reference bodies they restate: mat_solve.hip.  The shape rules
-// are those the reference states under ARM_MATH_MATRIX_CHECK, applied always (as mat_shapes_ok is), plus
-// a / dst agreement in the solves.
-namespace {
-using MatF = arm_matrix_instance_f32;
-
-// One operand of a synchronous drop-in call: host words are staged into device scratch (in) and copied
-// back after the launch (out); a device pointer is used in place.
-struct SolveBuf {
-  void* p;
-  size_t bytes;
-  bool in, out;
-  void* d = nullptr;
-  bool dev = false;
-};
-
-// launch(st) -> hipError_t runs on the staged operands (bufs[i].d) between the copies in and out.
-template <typename Launch>
-arm_status mat_staged_sync(SolveBuf* bufs, int nb, const char* what, Launch&& launch) {
-  hipStream_t st = sync_stream();
-  for (int i = 0; i < nb; ++i) {
-    SolveBuf& b = bufs[i];
-    b.dev = is_device_ptr(b.p);
-    b.d = b.dev ? b.p : scratch(b.bytes + 16, i);
-    for (int j = 0; j < i; ++j)          // exact alias (add / sub / scale in place): one staged copy
-      if (!b.dev && bufs[j].p == b.p && bufs[j].bytes == b.bytes) b.d = bufs[j].d;
-    if (!b.d) { set_error(hipErrorOutOfMemory, what); return ARM_MATH_ARGUMENT_ERROR; }
-  }
-  HostIO io(st);
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < nb && e == hipSuccess; ++i)
-    if (!bufs[i].dev && bufs[i].in) e = io.in(bufs[i].d, bufs[i].p, bufs[i].bytes);
-  if (e == hipSuccess) e = launch(st);
-  for (int i = 0; i < nb && e == hipSuccess; ++i)
-    if (!bufs[i].dev && bufs[i].out) e = io.out(bufs[i].p, bufs[i].d, bufs[i].bytes);
-  if (e == hipSuccess) e = io.finish();
-  return batch_status(e, what);
-}
-
-// launch(st, d_status) -> hipError_t runs one item on the staged operands; returns the item's status, which
-// is staged out like one more operand.
-template <typename Launch>
-arm_status mat_solve_sync(SolveBuf* bufs, int nb, const char* what, Launch&& launch) {
-  int32_t status = ARM_MATH_SUCCESS;
-  SolveBuf all[5];
-  for (int i = 0; i < nb; ++i) all[i] = bufs[i];
-  all[nb] = {&status, sizeof(status), false, true};
-  const arm_status r = mat_staged_sync(all, nb + 1, what, [&](hipStream_t st) {
-    for (int i = 0; i < nb; ++i) bufs[i] = all[i];      // the callers' launches read bufs[i].d
-    return launch(st, (int32_t*)all[nb].d);
-  });
-  return r != ARM_MATH_SUCCESS ? r : (arm_status)status;
-}
-
-bool square(const MatF* m) { return m->numRows == m->numCols; }
-
-arm_status solve_tri_sync(bool lower, const MatF* t, const MatF* a, MatF* dst, const char* what) {
-  if (!t || !a || !dst || !t->pData || !a->pData || !dst->pData) return ARM_MATH_ARGUMENT_ERROR;
-  if (!square(t) || t->numRows != a->numRows || a->numRows != dst->numRows || a->numCols != dst->numCols)
-    return ARM_MATH_SIZE_MISMATCH;
-  const int n = t->numRows, cols = a->numCols;
-  if (n == 0 || cols == 0) return ARM_MATH_SUCCESS;
-  // dst is staged in as well: a failing solve leaves most of its words alone
-  SolveBuf b[3] = {{t->pData, sizeof(float) * n * n, true, false},
-                   {a->pData, sizeof(float) * n * cols, true, false},
-                   {dst->pData, sizeof(float) * n * cols, true, true}};
-  return mat_solve_sync(b, 3, what, [&](hipStream_t st, int32_t* ds) {
-    return mat_solve_tri_f32_launch(lower, n, cols, (const float*)b[0].d, (const float*)b[1].d, (float*)b[2].d, 1, ds,
-                                    st);
-  });
-}
-
-arm_status solve_tri_batch(bool lower, const MatF* t, const MatF* a, MatF* dst, uint32_t batch, int32_t* d_status,
-                           void* stream, const char* what) {
-  if (!t || !a || !dst) return ARM_MATH_ARGUMENT_ERROR;
-  if (!square(t) || t->numRows != a->numRows || a->numRows != dst->numRows || a->numCols != dst->numCols)
-    return ARM_MATH_SIZE_MISMATCH;
-  if (batch == 0 || t->numRows == 0 || a->numCols == 0) return ARM_MATH_SUCCESS;
-  if (!t->pData || !a->pData || !dst->pData) return ARM_MATH_ARGUMENT_ERROR;
-  return batch_status(mat_solve_tri_f32_launch(lower, t->numRows, a->numCols, t->pData, a->pData, dst->pData, batch,
-                                               d_status, (hipStream_t)stream), what);
-}
-
-// ---- add / sub / scale, transposes, matrix x vector (mat_basic.hip) ------------------------------
-// matrix_functions.h groups MatrixAdd, MatrixSub, MatrixScale, MatrixTrans, MatrixComplexTrans and the
-// arm_mat_vec_mult_* of MatrixMult.  The shape rules are the reference's ARM_MATH_MATRIX_CHECK ones, applied
-// always.  sync: the drop-in (operands staged as SolveBuf describes); otherwise the batched form on device
-// pointers, which only enqueues.
-
-template <typename M>
-bool same_shape(const M* a, const M* b) { return a->numRows == b->numRows && a->numCols == b->numCols; }
-
-// op: kMatAdd / kMatSub (b != null) or kMatScale (b == null, scale and shift used).
-template <typename T, typename M>
-arm_status mat_ew(int op, const M* a, const M* b, M* d, T scale, int32_t shift, bool sync, uint32_t batch,
-                  void* stream, const char* what) {
-  const bool two = op != kMatScale;
-  if (!a || (two && !b) || !d) return ARM_MATH_ARGUMENT_ERROR;
-  if (sync && (!a->pData || (two && !b->pData) || !d->pData)) return ARM_MATH_ARGUMENT_ERROR;
-  if (!same_shape(a, d) || (two && !same_shape(a, b))) return ARM_MATH_SIZE_MISMATCH;
-  if (op == kMatScale && !std::is_same<T, float>::value) {
-    // past these the reference shifts by a negative or too large count
-    const int lo = sizeof(T) == 4 ? -1 : -16, hi = sizeof(T) == 4 ? 30 : 15;
-    if (shift < lo || shift > hi) return ARM_MATH_ARGUMENT_ERROR;
-  }
-  const size_t n = (size_t)a->numRows * a->numCols;
-  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
-  if (!sync) {
-    if (!a->pData || (two && !b->pData) || !d->pData) return ARM_MATH_ARGUMENT_ERROR;
-    return batch_status(mat_ew_launch<T>(op, (const T*)a->pData, two ? (const T*)b->pData : nullptr, (T*)d->pData,
-                                         n * batch, scale, shift, (hipStream_t)stream), what);
-  }
-  SolveBuf bufs[3] = {{a->pData, sizeof(T) * n, true, false},
-                      {d->pData, sizeof(T) * n, false, true},
-                      {two ? b->pData : nullptr, sizeof(T) * n, true, false}};
-  return mat_staged_sync(bufs, two ? 3 : 2, what, [&](hipStream_t st) {
-    return mat_ew_launch<T>(op, (const T*)bufs[0].d, (const T*)bufs[2].d, (T*)bufs[1].d, n, scale, shift, st);
-  });
-}
-
-// words: T words per element (2: interleaved complex).
-template <typename T, typename M>
-arm_status mat_trans(const M* s, M* d, int words, bool sync, uint32_t batch, void* stream, const char* what) {
-  if (!s || !d) return ARM_MATH_ARGUMENT_ERROR;
-  if (sync && (!s->pData || !d->pData)) return ARM_MATH_ARGUMENT_ERROR;
-  if (s->numRows != d->numCols || s->numCols != d->numRows) return ARM_MATH_SIZE_MISMATCH;
-  const size_t n = (size_t)s->numRows * s->numCols;
-  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
-  const int eb = (int)sizeof(T) * words;
-  if (!sync) {
-    if (!s->pData || !d->pData) return ARM_MATH_ARGUMENT_ERROR;
-    return batch_status(mat_trans_launch(eb, s->numRows, s->numCols, s->pData, d->pData, batch, (hipStream_t)stream),
-                        what);
-  }
-  SolveBuf bufs[2] = {{s->pData, eb * n, true, false}, {d->pData, eb * n, false, true}};
-  return mat_staged_sync(bufs, 2, what, [&](hipStream_t st) {
-    return mat_trans_launch(eb, s->numRows, s->numCols, bufs[0].d, bufs[1].d, 1, st);
-  });
-}
-
-template <typename T, typename M>
-arm_status mat_vec_mult_batch(const M* m, size_t matStride, const T* d_vec, T* d_dst, uint32_t batch, void* stream,
-                              const char* what) {
-  if (!m) return ARM_MATH_ARGUMENT_ERROR;
-  if (matStride != 0 && matStride < (size_t)m->numRows * m->numCols) return ARM_MATH_ARGUMENT_ERROR;
-  if (batch == 0 || m->numRows == 0) return ARM_MATH_SUCCESS;
-  if (!m->pData || !d_vec || !d_dst) return ARM_MATH_ARGUMENT_ERROR;
-  return batch_status(mat_vec_mult_launch<T>(m->numRows, m->numCols, (const T*)m->pData, matStride, d_vec, d_dst,
-                                             batch, (hipStream_t)stream), what);
-}
-
-template <typename T, typename M>
-void mat_vec_mult_sync(const M* m, const T* pVec, T* pDst, const char* what) {
-  if (!m || !m->pData || !pVec || !pDst) { set_error(hipErrorInvalidValue, what); return; }
-  const size_t rows = m->numRows, cols = m->numCols;
-  if (rows == 0) return;
-  // numCols == 0: every sum is empty and the outputs are zero, as in the reference; no operand word is read
-  SolveBuf bufs[3] = {{m->pData, sizeof(T) * rows * cols, cols != 0, false},
-                      {const_cast<T*>(pVec), sizeof(T) * cols, cols != 0, false},
-                      {pDst, sizeof(T) * rows, false, true}};
-  mat_staged_sync(bufs, 3, what, [&](hipStream_t st) {
-    return mat_vec_mult_launch<T>((int)rows, (int)cols, (const T*)bufs[0].d, 0, (const T*)bufs[1].d, (T*)bufs[2].d, 1,
-                                  st);
-  });
-}
-// ---- complex math, max / min (cmplx_math.hip) ---------------------------------------------------
-// complex_math_functions.h and arm_max_* / arm_min_* of statistics_functions.h.  sync: the void drop-in (operands
-// staged as SolveBuf describes, a failure only sets the last error); otherwise the batched form on device
-// pointers, which only enqueues.  On device memory dst may be a source exactly where the kernel allows it
-// (conj: the source; mult_cmplx: either source; mult_real: the complex source); any other overlap of an output
-// with a source is refused.
-
-bool cm_overlaps(const void* d, size_t db, const void* s, size_t sb, bool exactOk) {
-  if (!db || !sb || !s) return false;
-  if (d == s && db == sb && exactOk) return false;
-  const uintptr_t d0 = (uintptr_t)d, s0 = (uintptr_t)s;
-  return d0 < s0 + sb && s0 < d0 + db;
-}
-
-arm_status cm_null(bool sync, const char* what) {
-  if (sync) set_error(hipErrorInvalidValue, what);
-  return ARM_MATH_ARGUMENT_ERROR;
-}
-
-template <typename T>
-arm_status cmplx_ew(int op, const T* a, const T* b, T* d, uint32_t n, bool sync, uint32_t batch, void* stream,
-                    const char* what) {
-  const int wb = op == kCmMultCmplx ? 2 : op == kCmMultReal ? 1 : 0;
-  const int wd = op == kCmMag || op == kCmMagSquared || op == kCmMagFast ? 1 : 2;
-  if (sync && (!a || (wb && !b) || !d)) return cm_null(true, what);
-  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
-  if (!a || (wb && !b) || !d) return ARM_MATH_ARGUMENT_ERROR;
-  const size_t count = (size_t)n * batch;
-  const bool lut = op == kCmMag && !std::is_same<T, float>::value;
-  auto run = [&](const T* da, const T* db, T* dd, hipStream_t st) -> hipError_t {
-    if (cm_overlaps(dd, sizeof(T) * wd * count, da, sizeof(T) * 2 * count, wd == 2) ||
-        cm_overlaps(dd, sizeof(T) * wd * count, db, sizeof(T) * wb * count, op == kCmMultCmplx))
-      return hipErrorInvalidValue;
-    const int32_t* dl = lut ? (const int32_t*)device_table(sqrt_initial_lut_q31, sizeof(int32_t) * 32) : nullptr;
-    if (lut && !dl) return hipErrorOutOfMemory;
-    return cmplx_ew_launch<T>(op, da, db, dd, count, dl, st);
-  };
-  if (!sync) return batch_status(run(a, b, d, (hipStream_t)stream), what);
-  SolveBuf bufs[3] = {{const_cast<T*>(a), sizeof(T) * 2 * count, true, false},
-                      {d, sizeof(T) * wd * count, false, true},
-                      {const_cast<T*>(b), sizeof(T) * wb * count, true, false}};
-  return mat_staged_sync(bufs, wb ? 3 : 2, what, [&](hipStream_t st) {
-    return run((const T*)bufs[0].d, wb ? (const T*)bufs[2].d : nullptr, (T*)bufs[1].d, st);
-  });
-}
-
-// bStride (complex samples; the drop-in passes n): 0 shares one b, otherwise >= n.
-template <typename T, typename R>
-arm_status cmplx_dot(const T* a, const T* b, uint32_t bStride, uint32_t n, R* re, R* im, bool sync, uint32_t batch,
-                     void* stream, const char* what) {
-  if (sync && (!a || !b || !re || !im)) return cm_null(true, what);
-  if (bStride != 0 && bStride < n) return ARM_MATH_ARGUMENT_ERROR;
-  if (batch == 0) return ARM_MATH_SUCCESS;
-  if (!a || !b || !re || !im) return ARM_MATH_ARGUMENT_ERROR;
-  const size_t ab = sizeof(T) * 2 * n * batch, ob = sizeof(R) * batch;
-  const size_t bb = sizeof(T) * 2 * ((size_t)bStride * (batch - 1) + n);
-  auto run = [&](const T* da, const T* db, R* dre, R* dim, hipStream_t st) -> hipError_t {
-    if (cm_overlaps(dre, ob, da, ab, false) || cm_overlaps(dre, ob, db, bb, false) ||
-        cm_overlaps(dim, ob, da, ab, false) || cm_overlaps(dim, ob, db, bb, false) || cm_overlaps(dre, ob, dim, ob, false))
-      return hipErrorInvalidValue;
-    return cmplx_dot_launch<T, R>(da, db, bStride, n, dre, dim, batch, st);
-  };
-  if (!sync) return batch_status(run(a, b, re, im, (hipStream_t)stream), what);
-  SolveBuf bufs[4] = {{const_cast<T*>(a), ab, n != 0, false}, {const_cast<T*>(b), bb, n != 0, false},
-                      {re, ob, false, true}, {im, ob, false, true}};
-  return mat_staged_sync(bufs, 4, what, [&](hipStream_t st) {
-    return run((const T*)bufs[0].d, (const T*)bufs[1].d, (R*)bufs[2].d, (R*)bufs[3].d, st);
-  });
-}
-
-template <typename T>
-arm_status cm_search(bool max, const T* src, uint32_t n, T* result, uint32_t* index, bool sync, uint32_t batch,
-                     void* stream, const char* what) {
-  if (sync && (!src || !result || !index)) return cm_null(true, what);
-  if (batch == 0) return ARM_MATH_SUCCESS;
-  if (n == 0) return cm_null(sync, what);                  // the reference reads pSrc[0]
-  if (!src || !result || !index) return ARM_MATH_ARGUMENT_ERROR;
-  const size_t sb = sizeof(T) * n * batch, rb = sizeof(T) * batch, ib = sizeof(uint32_t) * batch;
-  auto run = [&](const T* ds, T* dr, uint32_t* di, hipStream_t st) -> hipError_t {
-    if (cm_overlaps(dr, rb, ds, sb, false) || cm_overlaps(di, ib, ds, sb, false) || cm_overlaps(dr, rb, di, ib, false))
-      return hipErrorInvalidValue;
-    return search_launch<T>(max, ds, n, dr, di, batch, st);
-  };
-  if (!sync) return batch_status(run(src, result, index, (hipStream_t)stream), what);
-  SolveBuf bufs[3] = {{const_cast<T*>(src), sb, true, false}, {result, rb, false, true}, {index, ib, false, true}};
-  return mat_staged_sync(bufs, 3, what, [&](hipStream_t st) {
-    return run((const T*)bufs[0].d, (T*)bufs[1].d, (uint32_t*)bufs[2].d, st);
-  });
-}
-
-// ---- statistics (statistics.hip) ------------------------------------------------------------------
-// The sums and level measures of statistics_functions.h (op: kStMean ... kStAccumulate; b: the second source of
-// kStMse) and the abs / no-index searches.  sync and the overlap rule as above.  blockSize == 0: what the
-// reference's empty sums give is stored (power, accumulate: 0; mean_f32, mse_f32: 0 / 0; rms_f32: +0.0; var, std:
-// 0; max / min_no_idx_f32: their start value); where it would divide an integer by zero or read pSrc[0] the call
-// is refused as cm_search refuses it.
-template <typename T, typename R>
-arm_status st_sum(int op, const T* a, const T* b, uint32_t n, R* result, bool sync, uint32_t batch, void* stream,
-                  const char* what) {
-  constexpr bool f32 = std::is_same<T, float>::value;
-  const bool two = op == kStMse;
-  if (sync && (!a || (two && !b) || !result)) return cm_null(true, what);
-  if (batch == 0) return ARM_MATH_SUCCESS;
-  if (n == 0 && !f32 && (op == kStMean || op == kStRms || op == kStMse)) return cm_null(sync, what);
-  if (!a || (two && !b) || !result) return ARM_MATH_ARGUMENT_ERROR;
-  const size_t sb = sizeof(T) * n * batch, rb = sizeof(R) * batch;
-  const bool lut = std::is_same<T, int32_t>::value && (op == kStRms || op == kStStd);
-  auto run = [&](const T* da, const T* db, R* dr, hipStream_t st) -> hipError_t {
-    if (cm_overlaps(dr, rb, da, sb, false) || (two && cm_overlaps(dr, rb, db, sb, false))) return hipErrorInvalidValue;
-    const int32_t* dl = lut ? (const int32_t*)device_table(sqrt_initial_lut_q31, sizeof(int32_t) * 32) : nullptr;
-    if (lut && !dl) return hipErrorOutOfMemory;
-    return stat_sum_launch<T, R>(op, da, db, n, dr, batch, dl, st);
-  };
-  if (!sync) return batch_status(run(a, b, result, (hipStream_t)stream), what);
-  SolveBuf bufs[3] = {{const_cast<T*>(a), sb, n != 0, false}, {result, rb, false, true},
-                      {const_cast<T*>(b), sb, n != 0, false}};
-  return mat_staged_sync(bufs, two ? 3 : 2, what, [&](hipStream_t st) {
-    return run((const T*)bufs[0].d, two ? (const T*)bufs[2].d : nullptr, (R*)bufs[1].d, st);
-  });
-}
-
-// idx false: the _no_idx forms (index unused).
-template <typename T>
-arm_status st_search(bool max, bool abs, bool idx, const T* src, uint32_t n, T* result, uint32_t* index, bool sync,
-                     uint32_t batch, void* stream, const char* what) {
-  if (sync && (!src || !result || (idx && !index))) return cm_null(true, what);
-  if (batch == 0) return ARM_MATH_SUCCESS;
-  const bool fromStart = std::is_same<T, float>::value && !abs && !idx;   // max / min_no_idx_f32 read no pSrc[0]
-  if (n == 0 && !fromStart) return cm_null(sync, what);
-  if (!src || !result || (idx && !index)) return ARM_MATH_ARGUMENT_ERROR;
-  const size_t sb = sizeof(T) * n * batch, rb = sizeof(T) * batch, ib = idx ? sizeof(uint32_t) * batch : 0;
-  auto run = [&](const T* ds, T* dr, uint32_t* di, hipStream_t st) -> hipError_t {
-    if (cm_overlaps(dr, rb, ds, sb, false) || cm_overlaps(di, ib, ds, sb, false) || cm_overlaps(dr, rb, di, ib, false))
-      return hipErrorInvalidValue;
-    return stat_search_launch<T>(max, abs, ds, n, dr, di, batch, st);
-  };
-  if (!sync) return batch_status(run(src, result, idx ? index : nullptr, (hipStream_t)stream), what);
-  SolveBuf bufs[3] = {{const_cast<T*>(src), sb, n != 0, false}, {result, rb, false, true}, {index, ib, false, true}};
-  return mat_staged_sync(bufs, idx ? 3 : 2, what, [&](hipStream_t st) {
-    return run((const T*)bufs[0].d, (T*)bufs[1].d, idx ? (uint32_t*)bufs[2].d : nullptr, st);
-  });
-}
-
-// ---- basic math (basic_math.hip; the dot products: statistics.hip) ---------------------------------
-// basic_math_functions.h.  sync and the null / overlap rules as the complex-math functions: dst may be a source
-// exactly, any other overlap of an output with a source is refused.  One scalar (offset, scale and shift, low and
-// high) serves the whole call.  shift: the counts at which the reference's C is defined (a count below 32 either way
-// on its promoted int operands): arm_shift_* -31 .. 31; arm_scale_q31 -32 .. 30 (kShift = shift + 1), _q15 -16 .. 15
-// (kShift = 15 - shift in 0 .. 31), _q7 -24 .. 7 (kShift = 7 - shift); outside the call is refused.
-bool bm_two(int op) { return op == kBmAdd || op == kBmSub || op == kBmMult || op == kBmAnd || op == kBmOr || op == kBmXor; }
-
-template <typename T>
-arm_status bm_ew(int op, const T* a, const T* b, T* d, uint32_t n, T s0, T s1, int shift, bool sync, uint32_t batch,
-                 void* stream, const char* what) {
-  const bool two = bm_two(op);
-  if (sync && (!a || (two && !b) || !d)) return cm_null(true, what);
-  int sh = 0;
-  if (op == kBmShift) {
-    if (shift < -31 || shift > 31) return cm_null(sync, what);
-    sh = shift;
-  } else if (op == kBmScale && !std::is_same<T, float>::value) {
-    const int lo = sizeof(T) == 4 ? -32 : sizeof(T) == 2 ? -16 : -24, hi = sizeof(T) == 4 ? 30 : sizeof(T) == 2 ? 15 : 7;
-    if (shift < lo || shift > hi) return cm_null(sync, what);
-    sh = sizeof(T) == 4 ? shift + 1 : hi - shift;
-  }
-  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
-  if (!a || (two && !b) || !d) return ARM_MATH_ARGUMENT_ERROR;
-  const size_t count = (size_t)n * batch, bytes = sizeof(T) * count;
-  auto run = [&](const T* da, const T* db, T* dd, hipStream_t st) -> hipError_t {
-    if (cm_overlaps(dd, bytes, da, bytes, true) || (two && cm_overlaps(dd, bytes, db, bytes, true)))
-      return hipErrorInvalidValue;
-    return basic_ew_launch<T>(op, da, db, dd, count, s0, s1, sh, st);
-  };
-  if (!sync) return batch_status(run(a, b, d, (hipStream_t)stream), what);
-  SolveBuf bufs[3] = {{const_cast<T*>(a), bytes, true, false}, {d, bytes, false, true},
-                      {const_cast<T*>(b), bytes, true, false}};
-  return mat_staged_sync(bufs, two ? 3 : 2, what, [&](hipStream_t st) {
-    return run((const T*)bufs[0].d, two ? (const T*)bufs[2].d : nullptr, (T*)bufs[1].d, st);
-  });
-}
-
-// bStride (words; the drop-in passes n): 0 shares one b, otherwise >= n.  n == 0 stores zeros.
-template <typename T, typename R>
-arm_status bm_dot(const T* a, const T* b, uint32_t bStride, uint32_t n, R* result, bool sync, uint32_t batch,
-                  void* stream, const char* what) {
-  if (sync && (!a || !b || !result)) return cm_null(true, what);
-  if (bStride != 0 && bStride < n) return ARM_MATH_ARGUMENT_ERROR;
-  if (batch == 0) return ARM_MATH_SUCCESS;
-  if (!a || !b || !result) return ARM_MATH_ARGUMENT_ERROR;
-  const size_t ab = sizeof(T) * n * batch, rb = sizeof(R) * batch;
-  const size_t bb = sizeof(T) * ((size_t)bStride * (batch - 1) + n);
-  auto run = [&](const T* da, const T* db, R* dr, hipStream_t st) -> hipError_t {
-    if (cm_overlaps(dr, rb, da, ab, false) || cm_overlaps(dr, rb, db, bb, false)) return hipErrorInvalidValue;
-    return dot_prod_launch<T, R>(da, db, bStride, n, dr, batch, st);
-  };
-  if (!sync) return batch_status(run(a, b, result, (hipStream_t)stream), what);
-  SolveBuf bufs[3] = {{const_cast<T*>(a), ab, n != 0, false}, {const_cast<T*>(b), bb, n != 0, false},
-                      {result, rb, false, true}};
-  return mat_staged_sync(bufs, 3, what, [&](hipStream_t st) {
-    return run((const T*)bufs[0].d, (const T*)bufs[1].d, (R*)bufs[2].d, st);
-  });
-}
-
-// ---- support functions (support.hip, sort.hip; the weighted average: statistics.hip) --------------
-// support_functions.h.  sync and the null / overlap rules as the basic math functions; dst may be src exactly where
-// both element widths are equal (float_to_q31, q31_to_float, copy) and in the sorts.
-template <typename S, typename D>
-arm_status sp_convert(const S* s, D* d, uint32_t n, bool sync, uint32_t batch, void* stream, const char* what) {
-  if (sync && (!s || !d)) return cm_null(true, what);
-  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
-  if (!s || !d) return ARM_MATH_ARGUMENT_ERROR;
-  const size_t count = (size_t)n * batch, sb = sizeof(S) * count, db = sizeof(D) * count;
-  auto run = [&](const S* ds, D* dd, hipStream_t st) -> hipError_t {
-    if (cm_overlaps(dd, db, ds, sb, sizeof(S) == sizeof(D))) return hipErrorInvalidValue;
-    return support_convert_launch<S, D>(ds, dd, count, st);
-  };
-  if (!sync) return batch_status(run(s, d, (hipStream_t)stream), what);
-  SolveBuf bufs[2] = {{const_cast<S*>(s), sb, true, false}, {d, db, false, true}};
-  return mat_staged_sync(bufs, 2, what, [&](hipStream_t st) { return run((const S*)bufs[0].d, (D*)bufs[1].d, st); });
-}
-
-template <typename T>
-arm_status sp_fill(T value, T* d, uint32_t n, bool sync, uint32_t batch, void* stream, const char* what) {
-  if (sync && !d) return cm_null(true, what);
-  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
-  if (!d) return ARM_MATH_ARGUMENT_ERROR;
-  const size_t count = (size_t)n * batch;
-  if (!sync) return batch_status(support_fill_launch<T>(value, d, count, (hipStream_t)stream), what);
-  SolveBuf bufs[1] = {{d, sizeof(T) * count, false, true}};
-  return mat_staged_sync(bufs, 1, what,
-                         [&](hipStream_t st) { return support_fill_launch<T>(value, (T*)bufs[0].d, count, st); });
-}
-
-// dir: ARM_SORT_DESCENDING (0) or ARM_SORT_ASCENDING (1), anything else is refused.
-arm_status sp_sort(int dir, const float* src, float* dst, uint32_t n, bool sync, uint32_t batch, void* stream,
-                   const char* what) {
-  if (sync && (!src || !dst)) return cm_null(true, what);
-  if ((dir != 0 && dir != 1) || n > 0x80000000u) return cm_null(sync, what);
-  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
-  if (!src || !dst) return ARM_MATH_ARGUMENT_ERROR;
-  const size_t bytes = sizeof(float) * n * batch;
-  auto run = [&](const float* ds, float* dd, hipStream_t st) -> hipError_t {
-    if (cm_overlaps(dd, bytes, ds, bytes, true)) return hipErrorInvalidValue;
-    return sort_launch((const uint32_t*)ds, (uint32_t*)dd, n, dir == 1, batch, st);
-  };
-  if (!sync) return batch_status(run(src, dst, (hipStream_t)stream), what);
-  SolveBuf bufs[2] = {{const_cast<float*>(src), bytes, true, false}, {dst, bytes, false, true}};
-  return mat_staged_sync(bufs, 2, what,
-                         [&](hipStream_t st) { return run((const float*)bufs[0].d, (float*)bufs[1].d, st); });
-}
-
-// wStride (words; the drop-in passes n): 0 shares one weight vector, otherwise >= n.  n == 0 stores 0 / 0.
-arm_status sp_wavg(const float* a, const float* w, uint32_t wStride, uint32_t n, float* result, bool sync,
-                   uint32_t batch, void* stream, const char* what) {
-  if (sync && (!a || !w || !result)) return cm_null(true, what);
-  if (wStride != 0 && wStride < n) return cm_null(sync, what);
-  if (batch == 0) return ARM_MATH_SUCCESS;
-  if (!a || !w || !result) return ARM_MATH_ARGUMENT_ERROR;
-  const size_t ab = sizeof(float) * n * batch, rb = sizeof(float) * batch;
-  const size_t wb = sizeof(float) * ((size_t)wStride * (batch - 1) + n);
-  auto run = [&](const float* da, const float* dw, float* dr, hipStream_t st) -> hipError_t {
-    if (cm_overlaps(dr, rb, da, ab, false) || cm_overlaps(dr, rb, dw, wb, false)) return hipErrorInvalidValue;
-    return weighted_average_launch(da, dw, wStride, n, dr, batch, st);
-  };
-  if (!sync) return batch_status(run(a, w, result, (hipStream_t)stream), what);
-  SolveBuf bufs[3] = {{const_cast<float*>(a), ab, n != 0, false}, {const_cast<float*>(w), wb, n != 0, false},
-                      {result, rb, false, true}};
-  return mat_staged_sync(bufs, 3, what, [&](hipStream_t st) {
-    return run((const float*)bufs[0].d, (const float*)bufs[1].d, (float*)bufs[2].d, st);
-  });
-}
-
-// wStride as sp_wavg against nbVectors.  vecDim == 0 writes nothing; nbVectors == 0 stores 0 / 0.
-arm_status sp_barycenter(const float* in, const float* w, uint32_t wStride, float* out, uint32_t nv, uint32_t dim,
-                         bool sync, uint32_t batch, void* stream, const char* what) {
-  if (sync && (!in || !w || !out)) return cm_null(true, what);
-  if (wStride != 0 && wStride < nv) return cm_null(sync, what);
-  if (batch == 0 || dim == 0) return ARM_MATH_SUCCESS;
-  if (!in || !w || !out) return ARM_MATH_ARGUMENT_ERROR;
-  const size_t ib = sizeof(float) * nv * dim * batch, ob = sizeof(float) * dim * batch;
-  const size_t wb = sizeof(float) * ((size_t)wStride * (batch - 1) + nv);
-  auto run = [&](const float* di, const float* dw, float* dout, hipStream_t st) -> hipError_t {
-    if (cm_overlaps(dout, ob, di, ib, false) || cm_overlaps(dout, ob, dw, wb, false)) return hipErrorInvalidValue;
-    return barycenter_launch(di, dw, wStride, dout, nv, dim, batch, st);
-  };
-  if (!sync) return batch_status(run(in, w, out, (hipStream_t)stream), what);
-  SolveBuf bufs[3] = {{const_cast<float*>(in), ib, nv != 0, false}, {const_cast<float*>(w), wb, nv != 0, false},
-                      {out, ob, false, true}};
-  return mat_staged_sync(bufs, 3, what, [&](hipStream_t st) {
-    return run((const float*)bufs[0].d, (const float*)bufs[1].d, (float*)bufs[2].d, st);
-  });
-}
-}  // namespace
-
 extern "C" {
 
 #ifndef MI355X_BUILD_DEFS
@@ -2133,532 +1667,6 @@ MI355X_CMAT(f32, arm_matrix_instance_f32, float32_t, float)
 MI355X_CMAT(q31, arm_matrix_instance_q31, q31_t, int32_t)
 MI355X_CMAT(q15, arm_matrix_instance_q15, q15_t, int16_t)
 #undef MI355X_CMAT
-
-// ---- inverse, Cholesky, LDLT, triangular solves (f32); mat_solve_sync and its kin precede the C block ----
-arm_status arm_mat_inverse_f32(const arm_matrix_instance_f32* pSrc, arm_matrix_instance_f32* pDst) {
-  if (!pSrc || !pDst || !pSrc->pData || !pDst->pData) return ARM_MATH_ARGUMENT_ERROR;
-  if (!square(pSrc) || !square(pDst) || pSrc->numRows != pDst->numRows) return ARM_MATH_SIZE_MISMATCH;
-  const int n = pSrc->numRows;
-  if (n == 0) return ARM_MATH_SUCCESS;
-  // src is written back: the reference destroys it, and its final words are part of the contract
-  SolveBuf b[2] = {{pSrc->pData, sizeof(float) * n * n, true, true}, {pDst->pData, sizeof(float) * n * n, false, true}};
-  return mat_solve_sync(b, 2, "arm_mat_inverse_f32", [&](hipStream_t st, int32_t* ds) {
-    return mat_inverse_f32_launch(n, (float*)b[0].d, (float*)b[1].d, 1, ds, st);
-  });
-}
-
-arm_status arm_mat_cholesky_f32(const arm_matrix_instance_f32* pSrc, arm_matrix_instance_f32* pDst) {
-  if (!pSrc || !pDst || !pSrc->pData || !pDst->pData) return ARM_MATH_ARGUMENT_ERROR;
-  if (!square(pSrc) || !square(pDst) || pSrc->numRows != pDst->numRows) return ARM_MATH_SIZE_MISMATCH;
-  const int n = pSrc->numRows;
-  if (n == 0) return ARM_MATH_SUCCESS;
-  // dst is staged in as well: its strict upper triangle, and the columns past a failure, are never written
-  SolveBuf b[2] = {{pSrc->pData, sizeof(float) * n * n, true, false}, {pDst->pData, sizeof(float) * n * n, true, true}};
-  return mat_solve_sync(b, 2, "arm_mat_cholesky_f32", [&](hipStream_t st, int32_t* ds) {
-    return mat_cholesky_f32_launch(n, (const float*)b[0].d, (float*)b[1].d, 1, ds, st);
-  });
-}
-
-arm_status arm_mat_ldlt_f32(const arm_matrix_instance_f32* pSrc, arm_matrix_instance_f32* pl,
-                            arm_matrix_instance_f32* pd, uint16_t* pp) {
-  if (!pSrc || !pl || !pd || !pp || !pSrc->pData || !pl->pData || !pd->pData) return ARM_MATH_ARGUMENT_ERROR;
-  if (!square(pSrc) || !square(pl) || !square(pd) || pl->numRows != pd->numRows || pSrc->numRows != pl->numRows)
-    return ARM_MATH_SIZE_MISMATCH;
-  const int n = pSrc->numRows;
-  if (n == 0) return ARM_MATH_SUCCESS;
-  SolveBuf b[4] = {{pSrc->pData, sizeof(float) * n * n, true, false},
-                   {pl->pData, sizeof(float) * n * n, false, true},
-                   {pd->pData, sizeof(float) * n * n, false, true},
-                   {pp, sizeof(uint16_t) * n, false, true}};
-  return mat_solve_sync(b, 4, "arm_mat_ldlt_f32", [&](hipStream_t st, int32_t* ds) {
-    hipError_t e = hipMemsetAsync(ds, 0, sizeof(int32_t), st);       // the function cannot fail
-    if (e == hipSuccess)
-      e = mat_ldlt_f32_launch(n, (const float*)b[0].d, (float*)b[1].d, (float*)b[2].d, (uint16_t*)b[3].d, 1, st);
-    return e;
-  });
-}
-
-arm_status arm_mat_solve_lower_triangular_f32(const arm_matrix_instance_f32* lt, const arm_matrix_instance_f32* a,
-                                              arm_matrix_instance_f32* dst) {
-  return solve_tri_sync(true, lt, a, dst, "arm_mat_solve_lower_triangular_f32");
-}
-arm_status arm_mat_solve_upper_triangular_f32(const arm_matrix_instance_f32* ut, const arm_matrix_instance_f32* a,
-                                              arm_matrix_instance_f32* dst) {
-  return solve_tri_sync(false, ut, a, dst, "arm_mat_solve_upper_triangular_f32");
-}
-
-arm_status arm_mat_inverse_f32_batch(const arm_matrix_instance_f32* pSrc, arm_matrix_instance_f32* pDst,
-                                     uint32_t batch, int32_t* d_status, void* stream) {
-  if (!pSrc || !pDst) return ARM_MATH_ARGUMENT_ERROR;
-  if (!square(pSrc) || !square(pDst) || pSrc->numRows != pDst->numRows) return ARM_MATH_SIZE_MISMATCH;
-  if (batch == 0 || pSrc->numRows == 0) return ARM_MATH_SUCCESS;
-  if (!pSrc->pData || !pDst->pData) return ARM_MATH_ARGUMENT_ERROR;
-  return batch_status(mat_inverse_f32_launch(pSrc->numRows, pSrc->pData, pDst->pData, batch, d_status,
-                                             (hipStream_t)stream), "arm_mat_inverse_f32_batch");
-}
-
-arm_status arm_mat_cholesky_f32_batch(const arm_matrix_instance_f32* pSrc, arm_matrix_instance_f32* pDst,
-                                      uint32_t batch, int32_t* d_status, void* stream) {
-  if (!pSrc || !pDst) return ARM_MATH_ARGUMENT_ERROR;
-  if (!square(pSrc) || !square(pDst) || pSrc->numRows != pDst->numRows) return ARM_MATH_SIZE_MISMATCH;
-  if (batch == 0 || pSrc->numRows == 0) return ARM_MATH_SUCCESS;
-  if (!pSrc->pData || !pDst->pData) return ARM_MATH_ARGUMENT_ERROR;
-  return batch_status(mat_cholesky_f32_launch(pSrc->numRows, pSrc->pData, pDst->pData, batch, d_status,
-                                              (hipStream_t)stream), "arm_mat_cholesky_f32_batch");
-}
-
-arm_status arm_mat_ldlt_f32_batch(const arm_matrix_instance_f32* pSrc, arm_matrix_instance_f32* pl,
-                                  arm_matrix_instance_f32* pd, uint16_t* d_pp, uint32_t batch, void* stream) {
-  if (!pSrc || !pl || !pd) return ARM_MATH_ARGUMENT_ERROR;
-  if (!square(pSrc) || !square(pl) || !square(pd) || pl->numRows != pd->numRows || pSrc->numRows != pl->numRows)
-    return ARM_MATH_SIZE_MISMATCH;
-  if (batch == 0 || pSrc->numRows == 0) return ARM_MATH_SUCCESS;
-  if (!pSrc->pData || !pl->pData || !pd->pData || !d_pp) return ARM_MATH_ARGUMENT_ERROR;
-  return batch_status(mat_ldlt_f32_launch(pSrc->numRows, pSrc->pData, pl->pData, pd->pData, d_pp, batch,
-                                          (hipStream_t)stream), "arm_mat_ldlt_f32_batch");
-}
-
-arm_status arm_mat_solve_lower_triangular_f32_batch(const arm_matrix_instance_f32* lt,
-                                                    const arm_matrix_instance_f32* a, arm_matrix_instance_f32* dst,
-                                                    uint32_t batch, int32_t* d_status, void* stream) {
-  return solve_tri_batch(true, lt, a, dst, batch, d_status, stream, "arm_mat_solve_lower_triangular_f32_batch");
-}
-arm_status arm_mat_solve_upper_triangular_f32_batch(const arm_matrix_instance_f32* ut,
-                                                    const arm_matrix_instance_f32* a, arm_matrix_instance_f32* dst,
-                                                    uint32_t batch, int32_t* d_status, void* stream) {
-  return solve_tri_batch(false, ut, a, dst, batch, d_status, stream, "arm_mat_solve_upper_triangular_f32_batch");
-}
-
-// ---- add / sub / scale, transposes, matrix x vector; mat_ew and its kin precede the C block ----
-#define MI355X_MAT_EW(SUF, INST, T, CT)                                                                          \
-  arm_status arm_mat_add_##SUF(const INST* pSrcA, const INST* pSrcB, INST* pDst) {                               \
-    return mat_ew<CT>(kMatAdd, pSrcA, pSrcB, pDst, (CT)0, 0, true, 1, nullptr, "arm_mat_add_" #SUF);             \
-  }                                                                                                              \
-  arm_status arm_mat_sub_##SUF(const INST* pSrcA, const INST* pSrcB, INST* pDst) {                               \
-    return mat_ew<CT>(kMatSub, pSrcA, pSrcB, pDst, (CT)0, 0, true, 1, nullptr, "arm_mat_sub_" #SUF);             \
-  }                                                                                                              \
-  arm_status arm_mat_add_##SUF##_batch(const INST* pSrcA, const INST* pSrcB, INST* pDst, uint32_t batch,         \
-                                       void* stream) {                                                           \
-    return mat_ew<CT>(kMatAdd, pSrcA, pSrcB, pDst, (CT)0, 0, false, batch, stream, "arm_mat_add_" #SUF "_batch"); \
-  }                                                                                                              \
-  arm_status arm_mat_sub_##SUF##_batch(const INST* pSrcA, const INST* pSrcB, INST* pDst, uint32_t batch,         \
-                                       void* stream) {                                                           \
-    return mat_ew<CT>(kMatSub, pSrcA, pSrcB, pDst, (CT)0, 0, false, batch, stream, "arm_mat_sub_" #SUF "_batch"); \
-  }
-MI355X_MAT_EW(f32, arm_matrix_instance_f32, float32_t, float)
-MI355X_MAT_EW(q31, arm_matrix_instance_q31, q31_t, int32_t)
-MI355X_MAT_EW(q15, arm_matrix_instance_q15, q15_t, int16_t)
-#undef MI355X_MAT_EW
-
-arm_status arm_mat_scale_f32(const arm_matrix_instance_f32* pSrc, float32_t scale, arm_matrix_instance_f32* pDst) {
-  return mat_ew<float>(kMatScale, pSrc, (const arm_matrix_instance_f32*)nullptr, pDst, scale, 0, true, 1, nullptr,
-                       "arm_mat_scale_f32");
-}
-arm_status arm_mat_scale_f32_batch(const arm_matrix_instance_f32* pSrc, float32_t scale,
-                                   arm_matrix_instance_f32* pDst, uint32_t batch, void* stream) {
-  return mat_ew<float>(kMatScale, pSrc, (const arm_matrix_instance_f32*)nullptr, pDst, scale, 0, false, batch, stream,
-                       "arm_mat_scale_f32_batch");
-}
-#define MI355X_MAT_SCALE(SUF, INST, T, CT)                                                                       \
-  arm_status arm_mat_scale_##SUF(const INST* pSrc, T scaleFract, int32_t shift, INST* pDst) {                    \
-    return mat_ew<CT>(kMatScale, pSrc, (const INST*)nullptr, pDst, scaleFract, shift, true, 1, nullptr,          \
-                      "arm_mat_scale_" #SUF);                                                                    \
-  }                                                                                                              \
-  arm_status arm_mat_scale_##SUF##_batch(const INST* pSrc, T scaleFract, int32_t shift, INST* pDst,              \
-                                         uint32_t batch, void* stream) {                                         \
-    return mat_ew<CT>(kMatScale, pSrc, (const INST*)nullptr, pDst, scaleFract, shift, false, batch, stream,      \
-                      "arm_mat_scale_" #SUF "_batch");                                                           \
-  }
-MI355X_MAT_SCALE(q31, arm_matrix_instance_q31, q31_t, int32_t)
-MI355X_MAT_SCALE(q15, arm_matrix_instance_q15, q15_t, int16_t)
-#undef MI355X_MAT_SCALE
-
-// NAME: trans / cmplx_trans; WORDS: CT words per element
-#define MI355X_MAT_TRANS(NAME, SUF, INST, CT, WORDS)                                                             \
-  arm_status arm_mat_##NAME##_##SUF(const INST* pSrc, INST* pDst) {                                              \
-    return mat_trans<CT>(pSrc, pDst, WORDS, true, 1, nullptr, "arm_mat_" #NAME "_" #SUF);                        \
-  }                                                                                                              \
-  arm_status arm_mat_##NAME##_##SUF##_batch(const INST* pSrc, INST* pDst, uint32_t batch, void* stream) {        \
-    return mat_trans<CT>(pSrc, pDst, WORDS, false, batch, stream, "arm_mat_" #NAME "_" #SUF "_batch");           \
-  }
-MI355X_MAT_TRANS(trans, f32, arm_matrix_instance_f32, float, 1)
-MI355X_MAT_TRANS(trans, q31, arm_matrix_instance_q31, int32_t, 1)
-MI355X_MAT_TRANS(trans, q15, arm_matrix_instance_q15, int16_t, 1)
-MI355X_MAT_TRANS(trans, q7, arm_matrix_instance_q7, int8_t, 1)
-MI355X_MAT_TRANS(cmplx_trans, f32, arm_matrix_instance_f32, float, 2)
-MI355X_MAT_TRANS(cmplx_trans, q31, arm_matrix_instance_q31, int32_t, 2)
-MI355X_MAT_TRANS(cmplx_trans, q15, arm_matrix_instance_q15, int16_t, 2)
-#undef MI355X_MAT_TRANS
-
-#define MI355X_MAT_VEC(SUF, INST, T, CT)                                                                         \
-  void arm_mat_vec_mult_##SUF(const INST* pSrcMat, const T* pVec, T* pDst) {                                     \
-    mat_vec_mult_sync<CT>(pSrcMat, (const CT*)pVec, (CT*)pDst, "arm_mat_vec_mult_" #SUF);                        \
-  }                                                                                                              \
-  arm_status arm_mat_vec_mult_##SUF##_batch(const INST* pSrcMat, uint32_t matStride, const T* d_vec, T* d_dst,   \
-                                            uint32_t batch, void* stream) {                                      \
-    return mat_vec_mult_batch<CT>(pSrcMat, matStride, (const CT*)d_vec, (CT*)d_dst, batch, stream,               \
-                                  "arm_mat_vec_mult_" #SUF "_batch");                                            \
-  }
-MI355X_MAT_VEC(f32, arm_matrix_instance_f32, float32_t, float)
-MI355X_MAT_VEC(q31, arm_matrix_instance_q31, q31_t, int32_t)
-MI355X_MAT_VEC(q15, arm_matrix_instance_q15, q15_t, int16_t)
-MI355X_MAT_VEC(q7, arm_matrix_instance_q7, q7_t, int8_t)
-#undef MI355X_MAT_VEC
-
-// ---- complex math, max / min; cmplx_ew and its kin precede the C block ----
-// one source: mag, mag_squared, conj
-#define MI355X_CMPLX_1(NAME, OP, SUF, T, CT)                                                                     \
-  void arm_cmplx_##NAME##_##SUF(const T* pSrc, T* pDst, uint32_t numSamples) {                                   \
-    cmplx_ew<CT>(OP, (const CT*)pSrc, (const CT*)nullptr, (CT*)pDst, numSamples, true, 1, nullptr,               \
-                 "arm_cmplx_" #NAME "_" #SUF);                                                                   \
-  }                                                                                                              \
-  arm_status arm_cmplx_##NAME##_##SUF##_batch(const T* d_src, T* d_dst, uint32_t numSamples, uint32_t batch,     \
-                                              void* stream) {                                                    \
-    return cmplx_ew<CT>(OP, (const CT*)d_src, (const CT*)nullptr, (CT*)d_dst, numSamples, false, batch, stream,  \
-                        "arm_cmplx_" #NAME "_" #SUF "_batch");                                                   \
-  }
-// two sources: mult_cmplx (pSrcB complex), mult_real (pSrcB real)
-#define MI355X_CMPLX_2(NAME, OP, SUF, T, CT)                                                                     \
-  void arm_cmplx_##NAME##_##SUF(const T* pSrcA, const T* pSrcB, T* pDst, uint32_t numSamples) {                  \
-    cmplx_ew<CT>(OP, (const CT*)pSrcA, (const CT*)pSrcB, (CT*)pDst, numSamples, true, 1, nullptr,                \
-                 "arm_cmplx_" #NAME "_" #SUF);                                                                   \
-  }                                                                                                              \
-  arm_status arm_cmplx_##NAME##_##SUF##_batch(const T* d_srcA, const T* d_srcB, T* d_dst, uint32_t numSamples,   \
-                                              uint32_t batch, void* stream) {                                    \
-    return cmplx_ew<CT>(OP, (const CT*)d_srcA, (const CT*)d_srcB, (CT*)d_dst, numSamples, false, batch, stream,  \
-                        "arm_cmplx_" #NAME "_" #SUF "_batch");                                                   \
-  }
-#define MI355X_CMPLX_DOT(SUF, T, CT, R, CR)                                                                      \
-  void arm_cmplx_dot_prod_##SUF(const T* pSrcA, const T* pSrcB, uint32_t numSamples, R* realResult,              \
-                                R* imagResult) {                                                                 \
-    cmplx_dot<CT, CR>((const CT*)pSrcA, (const CT*)pSrcB, numSamples, numSamples, (CR*)realResult,               \
-                      (CR*)imagResult, true, 1, nullptr, "arm_cmplx_dot_prod_" #SUF);                            \
-  }                                                                                                              \
-  arm_status arm_cmplx_dot_prod_##SUF##_batch(const T* d_a, const T* d_b, uint32_t bStride, uint32_t numSamples, \
-                                              R* d_re, R* d_im, uint32_t batch, void* stream) {                  \
-    return cmplx_dot<CT, CR>((const CT*)d_a, (const CT*)d_b, bStride, numSamples, (CR*)d_re, (CR*)d_im, false,   \
-                             batch, stream, "arm_cmplx_dot_prod_" #SUF "_batch");                                \
-  }
-#define MI355X_CMPLX_TYPE(SUF, T, CT, R, CR)                   \
-  MI355X_CMPLX_1(mag, kCmMag, SUF, T, CT)                      \
-  MI355X_CMPLX_1(mag_squared, kCmMagSquared, SUF, T, CT)       \
-  MI355X_CMPLX_1(conj, kCmConj, SUF, T, CT)                    \
-  MI355X_CMPLX_2(mult_cmplx, kCmMultCmplx, SUF, T, CT)         \
-  MI355X_CMPLX_2(mult_real, kCmMultReal, SUF, T, CT)           \
-  MI355X_CMPLX_DOT(SUF, T, CT, R, CR)
-MI355X_CMPLX_TYPE(f32, float32_t, float, float32_t, float)
-MI355X_CMPLX_TYPE(q31, q31_t, int32_t, q63_t, int64_t)
-MI355X_CMPLX_TYPE(q15, q15_t, int16_t, q31_t, int32_t)
-#undef MI355X_CMPLX_TYPE
-#undef MI355X_CMPLX_DOT
-#undef MI355X_CMPLX_2
-#undef MI355X_CMPLX_1
-
-#define MI355X_SEARCH(NAME, MAX, SUF, T, CT)                                                                     \
-  void arm_##NAME##_##SUF(const T* pSrc, uint32_t blockSize, T* pResult, uint32_t* pIndex) {                     \
-    cm_search<CT>(MAX, (const CT*)pSrc, blockSize, (CT*)pResult, pIndex, true, 1, nullptr, "arm_" #NAME "_" #SUF); \
-  }                                                                                                              \
-  arm_status arm_##NAME##_##SUF##_batch(const T* d_src, uint32_t blockSize, T* d_result, uint32_t* d_index,      \
-                                        uint32_t batch, void* stream) {                                          \
-    return cm_search<CT>(MAX, (const CT*)d_src, blockSize, (CT*)d_result, d_index, false, batch, stream,         \
-                         "arm_" #NAME "_" #SUF "_batch");                                                        \
-  }
-#define MI355X_SEARCH_TYPE(SUF, T, CT) MI355X_SEARCH(max, true, SUF, T, CT) MI355X_SEARCH(min, false, SUF, T, CT)
-MI355X_SEARCH_TYPE(f32, float32_t, float)
-MI355X_SEARCH_TYPE(q31, q31_t, int32_t)
-MI355X_SEARCH_TYPE(q15, q15_t, int16_t)
-MI355X_SEARCH_TYPE(q7, q7_t, int8_t)
-#undef MI355X_SEARCH_TYPE
-#undef MI355X_SEARCH
-
-// arm_cmplx_mag_fast_q15: one more operation of the element-wise kernel
-void arm_cmplx_mag_fast_q15(const q15_t* pSrc, q15_t* pDst, uint32_t numSamples) {
-  cmplx_ew<int16_t>(kCmMagFast, pSrc, (const int16_t*)nullptr, pDst, numSamples, true, 1, nullptr,
-                    "arm_cmplx_mag_fast_q15");
-}
-arm_status arm_cmplx_mag_fast_q15_batch(const q15_t* d_src, q15_t* d_dst, uint32_t numSamples, uint32_t batch,
-                                        void* stream) {
-  return cmplx_ew<int16_t>(kCmMagFast, d_src, (const int16_t*)nullptr, d_dst, numSamples, false, batch, stream,
-                           "arm_cmplx_mag_fast_q15_batch");
-}
-// the scalar of fast_math_functions.h, computed on the host
-arm_status arm_sqrt_q15(q15_t in, q15_t* pOut) {
-  if (!pOut) return ARM_MATH_ARGUMENT_ERROR;
-  *pOut = sqrt_q15_host(in);
-  return in >= 0 ? ARM_MATH_SUCCESS : ARM_MATH_ARGUMENT_ERROR;
-}
-
-// ---- statistics; st_sum and st_search precede the C block ----
-#define MI355X_STAT_1(NAME, OP, SUF, T, CT, R, CR)                                                               \
-  void arm_##NAME##_##SUF(const T* pSrc, uint32_t blockSize, R* pResult) {                                       \
-    st_sum<CT, CR>(OP, (const CT*)pSrc, (const CT*)nullptr, blockSize, (CR*)pResult, true, 1, nullptr,           \
-                   "arm_" #NAME "_" #SUF);                                                                       \
-  }                                                                                                              \
-  arm_status arm_##NAME##_##SUF##_batch(const T* d_src, uint32_t blockSize, R* d_result, uint32_t batch,         \
-                                        void* stream) {                                                          \
-    return st_sum<CT, CR>(OP, (const CT*)d_src, (const CT*)nullptr, blockSize, (CR*)d_result, false, batch,      \
-                          stream, "arm_" #NAME "_" #SUF "_batch");                                               \
-  }
-#define MI355X_STAT_MSE(SUF, T, CT)                                                                              \
-  void arm_mse_##SUF(const T* pSrcA, const T* pSrcB, uint32_t blockSize, T* pResult) {                           \
-    st_sum<CT, CT>(kStMse, (const CT*)pSrcA, (const CT*)pSrcB, blockSize, (CT*)pResult, true, 1, nullptr,        \
-                   "arm_mse_" #SUF);                                                                             \
-  }                                                                                                              \
-  arm_status arm_mse_##SUF##_batch(const T* d_a, const T* d_b, uint32_t blockSize, T* d_result, uint32_t batch,  \
-                                   void* stream) {                                                               \
-    return st_sum<CT, CT>(kStMse, (const CT*)d_a, (const CT*)d_b, blockSize, (CT*)d_result, false, batch,        \
-                          stream, "arm_mse_" #SUF "_batch");                                                     \
-  }
-#define MI355X_STAT_LEVELS(SUF, T, CT)               \
-  MI355X_STAT_1(rms, kStRms, SUF, T, CT, T, CT)      \
-  MI355X_STAT_1(var, kStVar, SUF, T, CT, T, CT)      \
-  MI355X_STAT_1(std, kStStd, SUF, T, CT, T, CT)
-#define MI355X_STAT_TYPE(SUF, T, CT, PR, CPR)        \
-  MI355X_STAT_1(mean, kStMean, SUF, T, CT, T, CT)    \
-  MI355X_STAT_1(power, kStPower, SUF, T, CT, PR, CPR) \
-  MI355X_STAT_MSE(SUF, T, CT)
-MI355X_STAT_TYPE(f32, float32_t, float, float32_t, float)
-MI355X_STAT_TYPE(q31, q31_t, int32_t, q63_t, int64_t)
-MI355X_STAT_TYPE(q15, q15_t, int16_t, q63_t, int64_t)
-MI355X_STAT_TYPE(q7, q7_t, int8_t, q31_t, int32_t)
-MI355X_STAT_LEVELS(f32, float32_t, float)
-MI355X_STAT_LEVELS(q31, q31_t, int32_t)
-MI355X_STAT_LEVELS(q15, q15_t, int16_t)
-MI355X_STAT_1(accumulate, kStAccumulate, f32, float32_t, float, float32_t, float)
-#undef MI355X_STAT_TYPE
-#undef MI355X_STAT_LEVELS
-#undef MI355X_STAT_MSE
-#undef MI355X_STAT_1
-
-// abs searches with the index, and the four searches without it
-#define MI355X_STAT_SEARCH(NAME, MAX, ABS, SUF, T, CT)                                                           \
-  void arm_##NAME##_##SUF(const T* pSrc, uint32_t blockSize, T* pResult, uint32_t* pIndex) {                     \
-    st_search<CT>(MAX, ABS, true, (const CT*)pSrc, blockSize, (CT*)pResult, pIndex, true, 1, nullptr,            \
-                  "arm_" #NAME "_" #SUF);                                                                        \
-  }                                                                                                              \
-  arm_status arm_##NAME##_##SUF##_batch(const T* d_src, uint32_t blockSize, T* d_result, uint32_t* d_index,      \
-                                        uint32_t batch, void* stream) {                                          \
-    return st_search<CT>(MAX, ABS, true, (const CT*)d_src, blockSize, (CT*)d_result, d_index, false, batch,      \
-                         stream, "arm_" #NAME "_" #SUF "_batch");                                                \
-  }
-#define MI355X_STAT_NO_IDX(NAME, MAX, ABS, SUF, T, CT)                                                           \
-  void arm_##NAME##_no_idx_##SUF(const T* pSrc, uint32_t blockSize, T* pResult) {                                \
-    st_search<CT>(MAX, ABS, false, (const CT*)pSrc, blockSize, (CT*)pResult, nullptr, true, 1, nullptr,          \
-                  "arm_" #NAME "_no_idx_" #SUF);                                                                 \
-  }                                                                                                              \
-  arm_status arm_##NAME##_no_idx_##SUF##_batch(const T* d_src, uint32_t blockSize, T* d_result, uint32_t batch,  \
-                                               void* stream) {                                                   \
-    return st_search<CT>(MAX, ABS, false, (const CT*)d_src, blockSize, (CT*)d_result, nullptr, false, batch,     \
-                         stream, "arm_" #NAME "_no_idx_" #SUF "_batch");                                         \
-  }
-#define MI355X_STAT_SEARCH_TYPE(SUF, T, CT)             \
-  MI355X_STAT_SEARCH(absmax, true, true, SUF, T, CT)    \
-  MI355X_STAT_SEARCH(absmin, false, true, SUF, T, CT)   \
-  MI355X_STAT_NO_IDX(max, true, false, SUF, T, CT)      \
-  MI355X_STAT_NO_IDX(min, false, false, SUF, T, CT)     \
-  MI355X_STAT_NO_IDX(absmax, true, true, SUF, T, CT)    \
-  MI355X_STAT_NO_IDX(absmin, false, true, SUF, T, CT)
-MI355X_STAT_SEARCH_TYPE(f32, float32_t, float)
-MI355X_STAT_SEARCH_TYPE(q31, q31_t, int32_t)
-MI355X_STAT_SEARCH_TYPE(q15, q15_t, int16_t)
-MI355X_STAT_SEARCH_TYPE(q7, q7_t, int8_t)
-#undef MI355X_STAT_SEARCH_TYPE
-#undef MI355X_STAT_NO_IDX
-#undef MI355X_STAT_SEARCH
-
-// ---- basic math; bm_ew and bm_dot precede the C block ----
-#define MI355X_BM_2(NAME, OP, SUF, T, CT)                                                                        \
-  void arm_##NAME##_##SUF(const T* pSrcA, const T* pSrcB, T* pDst, uint32_t blockSize) {                         \
-    bm_ew<CT>(OP, (const CT*)pSrcA, (const CT*)pSrcB, (CT*)pDst, blockSize, (CT)0, (CT)0, 0, true, 1, nullptr,   \
-              "arm_" #NAME "_" #SUF);                                                                            \
-  }                                                                                                              \
-  arm_status arm_##NAME##_##SUF##_batch(const T* d_srcA, const T* d_srcB, T* d_dst, uint32_t blockSize,          \
-                                        uint32_t batch, void* stream) {                                          \
-    return bm_ew<CT>(OP, (const CT*)d_srcA, (const CT*)d_srcB, (CT*)d_dst, blockSize, (CT)0, (CT)0, 0, false,    \
-                     batch, stream, "arm_" #NAME "_" #SUF "_batch");                                             \
-  }
-#define MI355X_BM_1(NAME, OP, SUF, T, CT)                                                                        \
-  void arm_##NAME##_##SUF(const T* pSrc, T* pDst, uint32_t blockSize) {                                          \
-    bm_ew<CT>(OP, (const CT*)pSrc, (const CT*)nullptr, (CT*)pDst, blockSize, (CT)0, (CT)0, 0, true, 1, nullptr,  \
-              "arm_" #NAME "_" #SUF);                                                                            \
-  }                                                                                                              \
-  arm_status arm_##NAME##_##SUF##_batch(const T* d_src, T* d_dst, uint32_t blockSize, uint32_t batch,            \
-                                        void* stream) {                                                          \
-    return bm_ew<CT>(OP, (const CT*)d_src, (const CT*)nullptr, (CT*)d_dst, blockSize, (CT)0, (CT)0, 0, false,    \
-                     batch, stream, "arm_" #NAME "_" #SUF "_batch");                                             \
-  }
-#define MI355X_BM_OFFSET(NAME, OP, SUF, T, CT)                                                                   \
-  void arm_##NAME##_##SUF(const T* pSrc, T value, T* pDst, uint32_t blockSize) {                                 \
-    bm_ew<CT>(OP, (const CT*)pSrc, (const CT*)nullptr, (CT*)pDst, blockSize, (CT)value, (CT)0, 0, true, 1,       \
-              nullptr, "arm_" #NAME "_" #SUF);                                                                   \
-  }                                                                                                              \
-  arm_status arm_##NAME##_##SUF##_batch(const T* d_src, T value, T* d_dst, uint32_t blockSize, uint32_t batch,   \
-                                        void* stream) {                                                          \
-    return bm_ew<CT>(OP, (const CT*)d_src, (const CT*)nullptr, (CT*)d_dst, blockSize, (CT)value, (CT)0, 0,       \
-                     false, batch, stream, "arm_" #NAME "_" #SUF "_batch");                                      \
-  }
-#define MI355X_BM_SCALE(SUF, T, CT)                                                                              \
-  void arm_scale_##SUF(const T* pSrc, T scaleFract, int8_t shift, T* pDst, uint32_t blockSize) {                 \
-    bm_ew<CT>(kBmScale, (const CT*)pSrc, (const CT*)nullptr, (CT*)pDst, blockSize, (CT)scaleFract, (CT)0, shift, \
-              true, 1, nullptr, "arm_scale_" #SUF);                                                              \
-  }                                                                                                              \
-  arm_status arm_scale_##SUF##_batch(const T* d_src, T scaleFract, int8_t shift, T* d_dst, uint32_t blockSize,   \
-                                     uint32_t batch, void* stream) {                                             \
-    return bm_ew<CT>(kBmScale, (const CT*)d_src, (const CT*)nullptr, (CT*)d_dst, blockSize, (CT)scaleFract,      \
-                     (CT)0, shift, false, batch, stream, "arm_scale_" #SUF "_batch");                            \
-  }
-#define MI355X_BM_SHIFT(SUF, T, CT)                                                                              \
-  void arm_shift_##SUF(const T* pSrc, int8_t shiftBits, T* pDst, uint32_t blockSize) {                           \
-    bm_ew<CT>(kBmShift, (const CT*)pSrc, (const CT*)nullptr, (CT*)pDst, blockSize, (CT)0, (CT)0, shiftBits,      \
-              true, 1, nullptr, "arm_shift_" #SUF);                                                              \
-  }                                                                                                              \
-  arm_status arm_shift_##SUF##_batch(const T* d_src, int8_t shiftBits, T* d_dst, uint32_t blockSize,             \
-                                     uint32_t batch, void* stream) {                                             \
-    return bm_ew<CT>(kBmShift, (const CT*)d_src, (const CT*)nullptr, (CT*)d_dst, blockSize, (CT)0, (CT)0,        \
-                     shiftBits, false, batch, stream, "arm_shift_" #SUF "_batch");                               \
-  }
-#define MI355X_BM_CLIP(SUF, T, CT)                                                                               \
-  void arm_clip_##SUF(const T* pSrc, T* pDst, T low, T high, uint32_t numSamples) {                              \
-    bm_ew<CT>(kBmClip, (const CT*)pSrc, (const CT*)nullptr, (CT*)pDst, numSamples, (CT)low, (CT)high, 0, true,   \
-              1, nullptr, "arm_clip_" #SUF);                                                                     \
-  }                                                                                                              \
-  arm_status arm_clip_##SUF##_batch(const T* d_src, T* d_dst, T low, T high, uint32_t numSamples,                \
-                                    uint32_t batch, void* stream) {                                              \
-    return bm_ew<CT>(kBmClip, (const CT*)d_src, (const CT*)nullptr, (CT*)d_dst, numSamples, (CT)low, (CT)high,   \
-                     0, false, batch, stream, "arm_clip_" #SUF "_batch");                                        \
-  }
-#define MI355X_BM_DOT(SUF, T, CT, R, CR)                                                                         \
-  void arm_dot_prod_##SUF(const T* pSrcA, const T* pSrcB, uint32_t blockSize, R* result) {                       \
-    bm_dot<CT, CR>((const CT*)pSrcA, (const CT*)pSrcB, blockSize, blockSize, (CR*)result, true, 1, nullptr,      \
-                   "arm_dot_prod_" #SUF);                                                                        \
-  }                                                                                                              \
-  arm_status arm_dot_prod_##SUF##_batch(const T* d_a, const T* d_b, uint32_t bStride, uint32_t blockSize,        \
-                                        R* d_result, uint32_t batch, void* stream) {                             \
-    return bm_dot<CT, CR>((const CT*)d_a, (const CT*)d_b, bStride, blockSize, (CR*)d_result, false, batch,       \
-                          stream, "arm_dot_prod_" #SUF "_batch");                                                \
-  }
-#define MI355X_BM_TYPE(SUF, T, CT, R, CR)          \
-  MI355X_BM_2(add, kBmAdd, SUF, T, CT)             \
-  MI355X_BM_2(sub, kBmSub, SUF, T, CT)             \
-  MI355X_BM_2(mult, kBmMult, SUF, T, CT)           \
-  MI355X_BM_OFFSET(offset, kBmOffset, SUF, T, CT)  \
-  MI355X_BM_CLIP(SUF, T, CT)                       \
-  MI355X_BM_1(abs, kBmAbs, SUF, T, CT)             \
-  MI355X_BM_1(negate, kBmNegate, SUF, T, CT)       \
-  MI355X_BM_DOT(SUF, T, CT, R, CR)
-#define MI355X_BM_BITS(SUF, T)                     \
-  MI355X_BM_2(and, kBmAnd, SUF, T, T)              \
-  MI355X_BM_2(or, kBmOr, SUF, T, T)                \
-  MI355X_BM_2(xor, kBmXor, SUF, T, T)              \
-  MI355X_BM_1(not, kBmNot, SUF, T, T)
-MI355X_BM_TYPE(f32, float32_t, float, float32_t, float)
-MI355X_BM_TYPE(q31, q31_t, int32_t, q63_t, int64_t)
-MI355X_BM_TYPE(q15, q15_t, int16_t, q63_t, int64_t)
-MI355X_BM_TYPE(q7, q7_t, int8_t, q31_t, int32_t)
-MI355X_BM_OFFSET(scale, kBmScale, f32, float32_t, float)
-MI355X_BM_SCALE(q31, q31_t, int32_t)
-MI355X_BM_SCALE(q15, q15_t, int16_t)
-MI355X_BM_SCALE(q7, q7_t, int8_t)
-MI355X_BM_SHIFT(q31, q31_t, int32_t)
-MI355X_BM_SHIFT(q15, q15_t, int16_t)
-MI355X_BM_SHIFT(q7, q7_t, int8_t)
-MI355X_BM_BITS(u32, uint32_t)
-MI355X_BM_BITS(u16, uint16_t)
-MI355X_BM_BITS(u8, uint8_t)
-#undef MI355X_BM_BITS
-#undef MI355X_BM_TYPE
-#undef MI355X_BM_DOT
-#undef MI355X_BM_CLIP
-#undef MI355X_BM_SHIFT
-#undef MI355X_BM_SCALE
-#undef MI355X_BM_OFFSET
-#undef MI355X_BM_1
-#undef MI355X_BM_2
-
-// ---- support functions; sp_convert .. sp_barycenter precede the C block ----
-#define MI355X_SP_TO(SN, ST, SCT, DN, DT, DCT)                                                                   \
-  void arm_##SN##_to_##DN(const ST* pSrc, DT* pDst, uint32_t blockSize) {                                        \
-    sp_convert<SCT, DCT>((const SCT*)pSrc, (DCT*)pDst, blockSize, true, 1, nullptr, "arm_" #SN "_to_" #DN);      \
-  }                                                                                                              \
-  arm_status arm_##SN##_to_##DN##_batch(const ST* d_src, DT* d_dst, uint32_t blockSize, uint32_t batch,          \
-                                        void* stream) {                                                          \
-    return sp_convert<SCT, DCT>((const SCT*)d_src, (DCT*)d_dst, blockSize, false, batch, stream,                 \
-                                "arm_" #SN "_to_" #DN "_batch");                                                 \
-  }
-#define MI355X_SP_COPY(SUF, T, CT)                                                                               \
-  void arm_copy_##SUF(const T* pSrc, T* pDst, uint32_t blockSize) {                                              \
-    sp_convert<CT, CT>((const CT*)pSrc, (CT*)pDst, blockSize, true, 1, nullptr, "arm_copy_" #SUF);               \
-  }                                                                                                              \
-  arm_status arm_copy_##SUF##_batch(const T* d_src, T* d_dst, uint32_t blockSize, uint32_t batch, void* stream) { \
-    return sp_convert<CT, CT>((const CT*)d_src, (CT*)d_dst, blockSize, false, batch, stream,                     \
-                              "arm_copy_" #SUF "_batch");                                                        \
-  }                                                                                                              \
-  void arm_fill_##SUF(T value, T* pDst, uint32_t blockSize) {                                                    \
-    sp_fill<CT>((CT)value, (CT*)pDst, blockSize, true, 1, nullptr, "arm_fill_" #SUF);                            \
-  }                                                                                                              \
-  arm_status arm_fill_##SUF##_batch(T value, T* d_dst, uint32_t blockSize, uint32_t batch, void* stream) {       \
-    return sp_fill<CT>((CT)value, (CT*)d_dst, blockSize, false, batch, stream, "arm_fill_" #SUF "_batch");       \
-  }
-MI355X_SP_TO(float, float32_t, float, q31, q31_t, int32_t)
-MI355X_SP_TO(float, float32_t, float, q15, q15_t, int16_t)
-MI355X_SP_TO(float, float32_t, float, q7, q7_t, int8_t)
-MI355X_SP_TO(q31, q31_t, int32_t, float, float32_t, float)
-MI355X_SP_TO(q31, q31_t, int32_t, q15, q15_t, int16_t)
-MI355X_SP_TO(q31, q31_t, int32_t, q7, q7_t, int8_t)
-MI355X_SP_TO(q15, q15_t, int16_t, float, float32_t, float)
-MI355X_SP_TO(q15, q15_t, int16_t, q31, q31_t, int32_t)
-MI355X_SP_TO(q15, q15_t, int16_t, q7, q7_t, int8_t)
-MI355X_SP_TO(q7, q7_t, int8_t, float, float32_t, float)
-MI355X_SP_TO(q7, q7_t, int8_t, q31, q31_t, int32_t)
-MI355X_SP_TO(q7, q7_t, int8_t, q15, q15_t, int16_t)
-MI355X_SP_COPY(f32, float32_t, float)
-MI355X_SP_COPY(q31, q31_t, int32_t)
-MI355X_SP_COPY(q15, q15_t, int16_t)
-MI355X_SP_COPY(q7, q7_t, int8_t)
-#undef MI355X_SP_COPY
-#undef MI355X_SP_TO
-
-// S->alg selects among equal results: a value of arm_sort_alg sorts, any other is the no-op of the reference's switch.
-void arm_sort_f32(const arm_sort_instance_f32* S, float32_t* pSrc, float32_t* pDst, uint32_t blockSize) {
-  if (!S) { cm_null(true, "arm_sort_f32"); return; }
-  if ((int)S->alg < (int)ARM_SORT_BITONIC || (int)S->alg > (int)ARM_SORT_SELECTION) return;
-  sp_sort((int)S->dir, pSrc, pDst, blockSize, true, 1, nullptr, "arm_sort_f32");
-}
-// S->buffer is neither read nor written.
-void arm_merge_sort_f32(const arm_merge_sort_instance_f32* S, float32_t* pSrc, float32_t* pDst, uint32_t blockSize) {
-  if (!S) { cm_null(true, "arm_merge_sort_f32"); return; }
-  sp_sort((int)S->dir, pSrc, pDst, blockSize, true, 1, nullptr, "arm_merge_sort_f32");
-}
-arm_status arm_sort_f32_batch(const float32_t* d_src, float32_t* d_dst, uint32_t blockSize, arm_sort_dir dir,
-                              uint32_t batch, void* stream) {
-  return sp_sort((int)dir, d_src, d_dst, blockSize, false, batch, stream, "arm_sort_f32_batch");
-}
-arm_status arm_merge_sort_f32_batch(const float32_t* d_src, float32_t* d_dst, uint32_t blockSize, arm_sort_dir dir,
-                                    uint32_t batch, void* stream) {
-  return sp_sort((int)dir, d_src, d_dst, blockSize, false, batch, stream, "arm_merge_sort_f32_batch");
-}
-float32_t arm_weighted_average_f32(const float32_t* in, const float32_t* weights, uint32_t blockSize) {
-  float32_t r = 0.0f;
-  if (sp_wavg(in, weights, blockSize, blockSize, &r, true, 1, nullptr, "arm_weighted_average_f32") !=
-      ARM_MATH_SUCCESS)
-    return __builtin_nanf("");
-  return r;
-}
-arm_status arm_weighted_average_f32_batch(const float32_t* d_in, const float32_t* d_weights, uint32_t wStride,
-                                          uint32_t blockSize, float32_t* d_result, uint32_t batch, void* stream) {
-  return sp_wavg(d_in, d_weights, wStride, blockSize, d_result, false, batch, stream,
-                 "arm_weighted_average_f32_batch");
-}
-void arm_barycenter_f32(const float32_t* in, const float32_t* weights, float32_t* out, uint32_t nbVectors,
-                        uint32_t vecDim) {
-  sp_barycenter(in, weights, nbVectors, out, nbVectors, vecDim, true, 1, nullptr, "arm_barycenter_f32");
-}
-arm_status arm_barycenter_f32_batch(const float32_t* d_in, const float32_t* d_weights, uint32_t wStride,
-                                    float32_t* d_out, uint32_t nbVectors, uint32_t vecDim, uint32_t batch,
-                                    void* stream) {
-  return sp_barycenter(d_in, d_weights, wStride, d_out, nbVectors, vecDim, false, batch, stream,
-                       "arm_barycenter_f32_batch");
-}
 
 // ---- convolution ------------------------------------------------------------------
 #define MI355X_CONV_FULL(NAME, T, CT, OP, VAR)                                                                  \

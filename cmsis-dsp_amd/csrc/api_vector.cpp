@@ -1,0 +1,929 @@
+// C ABI of the stateless vector and matrix families: the f32 solves, the basic matrix functions, complex math
+// with max / min, statistics, basic math and the support functions, each as the drop-in of arm_math.h and the
+// batched device form of arm_math_mi355x.h.  Every family describes a call as a table of operands and hands it to
+// one driver (VecCall); api.cpp holds the transforms, filters, convolution, MFCC and the matrix multiplies.
+#include <type_traits>
+
+#include "../../include/arm_math.h"
+#include "../../include/arm_math_mi355x.h"
+#include "api_status.hpp"
+#include "kernels.hpp"
+#include "runtime.hpp"
+
+using namespace mi355x;
+
+namespace {
+
+// ---- the call driver --------------------------------------------------------------------------------------
+// The calling contract of these families ("Calling contract of the vector and matrix families"):
+//   * sync (the drop-in): operands are host or device pointers.  A null operand is refused first; void functions
+//     report it through the last error, the matrix functions that return a status through that alone (kQuietNull).
+//     Host words are staged into device scratch (slot = operand index), a device pointer is used in place, and the
+//     call returns after the stream has drained.
+//   * batched: operands are device pointers, the call only enqueues.  A null operand is refused after the family's
+//     parameter refusals and its empty-call rule, with ARM_MATH_ARGUMENT_ERROR and no last error.
+//   * the overlap rule, on the pointers the kernel is given (the caller's in a batched call; the staged ones in a
+//     sync call, where host operands that are exactly the same buffer share one scratch slot and any other host
+//     overlap has gone): a result must not overlap a source, except that it may be exactly the source where the
+//     source allows it (kExactOk), and must not overlap another result.  A refusal is hipErrorInvalidValue under
+//     `what`.  The matrix functions and the solves have no overlap rule (kNoOverlapRule).
+enum : unsigned { kIn = 1, kOut = 2, kExactOk = 4 };        // Operand::role: a source, a result, or both
+enum : unsigned { kNoOverlapRule = 1, kQuietNull = 2 };     // VecCall::flags
+constexpr int kMaxOperands = 5;
+
+// One operand of a call: its byte span over the whole call.  A sync call copies a host source in (a span without
+// words is not copied) and a host result out.
+struct Operand {
+  const void* p;
+  size_t bytes;
+  unsigned role;
+};
+
+bool spans_overlap(const void* d, size_t db, const void* s, size_t sb, bool exactOk) {
+  if (!db || !sb) return false;
+  if (d == s && db == sb && exactOk) return false;
+  const uintptr_t d0 = (uintptr_t)d, s0 = (uintptr_t)s;
+  return d0 < s0 + sb && s0 < d0 + db;
+}
+
+struct VecCall {
+  const char* what;
+  bool sync;
+  void* stream;          // batched calls; a sync call runs on sync_stream()
+  unsigned flags;
+  int n;
+  Operand op[kMaxOperands];
+
+  bool any_null() const {
+    for (int i = 0; i < n; ++i)
+      if (!op[i].p) return true;
+    return false;
+  }
+
+  // The first test of a helper: a drop-in refuses a null operand before anything else.
+  bool null_in_sync() const {
+    if (!sync || !any_null()) return false;
+    if (!(flags & kQuietNull)) set_error(hipErrorInvalidValue, what);
+    return true;
+  }
+
+  bool overlap_refused(void* const* p) const {
+    if (flags & kNoOverlapRule) return false;
+    for (int i = 0; i < n; ++i) {
+      if (!(op[i].role & kOut)) continue;
+      for (int j = 0; j < n; ++j) {
+        const bool source = op[j].role & kIn;
+        if (j == i || (!source && j < i)) continue;          // a pair of results is tested once
+        if (spans_overlap(p[i], op[i].bytes, p[j], op[j].bytes, source && (op[j].role & kExactOk))) return true;
+      }
+    }
+    return false;
+  }
+
+  // The last step of a helper, after its parameter refusals and its empty-call rule.  launch(p, st) -> hipError_t
+  // receives the device pointer of every operand (p[i] for op[i], null past n) and the stream.
+  template <typename Launch>
+  arm_status run(Launch&& launch) const {
+    void* p[kMaxOperands] = {};
+    if (!sync) {
+      if (any_null()) return ARM_MATH_ARGUMENT_ERROR;
+      for (int i = 0; i < n; ++i) p[i] = const_cast<void*>(op[i].p);
+      return batch_status(overlap_refused(p) ? hipErrorInvalidValue : launch(p, (hipStream_t)stream), what);
+    }
+    hipStream_t st = sync_stream();
+    bool dev[kMaxOperands];
+    for (int i = 0; i < n; ++i) {
+      dev[i] = is_device_ptr(op[i].p);
+      p[i] = dev[i] ? const_cast<void*>(op[i].p) : scratch(op[i].bytes + 16, i);
+      for (int j = 0; j < i; ++j)          // exact alias (add / sub / scale in place): one staged copy
+        if (!dev[i] && op[j].p == op[i].p && op[j].bytes == op[i].bytes) p[i] = p[j];
+      if (!p[i]) { set_error(hipErrorOutOfMemory, what); return ARM_MATH_ARGUMENT_ERROR; }
+    }
+    HostIO io(st);
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < n && e == hipSuccess; ++i)
+      if (!dev[i] && (op[i].role & kIn) && op[i].bytes) e = io.in(p[i], op[i].p, op[i].bytes);
+    if (e == hipSuccess) e = overlap_refused(p) ? hipErrorInvalidValue : launch(p, st);
+    for (int i = 0; i < n && e == hipSuccess; ++i)
+      if (!dev[i] && (op[i].role & kOut)) e = io.out(const_cast<void*>(op[i].p), p[i], op[i].bytes);
+    if (e == hipSuccess) e = io.finish();
+    return batch_status(e, what);
+  }
+
+  // run() for the solves, whose items report a status word.  launch(p, d_status, st): a batched call passes the
+  // caller's d_status (may be null) through; a sync call stages one word out as one more result operand and returns
+  // it once the call itself has succeeded.
+  template <typename Launch>
+  arm_status run_with_status(int32_t* d_status, Launch&& launch) {
+    if (!sync) return run([&](void* const* p, hipStream_t st) { return launch(p, d_status, st); });
+    int32_t status = ARM_MATH_SUCCESS;
+    const int k = n++;
+    op[k] = {&status, sizeof(status), kOut};
+    const arm_status r = run([&](void* const* p, hipStream_t st) { return launch(p, (int32_t*)p[k], st); });
+    return r != ARM_MATH_SUCCESS ? r : (arm_status)status;
+  }
+};
+
+// a refusal of a parameter: a drop-in (most are void) also records it
+arm_status refuse(bool sync, const char* what) {
+  if (sync) set_error(hipErrorInvalidValue, what);
+  return ARM_MATH_ARGUMENT_ERROR;
+}
+
+// The reductions over a second source at a stride: the dot products (words 1), the weighted average (words 1) and
+// the complex dot products (words 2: interleaved samples and two results, otherwise r1 is null).  bStride (samples;
+// the drop-in passes n): 0 shares one b, otherwise >= n.  n == 0 stores what the empty sums give.
+// launch(a, b, r0, r1, st) -> hipError_t.
+template <typename T, typename R, typename Launch>
+arm_status strided_reduce(int words, const T* a, const T* b, uint32_t bStride, uint32_t n, R* r0, R* r1, bool sync,
+                          uint32_t batch, void* stream, const char* what, Launch&& launch) {
+  const size_t ab = sizeof(T) * words * n * batch, rb = sizeof(R) * batch;
+  const size_t bb = sizeof(T) * words * ((size_t)bStride * (batch - 1) + n);
+  const VecCall c{what, sync, stream, 0, words == 2 ? 4 : 3, {{a, ab, kIn}, {b, bb, kIn}, {r0, rb, kOut}, {r1, rb, kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (bStride != 0 && bStride < n) return ARM_MATH_ARGUMENT_ERROR;
+  if (batch == 0) return ARM_MATH_SUCCESS;
+  return c.run([&](void* const* p, hipStream_t st) {
+    return launch((const T*)p[0], (const T*)p[1], (R*)p[2], (R*)p[3], st);
+  });
+}
+
+// The max / min searches of cmplx_math.hip (abs false, idx true) and the abs / no-index searches of statistics.hip
+// (idx false: the _no_idx forms, index unused).  n == 0 is refused where the reference reads pSrc[0].
+template <typename T>
+arm_status search(bool max, bool abs, bool idx, const T* src, uint32_t n, T* result, uint32_t* index, bool sync,
+                  uint32_t batch, void* stream, const char* what) {
+  const VecCall c{what, sync, stream, 0, idx ? 3 : 2,
+                  {{src, sizeof(T) * n * batch, kIn}, {result, sizeof(T) * batch, kOut},
+                   {index, sizeof(uint32_t) * batch, kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (batch == 0) return ARM_MATH_SUCCESS;
+  const bool fromStart = std::is_same<T, float>::value && !abs && !idx;   // max / min_no_idx_f32 read no pSrc[0]
+  if (n == 0 && !fromStart) return refuse(sync, what);
+  return c.run([&](void* const* p, hipStream_t st) {
+    if (!abs && idx) return search_launch<T>(max, (const T*)p[0], n, (T*)p[1], (uint32_t*)p[2], batch, st);
+    return stat_search_launch<T>(max, abs, (const T*)p[0], n, (T*)p[1], (uint32_t*)p[2], batch, st);
+  });
+}
+
+}  // namespace
+
+// ---- inverse, Cholesky, LDLT, triangular solves (f32) ---------------------------------
+// matrix_functions.h:659-777; kernels and the reference bodies they restate: mat_solve.hip.  The shape rules
+// are those the reference states under ARM_MATH_MATRIX_CHECK, applied always, plus a / dst agreement in the
+// solves.  No overlap rule; a null instance or pData is a status, not a last error.
+namespace {
+using MatF = arm_matrix_instance_f32;
+constexpr unsigned kMatrixCall = kNoOverlapRule | kQuietNull;
+
+bool square(const MatF* m) { return m->numRows == m->numCols; }
+
+// The inverse writes src back: the reference destroys it, and its final words are part of the contract.  Cholesky
+// stages dst in as well: its strict upper triangle, and the columns past a failure, are never written.
+arm_status solve_square(bool inverse, const MatF* src, MatF* dst, bool sync, uint32_t batch, int32_t* d_status,
+                        void* stream, const char* what) {
+  if (!src || !dst) return ARM_MATH_ARGUMENT_ERROR;
+  const int n = src->numRows;
+  const size_t bytes = sizeof(float) * n * n * batch;
+  VecCall c{what, sync, stream, kMatrixCall, 2,
+            {{src->pData, bytes, inverse ? kIn | kOut : kIn}, {dst->pData, bytes, inverse ? kOut : kIn | kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (!square(src) || !square(dst) || src->numRows != dst->numRows) return ARM_MATH_SIZE_MISMATCH;
+  if (batch == 0 || n == 0) return ARM_MATH_SUCCESS;
+  return c.run_with_status(d_status, [&](void* const* p, int32_t* ds, hipStream_t st) {
+    return inverse ? mat_inverse_f32_launch(n, (float*)p[0], (float*)p[1], batch, ds, st)
+                   : mat_cholesky_f32_launch(n, (const float*)p[0], (float*)p[1], batch, ds, st);
+  });
+}
+
+arm_status solve_ldlt(const MatF* src, MatF* pl, MatF* pd, uint16_t* pp, bool sync, uint32_t batch, void* stream,
+                      const char* what) {
+  if (!src || !pl || !pd) return ARM_MATH_ARGUMENT_ERROR;
+  const int n = src->numRows;
+  const size_t bytes = sizeof(float) * n * n * batch;
+  VecCall c{what, sync, stream, kMatrixCall, 4,
+            {{src->pData, bytes, kIn}, {pl->pData, bytes, kOut}, {pd->pData, bytes, kOut},
+             {pp, sizeof(uint16_t) * n * batch, kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (!square(src) || !square(pl) || !square(pd) || pl->numRows != pd->numRows || src->numRows != pl->numRows)
+    return ARM_MATH_SIZE_MISMATCH;
+  if (batch == 0 || n == 0) return ARM_MATH_SUCCESS;
+  // the function cannot fail: the drop-in's status word is cleared, the batched form has none
+  return c.run_with_status(nullptr, [&](void* const* p, int32_t* ds, hipStream_t st) {
+    hipError_t e = ds ? hipMemsetAsync(ds, 0, sizeof(int32_t), st) : hipSuccess;
+    if (e == hipSuccess)
+      e = mat_ldlt_f32_launch(n, (const float*)p[0], (float*)p[1], (float*)p[2], (uint16_t*)p[3], batch, st);
+    return e;
+  });
+}
+
+arm_status solve_tri(bool lower, const MatF* t, const MatF* a, MatF* dst, bool sync, uint32_t batch,
+                     int32_t* d_status, void* stream, const char* what) {
+  if (!t || !a || !dst) return ARM_MATH_ARGUMENT_ERROR;
+  const int n = t->numRows, cols = a->numCols;
+  const size_t xb = sizeof(float) * n * cols * batch;
+  // dst is staged in as well: a failing solve leaves most of its words alone
+  VecCall c{what, sync, stream, kMatrixCall, 3,
+            {{t->pData, sizeof(float) * n * n * batch, kIn}, {a->pData, xb, kIn}, {dst->pData, xb, kIn | kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (!square(t) || t->numRows != a->numRows || a->numRows != dst->numRows || a->numCols != dst->numCols)
+    return ARM_MATH_SIZE_MISMATCH;
+  if (batch == 0 || n == 0 || cols == 0) return ARM_MATH_SUCCESS;
+  return c.run_with_status(d_status, [&](void* const* p, int32_t* ds, hipStream_t st) {
+    return mat_solve_tri_f32_launch(lower, n, cols, (const float*)p[0], (const float*)p[1], (float*)p[2], batch, ds, st);
+  });
+}
+}  // namespace
+
+extern "C" {
+arm_status arm_mat_inverse_f32(const arm_matrix_instance_f32* pSrc, arm_matrix_instance_f32* pDst) {
+  return solve_square(true, pSrc, pDst, true, 1, nullptr, nullptr, "arm_mat_inverse_f32");
+}
+arm_status arm_mat_cholesky_f32(const arm_matrix_instance_f32* pSrc, arm_matrix_instance_f32* pDst) {
+  return solve_square(false, pSrc, pDst, true, 1, nullptr, nullptr, "arm_mat_cholesky_f32");
+}
+arm_status arm_mat_ldlt_f32(const arm_matrix_instance_f32* pSrc, arm_matrix_instance_f32* pl,
+                            arm_matrix_instance_f32* pd, uint16_t* pp) {
+  return solve_ldlt(pSrc, pl, pd, pp, true, 1, nullptr, "arm_mat_ldlt_f32");
+}
+arm_status arm_mat_solve_lower_triangular_f32(const arm_matrix_instance_f32* lt, const arm_matrix_instance_f32* a,
+                                              arm_matrix_instance_f32* dst) {
+  return solve_tri(true, lt, a, dst, true, 1, nullptr, nullptr, "arm_mat_solve_lower_triangular_f32");
+}
+arm_status arm_mat_solve_upper_triangular_f32(const arm_matrix_instance_f32* ut, const arm_matrix_instance_f32* a,
+                                              arm_matrix_instance_f32* dst) {
+  return solve_tri(false, ut, a, dst, true, 1, nullptr, nullptr, "arm_mat_solve_upper_triangular_f32");
+}
+
+arm_status arm_mat_inverse_f32_batch(const arm_matrix_instance_f32* pSrc, arm_matrix_instance_f32* pDst,
+                                     uint32_t batch, int32_t* d_status, void* stream) {
+  return solve_square(true, pSrc, pDst, false, batch, d_status, stream, "arm_mat_inverse_f32_batch");
+}
+arm_status arm_mat_cholesky_f32_batch(const arm_matrix_instance_f32* pSrc, arm_matrix_instance_f32* pDst,
+                                      uint32_t batch, int32_t* d_status, void* stream) {
+  return solve_square(false, pSrc, pDst, false, batch, d_status, stream, "arm_mat_cholesky_f32_batch");
+}
+arm_status arm_mat_ldlt_f32_batch(const arm_matrix_instance_f32* pSrc, arm_matrix_instance_f32* pl,
+                                  arm_matrix_instance_f32* pd, uint16_t* d_pp, uint32_t batch, void* stream) {
+  return solve_ldlt(pSrc, pl, pd, d_pp, false, batch, stream, "arm_mat_ldlt_f32_batch");
+}
+arm_status arm_mat_solve_lower_triangular_f32_batch(const arm_matrix_instance_f32* lt,
+                                                    const arm_matrix_instance_f32* a, arm_matrix_instance_f32* dst,
+                                                    uint32_t batch, int32_t* d_status, void* stream) {
+  return solve_tri(true, lt, a, dst, false, batch, d_status, stream, "arm_mat_solve_lower_triangular_f32_batch");
+}
+arm_status arm_mat_solve_upper_triangular_f32_batch(const arm_matrix_instance_f32* ut,
+                                                    const arm_matrix_instance_f32* a, arm_matrix_instance_f32* dst,
+                                                    uint32_t batch, int32_t* d_status, void* stream) {
+  return solve_tri(false, ut, a, dst, false, batch, d_status, stream, "arm_mat_solve_upper_triangular_f32_batch");
+}
+}  // extern "C"
+
+// ---- add / sub / scale, transposes, matrix x vector (mat_basic.hip) ------------------------------
+// matrix_functions.h groups MatrixAdd, MatrixSub, MatrixScale, MatrixTrans, MatrixComplexTrans and the
+// arm_mat_vec_mult_* of MatrixMult.  The shape rules are the reference's ARM_MATH_MATRIX_CHECK ones, applied
+// always.  No overlap rule (add / sub / scale work in place; a transpose onto its source is the caller's error).
+namespace {
+template <typename M>
+bool same_shape(const M* a, const M* b) { return a->numRows == b->numRows && a->numCols == b->numCols; }
+
+// op: kMatAdd / kMatSub (b != null) or kMatScale (b == null, scale and shift used).
+template <typename T, typename M>
+arm_status mat_ew(int op, const M* a, const M* b, M* d, T scale, int32_t shift, bool sync, uint32_t batch,
+                  void* stream, const char* what) {
+  const bool two = op != kMatScale;
+  if (!a || (two && !b) || !d) return ARM_MATH_ARGUMENT_ERROR;
+  const size_t n = (size_t)a->numRows * a->numCols, bytes = sizeof(T) * n * batch;
+  const VecCall c{what, sync, stream, kMatrixCall, two ? 3 : 2,
+                  {{a->pData, bytes, kIn}, {d->pData, bytes, kOut}, {two ? b->pData : nullptr, bytes, kIn}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (!same_shape(a, d) || (two && !same_shape(a, b))) return ARM_MATH_SIZE_MISMATCH;
+  if (op == kMatScale && !std::is_same<T, float>::value) {
+    // past these the reference shifts by a negative or too large count
+    const int lo = sizeof(T) == 4 ? -1 : -16, hi = sizeof(T) == 4 ? 30 : 15;
+    if (shift < lo || shift > hi) return ARM_MATH_ARGUMENT_ERROR;
+  }
+  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
+  return c.run([&](void* const* p, hipStream_t st) {
+    return mat_ew_launch<T>(op, (const T*)p[0], (const T*)p[2], (T*)p[1], n * batch, scale, shift, st);
+  });
+}
+
+// words: T words per element (2: interleaved complex).
+template <typename T, typename M>
+arm_status mat_trans(const M* s, M* d, int words, bool sync, uint32_t batch, void* stream, const char* what) {
+  if (!s || !d) return ARM_MATH_ARGUMENT_ERROR;
+  const size_t n = (size_t)s->numRows * s->numCols;
+  const int eb = (int)sizeof(T) * words;
+  const VecCall c{what, sync, stream, kMatrixCall, 2, {{s->pData, eb * n * batch, kIn}, {d->pData, eb * n * batch, kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (s->numRows != d->numCols || s->numCols != d->numRows) return ARM_MATH_SIZE_MISMATCH;
+  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
+  return c.run([&](void* const* p, hipStream_t st) {
+    return mat_trans_launch(eb, s->numRows, s->numCols, p[0], p[1], batch, st);
+  });
+}
+
+// matStride (elements; the drop-in passes 0): 0 shares one matrix, otherwise >= numRows * numCols.  The drop-in is
+// void and reports a null operand through the last error.  numCols == 0: every sum is empty and the outputs are
+// zero, as in the reference; no operand word is read.
+template <typename T, typename M>
+arm_status mat_vec_mult(const M* m, size_t matStride, const T* vec, T* dst, bool sync, uint32_t batch, void* stream,
+                        const char* what) {
+  if (!m) return refuse(sync, what);
+  const size_t rows = m->numRows, cols = m->numCols;
+  const VecCall c{what, sync, stream, kNoOverlapRule, 3,
+                  {{m->pData, sizeof(T) * (matStride * (batch - 1) + rows * cols), kIn},
+                   {vec, sizeof(T) * cols * batch, kIn}, {dst, sizeof(T) * rows * batch, kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (matStride != 0 && matStride < rows * cols) return ARM_MATH_ARGUMENT_ERROR;
+  if (batch == 0 || rows == 0) return ARM_MATH_SUCCESS;
+  return c.run([&](void* const* p, hipStream_t st) {
+    return mat_vec_mult_launch<T>((int)rows, (int)cols, (const T*)p[0], matStride, (const T*)p[1], (T*)p[2], batch, st);
+  });
+}
+}  // namespace
+
+extern "C" {
+#define MI355X_MAT_EW(SUF, INST, T, CT)                                                                          \
+  arm_status arm_mat_add_##SUF(const INST* pSrcA, const INST* pSrcB, INST* pDst) {                               \
+    return mat_ew<CT>(kMatAdd, pSrcA, pSrcB, pDst, (CT)0, 0, true, 1, nullptr, "arm_mat_add_" #SUF);             \
+  }                                                                                                              \
+  arm_status arm_mat_sub_##SUF(const INST* pSrcA, const INST* pSrcB, INST* pDst) {                               \
+    return mat_ew<CT>(kMatSub, pSrcA, pSrcB, pDst, (CT)0, 0, true, 1, nullptr, "arm_mat_sub_" #SUF);             \
+  }                                                                                                              \
+  arm_status arm_mat_add_##SUF##_batch(const INST* pSrcA, const INST* pSrcB, INST* pDst, uint32_t batch,         \
+                                       void* stream) {                                                           \
+    return mat_ew<CT>(kMatAdd, pSrcA, pSrcB, pDst, (CT)0, 0, false, batch, stream, "arm_mat_add_" #SUF "_batch"); \
+  }                                                                                                              \
+  arm_status arm_mat_sub_##SUF##_batch(const INST* pSrcA, const INST* pSrcB, INST* pDst, uint32_t batch,         \
+                                       void* stream) {                                                           \
+    return mat_ew<CT>(kMatSub, pSrcA, pSrcB, pDst, (CT)0, 0, false, batch, stream, "arm_mat_sub_" #SUF "_batch"); \
+  }
+MI355X_MAT_EW(f32, arm_matrix_instance_f32, float32_t, float)
+MI355X_MAT_EW(q31, arm_matrix_instance_q31, q31_t, int32_t)
+MI355X_MAT_EW(q15, arm_matrix_instance_q15, q15_t, int16_t)
+#undef MI355X_MAT_EW
+
+arm_status arm_mat_scale_f32(const arm_matrix_instance_f32* pSrc, float32_t scale, arm_matrix_instance_f32* pDst) {
+  return mat_ew<float>(kMatScale, pSrc, (const arm_matrix_instance_f32*)nullptr, pDst, scale, 0, true, 1, nullptr,
+                       "arm_mat_scale_f32");
+}
+arm_status arm_mat_scale_f32_batch(const arm_matrix_instance_f32* pSrc, float32_t scale,
+                                   arm_matrix_instance_f32* pDst, uint32_t batch, void* stream) {
+  return mat_ew<float>(kMatScale, pSrc, (const arm_matrix_instance_f32*)nullptr, pDst, scale, 0, false, batch, stream,
+                       "arm_mat_scale_f32_batch");
+}
+#define MI355X_MAT_SCALE(SUF, INST, T, CT)                                                                       \
+  arm_status arm_mat_scale_##SUF(const INST* pSrc, T scaleFract, int32_t shift, INST* pDst) {                    \
+    return mat_ew<CT>(kMatScale, pSrc, (const INST*)nullptr, pDst, scaleFract, shift, true, 1, nullptr,          \
+                      "arm_mat_scale_" #SUF);                                                                    \
+  }                                                                                                              \
+  arm_status arm_mat_scale_##SUF##_batch(const INST* pSrc, T scaleFract, int32_t shift, INST* pDst,              \
+                                         uint32_t batch, void* stream) {                                         \
+    return mat_ew<CT>(kMatScale, pSrc, (const INST*)nullptr, pDst, scaleFract, shift, false, batch, stream,      \
+                      "arm_mat_scale_" #SUF "_batch");                                                           \
+  }
+MI355X_MAT_SCALE(q31, arm_matrix_instance_q31, q31_t, int32_t)
+MI355X_MAT_SCALE(q15, arm_matrix_instance_q15, q15_t, int16_t)
+#undef MI355X_MAT_SCALE
+
+// NAME: trans / cmplx_trans; WORDS: CT words per element
+#define MI355X_MAT_TRANS(NAME, SUF, INST, CT, WORDS)                                                             \
+  arm_status arm_mat_##NAME##_##SUF(const INST* pSrc, INST* pDst) {                                              \
+    return mat_trans<CT>(pSrc, pDst, WORDS, true, 1, nullptr, "arm_mat_" #NAME "_" #SUF);                        \
+  }                                                                                                              \
+  arm_status arm_mat_##NAME##_##SUF##_batch(const INST* pSrc, INST* pDst, uint32_t batch, void* stream) {        \
+    return mat_trans<CT>(pSrc, pDst, WORDS, false, batch, stream, "arm_mat_" #NAME "_" #SUF "_batch");           \
+  }
+MI355X_MAT_TRANS(trans, f32, arm_matrix_instance_f32, float, 1)
+MI355X_MAT_TRANS(trans, q31, arm_matrix_instance_q31, int32_t, 1)
+MI355X_MAT_TRANS(trans, q15, arm_matrix_instance_q15, int16_t, 1)
+MI355X_MAT_TRANS(trans, q7, arm_matrix_instance_q7, int8_t, 1)
+MI355X_MAT_TRANS(cmplx_trans, f32, arm_matrix_instance_f32, float, 2)
+MI355X_MAT_TRANS(cmplx_trans, q31, arm_matrix_instance_q31, int32_t, 2)
+MI355X_MAT_TRANS(cmplx_trans, q15, arm_matrix_instance_q15, int16_t, 2)
+#undef MI355X_MAT_TRANS
+
+#define MI355X_MAT_VEC(SUF, INST, T, CT)                                                                         \
+  void arm_mat_vec_mult_##SUF(const INST* pSrcMat, const T* pVec, T* pDst) {                                     \
+    mat_vec_mult<CT>(pSrcMat, 0, (const CT*)pVec, (CT*)pDst, true, 1, nullptr, "arm_mat_vec_mult_" #SUF);        \
+  }                                                                                                              \
+  arm_status arm_mat_vec_mult_##SUF##_batch(const INST* pSrcMat, uint32_t matStride, const T* d_vec, T* d_dst,   \
+                                            uint32_t batch, void* stream) {                                      \
+    return mat_vec_mult<CT>(pSrcMat, matStride, (const CT*)d_vec, (CT*)d_dst, false, batch, stream,              \
+                            "arm_mat_vec_mult_" #SUF "_batch");                                                  \
+  }
+MI355X_MAT_VEC(f32, arm_matrix_instance_f32, float32_t, float)
+MI355X_MAT_VEC(q31, arm_matrix_instance_q31, q31_t, int32_t)
+MI355X_MAT_VEC(q15, arm_matrix_instance_q15, q15_t, int16_t)
+MI355X_MAT_VEC(q7, arm_matrix_instance_q7, q7_t, int8_t)
+#undef MI355X_MAT_VEC
+}  // extern "C"
+
+// ---- complex math, max / min (cmplx_math.hip) ---------------------------------------------------
+// complex_math_functions.h and arm_max_* / arm_min_* of statistics_functions.h.  dst may be a source exactly where
+// the kernel allows it (conj: the source; mult_cmplx: either source; mult_real: the complex source).
+namespace {
+template <typename T>
+arm_status cmplx_ew(int op, const T* a, const T* b, T* d, uint32_t n, bool sync, uint32_t batch, void* stream,
+                    const char* what) {
+  const int wb = op == kCmMultCmplx ? 2 : op == kCmMultReal ? 1 : 0;
+  const int wd = op == kCmMag || op == kCmMagSquared || op == kCmMagFast ? 1 : 2;
+  const size_t count = (size_t)n * batch;
+  const VecCall c{what, sync, stream, 0, wb ? 3 : 2,
+                  {{a, sizeof(T) * 2 * count, wd == 2 ? kIn | kExactOk : kIn}, {d, sizeof(T) * wd * count, kOut},
+                   {b, sizeof(T) * wb * count, op == kCmMultCmplx ? kIn | kExactOk : kIn}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
+  const bool lut = op == kCmMag && !std::is_same<T, float>::value;
+  return c.run([&](void* const* p, hipStream_t st) -> hipError_t {
+    const int32_t* dl = lut ? (const int32_t*)device_table(sqrt_initial_lut_q31, sizeof(int32_t) * 32) : nullptr;
+    if (lut && !dl) return hipErrorOutOfMemory;
+    return cmplx_ew_launch<T>(op, (const T*)p[0], (const T*)p[2], (T*)p[1], count, dl, st);
+  });
+}
+
+template <typename T, typename R>
+arm_status cmplx_dot(const T* a, const T* b, uint32_t bStride, uint32_t n, R* re, R* im, bool sync, uint32_t batch,
+                     void* stream, const char* what) {
+  return strided_reduce(2, a, b, bStride, n, re, im, sync, batch, stream, what,
+                        [&](const T* da, const T* db, R* dre, R* dim, hipStream_t st) {
+                          return cmplx_dot_launch<T, R>(da, db, bStride, n, dre, dim, batch, st);
+                        });
+}
+}  // namespace
+
+extern "C" {
+// one source: mag, mag_squared, conj
+#define MI355X_CMPLX_1(NAME, OP, SUF, T, CT)                                                                     \
+  void arm_cmplx_##NAME##_##SUF(const T* pSrc, T* pDst, uint32_t numSamples) {                                   \
+    cmplx_ew<CT>(OP, (const CT*)pSrc, (const CT*)nullptr, (CT*)pDst, numSamples, true, 1, nullptr,               \
+                 "arm_cmplx_" #NAME "_" #SUF);                                                                   \
+  }                                                                                                              \
+  arm_status arm_cmplx_##NAME##_##SUF##_batch(const T* d_src, T* d_dst, uint32_t numSamples, uint32_t batch,     \
+                                              void* stream) {                                                    \
+    return cmplx_ew<CT>(OP, (const CT*)d_src, (const CT*)nullptr, (CT*)d_dst, numSamples, false, batch, stream,  \
+                        "arm_cmplx_" #NAME "_" #SUF "_batch");                                                   \
+  }
+// two sources: mult_cmplx (pSrcB complex), mult_real (pSrcB real)
+#define MI355X_CMPLX_2(NAME, OP, SUF, T, CT)                                                                     \
+  void arm_cmplx_##NAME##_##SUF(const T* pSrcA, const T* pSrcB, T* pDst, uint32_t numSamples) {                  \
+    cmplx_ew<CT>(OP, (const CT*)pSrcA, (const CT*)pSrcB, (CT*)pDst, numSamples, true, 1, nullptr,                \
+                 "arm_cmplx_" #NAME "_" #SUF);                                                                   \
+  }                                                                                                              \
+  arm_status arm_cmplx_##NAME##_##SUF##_batch(const T* d_srcA, const T* d_srcB, T* d_dst, uint32_t numSamples,   \
+                                              uint32_t batch, void* stream) {                                    \
+    return cmplx_ew<CT>(OP, (const CT*)d_srcA, (const CT*)d_srcB, (CT*)d_dst, numSamples, false, batch, stream,  \
+                        "arm_cmplx_" #NAME "_" #SUF "_batch");                                                   \
+  }
+#define MI355X_CMPLX_DOT(SUF, T, CT, R, CR)                                                                      \
+  void arm_cmplx_dot_prod_##SUF(const T* pSrcA, const T* pSrcB, uint32_t numSamples, R* realResult,              \
+                                R* imagResult) {                                                                 \
+    cmplx_dot<CT, CR>((const CT*)pSrcA, (const CT*)pSrcB, numSamples, numSamples, (CR*)realResult,               \
+                      (CR*)imagResult, true, 1, nullptr, "arm_cmplx_dot_prod_" #SUF);                            \
+  }                                                                                                              \
+  arm_status arm_cmplx_dot_prod_##SUF##_batch(const T* d_a, const T* d_b, uint32_t bStride, uint32_t numSamples, \
+                                              R* d_re, R* d_im, uint32_t batch, void* stream) {                  \
+    return cmplx_dot<CT, CR>((const CT*)d_a, (const CT*)d_b, bStride, numSamples, (CR*)d_re, (CR*)d_im, false,   \
+                             batch, stream, "arm_cmplx_dot_prod_" #SUF "_batch");                                \
+  }
+#define MI355X_CMPLX_TYPE(SUF, T, CT, R, CR)                   \
+  MI355X_CMPLX_1(mag, kCmMag, SUF, T, CT)                      \
+  MI355X_CMPLX_1(mag_squared, kCmMagSquared, SUF, T, CT)       \
+  MI355X_CMPLX_1(conj, kCmConj, SUF, T, CT)                    \
+  MI355X_CMPLX_2(mult_cmplx, kCmMultCmplx, SUF, T, CT)         \
+  MI355X_CMPLX_2(mult_real, kCmMultReal, SUF, T, CT)           \
+  MI355X_CMPLX_DOT(SUF, T, CT, R, CR)
+MI355X_CMPLX_TYPE(f32, float32_t, float, float32_t, float)
+MI355X_CMPLX_TYPE(q31, q31_t, int32_t, q63_t, int64_t)
+MI355X_CMPLX_TYPE(q15, q15_t, int16_t, q31_t, int32_t)
+#undef MI355X_CMPLX_TYPE
+#undef MI355X_CMPLX_DOT
+#undef MI355X_CMPLX_2
+#undef MI355X_CMPLX_1
+
+// NAME: max, min, absmax, absmin, with the index
+#define MI355X_SEARCH(NAME, MAX, ABS, SUF, T, CT)                                                                \
+  void arm_##NAME##_##SUF(const T* pSrc, uint32_t blockSize, T* pResult, uint32_t* pIndex) {                     \
+    search<CT>(MAX, ABS, true, (const CT*)pSrc, blockSize, (CT*)pResult, pIndex, true, 1, nullptr,               \
+               "arm_" #NAME "_" #SUF);                                                                           \
+  }                                                                                                              \
+  arm_status arm_##NAME##_##SUF##_batch(const T* d_src, uint32_t blockSize, T* d_result, uint32_t* d_index,      \
+                                        uint32_t batch, void* stream) {                                          \
+    return search<CT>(MAX, ABS, true, (const CT*)d_src, blockSize, (CT*)d_result, d_index, false, batch, stream, \
+                      "arm_" #NAME "_" #SUF "_batch");                                                           \
+  }
+// the same four without it
+#define MI355X_SEARCH_NO_IDX(NAME, MAX, ABS, SUF, T, CT)                                                         \
+  void arm_##NAME##_no_idx_##SUF(const T* pSrc, uint32_t blockSize, T* pResult) {                                \
+    search<CT>(MAX, ABS, false, (const CT*)pSrc, blockSize, (CT*)pResult, nullptr, true, 1, nullptr,             \
+               "arm_" #NAME "_no_idx_" #SUF);                                                                    \
+  }                                                                                                              \
+  arm_status arm_##NAME##_no_idx_##SUF##_batch(const T* d_src, uint32_t blockSize, T* d_result, uint32_t batch,  \
+                                               void* stream) {                                                   \
+    return search<CT>(MAX, ABS, false, (const CT*)d_src, blockSize, (CT*)d_result, nullptr, false, batch,        \
+                      stream, "arm_" #NAME "_no_idx_" #SUF "_batch");                                            \
+  }
+#define MI355X_SEARCH_TYPE(SUF, T, CT)                    \
+  MI355X_SEARCH(max, true, false, SUF, T, CT)             \
+  MI355X_SEARCH(min, false, false, SUF, T, CT)            \
+  MI355X_SEARCH(absmax, true, true, SUF, T, CT)           \
+  MI355X_SEARCH(absmin, false, true, SUF, T, CT)          \
+  MI355X_SEARCH_NO_IDX(max, true, false, SUF, T, CT)      \
+  MI355X_SEARCH_NO_IDX(min, false, false, SUF, T, CT)     \
+  MI355X_SEARCH_NO_IDX(absmax, true, true, SUF, T, CT)    \
+  MI355X_SEARCH_NO_IDX(absmin, false, true, SUF, T, CT)
+MI355X_SEARCH_TYPE(f32, float32_t, float)
+MI355X_SEARCH_TYPE(q31, q31_t, int32_t)
+MI355X_SEARCH_TYPE(q15, q15_t, int16_t)
+MI355X_SEARCH_TYPE(q7, q7_t, int8_t)
+#undef MI355X_SEARCH_TYPE
+#undef MI355X_SEARCH_NO_IDX
+#undef MI355X_SEARCH
+
+// arm_cmplx_mag_fast_q15: one more operation of the element-wise kernel
+void arm_cmplx_mag_fast_q15(const q15_t* pSrc, q15_t* pDst, uint32_t numSamples) {
+  cmplx_ew<int16_t>(kCmMagFast, pSrc, (const int16_t*)nullptr, pDst, numSamples, true, 1, nullptr,
+                    "arm_cmplx_mag_fast_q15");
+}
+arm_status arm_cmplx_mag_fast_q15_batch(const q15_t* d_src, q15_t* d_dst, uint32_t numSamples, uint32_t batch,
+                                        void* stream) {
+  return cmplx_ew<int16_t>(kCmMagFast, d_src, (const int16_t*)nullptr, d_dst, numSamples, false, batch, stream,
+                           "arm_cmplx_mag_fast_q15_batch");
+}
+// the scalar of fast_math_functions.h, computed on the host
+arm_status arm_sqrt_q15(q15_t in, q15_t* pOut) {
+  if (!pOut) return ARM_MATH_ARGUMENT_ERROR;
+  *pOut = sqrt_q15_host(in);
+  return in >= 0 ? ARM_MATH_SUCCESS : ARM_MATH_ARGUMENT_ERROR;
+}
+}  // extern "C"
+
+// ---- statistics (statistics.hip) ------------------------------------------------------------------
+// The sums and level measures of statistics_functions.h (op: kStMean ... kStAccumulate; b: the second source of
+// kStMse); the abs / no-index searches are stamped out with max / min above.  blockSize == 0: what the reference's
+// empty sums give is stored (power, accumulate: 0; mean_f32, mse_f32: 0 / 0; rms_f32: +0.0; var, std: 0; max /
+// min_no_idx_f32: their start value); where it would divide an integer by zero or read pSrc[0] the call is refused.
+namespace {
+template <typename T, typename R>
+arm_status st_sum(int op, const T* a, const T* b, uint32_t n, R* result, bool sync, uint32_t batch, void* stream,
+                  const char* what) {
+  constexpr bool f32 = std::is_same<T, float>::value;
+  const bool two = op == kStMse;
+  const size_t sb = sizeof(T) * n * batch;
+  const VecCall c{what, sync, stream, 0, two ? 3 : 2, {{a, sb, kIn}, {result, sizeof(R) * batch, kOut}, {b, sb, kIn}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (batch == 0) return ARM_MATH_SUCCESS;
+  if (n == 0 && !f32 && (op == kStMean || op == kStRms || op == kStMse)) return refuse(sync, what);
+  const bool lut = std::is_same<T, int32_t>::value && (op == kStRms || op == kStStd);
+  return c.run([&](void* const* p, hipStream_t st) -> hipError_t {
+    const int32_t* dl = lut ? (const int32_t*)device_table(sqrt_initial_lut_q31, sizeof(int32_t) * 32) : nullptr;
+    if (lut && !dl) return hipErrorOutOfMemory;
+    return stat_sum_launch<T, R>(op, (const T*)p[0], (const T*)p[2], n, (R*)p[1], batch, dl, st);
+  });
+}
+}  // namespace
+
+extern "C" {
+#define MI355X_STAT_1(NAME, OP, SUF, T, CT, R, CR)                                                               \
+  void arm_##NAME##_##SUF(const T* pSrc, uint32_t blockSize, R* pResult) {                                       \
+    st_sum<CT, CR>(OP, (const CT*)pSrc, (const CT*)nullptr, blockSize, (CR*)pResult, true, 1, nullptr,           \
+                   "arm_" #NAME "_" #SUF);                                                                       \
+  }                                                                                                              \
+  arm_status arm_##NAME##_##SUF##_batch(const T* d_src, uint32_t blockSize, R* d_result, uint32_t batch,         \
+                                        void* stream) {                                                          \
+    return st_sum<CT, CR>(OP, (const CT*)d_src, (const CT*)nullptr, blockSize, (CR*)d_result, false, batch,      \
+                          stream, "arm_" #NAME "_" #SUF "_batch");                                               \
+  }
+#define MI355X_STAT_MSE(SUF, T, CT)                                                                              \
+  void arm_mse_##SUF(const T* pSrcA, const T* pSrcB, uint32_t blockSize, T* pResult) {                           \
+    st_sum<CT, CT>(kStMse, (const CT*)pSrcA, (const CT*)pSrcB, blockSize, (CT*)pResult, true, 1, nullptr,        \
+                   "arm_mse_" #SUF);                                                                             \
+  }                                                                                                              \
+  arm_status arm_mse_##SUF##_batch(const T* d_a, const T* d_b, uint32_t blockSize, T* d_result, uint32_t batch,  \
+                                   void* stream) {                                                               \
+    return st_sum<CT, CT>(kStMse, (const CT*)d_a, (const CT*)d_b, blockSize, (CT*)d_result, false, batch,        \
+                          stream, "arm_mse_" #SUF "_batch");                                                     \
+  }
+#define MI355X_STAT_LEVELS(SUF, T, CT)               \
+  MI355X_STAT_1(rms, kStRms, SUF, T, CT, T, CT)      \
+  MI355X_STAT_1(var, kStVar, SUF, T, CT, T, CT)      \
+  MI355X_STAT_1(std, kStStd, SUF, T, CT, T, CT)
+#define MI355X_STAT_TYPE(SUF, T, CT, PR, CPR)        \
+  MI355X_STAT_1(mean, kStMean, SUF, T, CT, T, CT)    \
+  MI355X_STAT_1(power, kStPower, SUF, T, CT, PR, CPR) \
+  MI355X_STAT_MSE(SUF, T, CT)
+MI355X_STAT_TYPE(f32, float32_t, float, float32_t, float)
+MI355X_STAT_TYPE(q31, q31_t, int32_t, q63_t, int64_t)
+MI355X_STAT_TYPE(q15, q15_t, int16_t, q63_t, int64_t)
+MI355X_STAT_TYPE(q7, q7_t, int8_t, q31_t, int32_t)
+MI355X_STAT_LEVELS(f32, float32_t, float)
+MI355X_STAT_LEVELS(q31, q31_t, int32_t)
+MI355X_STAT_LEVELS(q15, q15_t, int16_t)
+MI355X_STAT_1(accumulate, kStAccumulate, f32, float32_t, float, float32_t, float)
+#undef MI355X_STAT_TYPE
+#undef MI355X_STAT_LEVELS
+#undef MI355X_STAT_MSE
+#undef MI355X_STAT_1
+}  // extern "C"
+
+// ---- basic math (basic_math.hip; the dot products: statistics.hip) ---------------------------------
+// basic_math_functions.h.  dst may be a source exactly.  One scalar (offset, scale and shift, low and high) serves
+// the whole call.  shift: the counts at which the reference's C is defined (a count below 32 either way on its
+// promoted int operands): arm_shift_* -31 .. 31; arm_scale_q31 -32 .. 30 (kShift = shift + 1), _q15 -16 .. 15
+// (kShift = 15 - shift in 0 .. 31), _q7 -24 .. 7 (kShift = 7 - shift); outside the call is refused.
+namespace {
+bool bm_two(int op) { return op == kBmAdd || op == kBmSub || op == kBmMult || op == kBmAnd || op == kBmOr || op == kBmXor; }
+
+template <typename T>
+arm_status bm_ew(int op, const T* a, const T* b, T* d, uint32_t n, T s0, T s1, int shift, bool sync, uint32_t batch,
+                 void* stream, const char* what) {
+  const bool two = bm_two(op);
+  const size_t count = (size_t)n * batch, bytes = sizeof(T) * count;
+  const VecCall c{what, sync, stream, 0, two ? 3 : 2,
+                  {{a, bytes, kIn | kExactOk}, {d, bytes, kOut}, {b, bytes, kIn | kExactOk}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  int sh = 0;
+  if (op == kBmShift) {
+    if (shift < -31 || shift > 31) return refuse(sync, what);
+    sh = shift;
+  } else if (op == kBmScale && !std::is_same<T, float>::value) {
+    const int lo = sizeof(T) == 4 ? -32 : sizeof(T) == 2 ? -16 : -24, hi = sizeof(T) == 4 ? 30 : sizeof(T) == 2 ? 15 : 7;
+    if (shift < lo || shift > hi) return refuse(sync, what);
+    sh = sizeof(T) == 4 ? shift + 1 : hi - shift;
+  }
+  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
+  return c.run([&](void* const* p, hipStream_t st) {
+    return basic_ew_launch<T>(op, (const T*)p[0], (const T*)p[2], (T*)p[1], count, s0, s1, sh, st);
+  });
+}
+
+template <typename T, typename R>
+arm_status bm_dot(const T* a, const T* b, uint32_t bStride, uint32_t n, R* result, bool sync, uint32_t batch,
+                  void* stream, const char* what) {
+  return strided_reduce(1, a, b, bStride, n, result, (R*)nullptr, sync, batch, stream, what,
+                        [&](const T* da, const T* db, R* dr, R*, hipStream_t st) {
+                          return dot_prod_launch<T, R>(da, db, bStride, n, dr, batch, st);
+                        });
+}
+}  // namespace
+
+extern "C" {
+#define MI355X_BM_2(NAME, OP, SUF, T, CT)                                                                        \
+  void arm_##NAME##_##SUF(const T* pSrcA, const T* pSrcB, T* pDst, uint32_t blockSize) {                         \
+    bm_ew<CT>(OP, (const CT*)pSrcA, (const CT*)pSrcB, (CT*)pDst, blockSize, (CT)0, (CT)0, 0, true, 1, nullptr,   \
+              "arm_" #NAME "_" #SUF);                                                                            \
+  }                                                                                                              \
+  arm_status arm_##NAME##_##SUF##_batch(const T* d_srcA, const T* d_srcB, T* d_dst, uint32_t blockSize,          \
+                                        uint32_t batch, void* stream) {                                          \
+    return bm_ew<CT>(OP, (const CT*)d_srcA, (const CT*)d_srcB, (CT*)d_dst, blockSize, (CT)0, (CT)0, 0, false,    \
+                     batch, stream, "arm_" #NAME "_" #SUF "_batch");                                             \
+  }
+#define MI355X_BM_1(NAME, OP, SUF, T, CT)                                                                        \
+  void arm_##NAME##_##SUF(const T* pSrc, T* pDst, uint32_t blockSize) {                                          \
+    bm_ew<CT>(OP, (const CT*)pSrc, (const CT*)nullptr, (CT*)pDst, blockSize, (CT)0, (CT)0, 0, true, 1, nullptr,  \
+              "arm_" #NAME "_" #SUF);                                                                            \
+  }                                                                                                              \
+  arm_status arm_##NAME##_##SUF##_batch(const T* d_src, T* d_dst, uint32_t blockSize, uint32_t batch,            \
+                                        void* stream) {                                                          \
+    return bm_ew<CT>(OP, (const CT*)d_src, (const CT*)nullptr, (CT*)d_dst, blockSize, (CT)0, (CT)0, 0, false,    \
+                     batch, stream, "arm_" #NAME "_" #SUF "_batch");                                             \
+  }
+#define MI355X_BM_OFFSET(NAME, OP, SUF, T, CT)                                                                   \
+  void arm_##NAME##_##SUF(const T* pSrc, T value, T* pDst, uint32_t blockSize) {                                 \
+    bm_ew<CT>(OP, (const CT*)pSrc, (const CT*)nullptr, (CT*)pDst, blockSize, (CT)value, (CT)0, 0, true, 1,       \
+              nullptr, "arm_" #NAME "_" #SUF);                                                                   \
+  }                                                                                                              \
+  arm_status arm_##NAME##_##SUF##_batch(const T* d_src, T value, T* d_dst, uint32_t blockSize, uint32_t batch,   \
+                                        void* stream) {                                                          \
+    return bm_ew<CT>(OP, (const CT*)d_src, (const CT*)nullptr, (CT*)d_dst, blockSize, (CT)value, (CT)0, 0,       \
+                     false, batch, stream, "arm_" #NAME "_" #SUF "_batch");                                      \
+  }
+#define MI355X_BM_SCALE(SUF, T, CT)                                                                              \
+  void arm_scale_##SUF(const T* pSrc, T scaleFract, int8_t shift, T* pDst, uint32_t blockSize) {                 \
+    bm_ew<CT>(kBmScale, (const CT*)pSrc, (const CT*)nullptr, (CT*)pDst, blockSize, (CT)scaleFract, (CT)0, shift, \
+              true, 1, nullptr, "arm_scale_" #SUF);                                                              \
+  }                                                                                                              \
+  arm_status arm_scale_##SUF##_batch(const T* d_src, T scaleFract, int8_t shift, T* d_dst, uint32_t blockSize,   \
+                                     uint32_t batch, void* stream) {                                             \
+    return bm_ew<CT>(kBmScale, (const CT*)d_src, (const CT*)nullptr, (CT*)d_dst, blockSize, (CT)scaleFract,      \
+                     (CT)0, shift, false, batch, stream, "arm_scale_" #SUF "_batch");                            \
+  }
+#define MI355X_BM_SHIFT(SUF, T, CT)                                                                              \
+  void arm_shift_##SUF(const T* pSrc, int8_t shiftBits, T* pDst, uint32_t blockSize) {                           \
+    bm_ew<CT>(kBmShift, (const CT*)pSrc, (const CT*)nullptr, (CT*)pDst, blockSize, (CT)0, (CT)0, shiftBits,      \
+              true, 1, nullptr, "arm_shift_" #SUF);                                                              \
+  }                                                                                                              \
+  arm_status arm_shift_##SUF##_batch(const T* d_src, int8_t shiftBits, T* d_dst, uint32_t blockSize,             \
+                                     uint32_t batch, void* stream) {                                             \
+    return bm_ew<CT>(kBmShift, (const CT*)d_src, (const CT*)nullptr, (CT*)d_dst, blockSize, (CT)0, (CT)0,        \
+                     shiftBits, false, batch, stream, "arm_shift_" #SUF "_batch");                               \
+  }
+#define MI355X_BM_CLIP(SUF, T, CT)                                                                               \
+  void arm_clip_##SUF(const T* pSrc, T* pDst, T low, T high, uint32_t numSamples) {                              \
+    bm_ew<CT>(kBmClip, (const CT*)pSrc, (const CT*)nullptr, (CT*)pDst, numSamples, (CT)low, (CT)high, 0, true,   \
+              1, nullptr, "arm_clip_" #SUF);                                                                     \
+  }                                                                                                              \
+  arm_status arm_clip_##SUF##_batch(const T* d_src, T* d_dst, T low, T high, uint32_t numSamples,                \
+                                    uint32_t batch, void* stream) {                                              \
+    return bm_ew<CT>(kBmClip, (const CT*)d_src, (const CT*)nullptr, (CT*)d_dst, numSamples, (CT)low, (CT)high,   \
+                     0, false, batch, stream, "arm_clip_" #SUF "_batch");                                        \
+  }
+#define MI355X_BM_DOT(SUF, T, CT, R, CR)                                                                         \
+  void arm_dot_prod_##SUF(const T* pSrcA, const T* pSrcB, uint32_t blockSize, R* result) {                       \
+    bm_dot<CT, CR>((const CT*)pSrcA, (const CT*)pSrcB, blockSize, blockSize, (CR*)result, true, 1, nullptr,      \
+                   "arm_dot_prod_" #SUF);                                                                        \
+  }                                                                                                              \
+  arm_status arm_dot_prod_##SUF##_batch(const T* d_a, const T* d_b, uint32_t bStride, uint32_t blockSize,        \
+                                        R* d_result, uint32_t batch, void* stream) {                             \
+    return bm_dot<CT, CR>((const CT*)d_a, (const CT*)d_b, bStride, blockSize, (CR*)d_result, false, batch,       \
+                          stream, "arm_dot_prod_" #SUF "_batch");                                                \
+  }
+#define MI355X_BM_TYPE(SUF, T, CT, R, CR)          \
+  MI355X_BM_2(add, kBmAdd, SUF, T, CT)             \
+  MI355X_BM_2(sub, kBmSub, SUF, T, CT)             \
+  MI355X_BM_2(mult, kBmMult, SUF, T, CT)           \
+  MI355X_BM_OFFSET(offset, kBmOffset, SUF, T, CT)  \
+  MI355X_BM_CLIP(SUF, T, CT)                       \
+  MI355X_BM_1(abs, kBmAbs, SUF, T, CT)             \
+  MI355X_BM_1(negate, kBmNegate, SUF, T, CT)       \
+  MI355X_BM_DOT(SUF, T, CT, R, CR)
+#define MI355X_BM_BITS(SUF, T)                     \
+  MI355X_BM_2(and, kBmAnd, SUF, T, T)              \
+  MI355X_BM_2(or, kBmOr, SUF, T, T)                \
+  MI355X_BM_2(xor, kBmXor, SUF, T, T)              \
+  MI355X_BM_1(not, kBmNot, SUF, T, T)
+MI355X_BM_TYPE(f32, float32_t, float, float32_t, float)
+MI355X_BM_TYPE(q31, q31_t, int32_t, q63_t, int64_t)
+MI355X_BM_TYPE(q15, q15_t, int16_t, q63_t, int64_t)
+MI355X_BM_TYPE(q7, q7_t, int8_t, q31_t, int32_t)
+MI355X_BM_OFFSET(scale, kBmScale, f32, float32_t, float)
+MI355X_BM_SCALE(q31, q31_t, int32_t)
+MI355X_BM_SCALE(q15, q15_t, int16_t)
+MI355X_BM_SCALE(q7, q7_t, int8_t)
+MI355X_BM_SHIFT(q31, q31_t, int32_t)
+MI355X_BM_SHIFT(q15, q15_t, int16_t)
+MI355X_BM_SHIFT(q7, q7_t, int8_t)
+MI355X_BM_BITS(u32, uint32_t)
+MI355X_BM_BITS(u16, uint16_t)
+MI355X_BM_BITS(u8, uint8_t)
+#undef MI355X_BM_BITS
+#undef MI355X_BM_TYPE
+#undef MI355X_BM_DOT
+#undef MI355X_BM_CLIP
+#undef MI355X_BM_SHIFT
+#undef MI355X_BM_SCALE
+#undef MI355X_BM_OFFSET
+#undef MI355X_BM_1
+#undef MI355X_BM_2
+}  // extern "C"
+
+// ---- support functions (support.hip, sort.hip; the weighted average: statistics.hip) --------------
+// support_functions.h.  dst may be src exactly where both element widths are equal (float_to_q31, q31_to_float,
+// copy) and in the sorts.
+namespace {
+template <typename S, typename D>
+arm_status sp_convert(const S* s, D* d, uint32_t n, bool sync, uint32_t batch, void* stream, const char* what) {
+  const size_t count = (size_t)n * batch;
+  const VecCall c{what, sync, stream, 0, 2,
+                  {{s, sizeof(S) * count, sizeof(S) == sizeof(D) ? kIn | kExactOk : kIn}, {d, sizeof(D) * count, kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
+  return c.run([&](void* const* p, hipStream_t st) {
+    return support_convert_launch<S, D>((const S*)p[0], (D*)p[1], count, st);
+  });
+}
+
+template <typename T>
+arm_status sp_fill(T value, T* d, uint32_t n, bool sync, uint32_t batch, void* stream, const char* what) {
+  const size_t count = (size_t)n * batch;
+  const VecCall c{what, sync, stream, 0, 1, {{d, sizeof(T) * count, kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
+  return c.run([&](void* const* p, hipStream_t st) { return support_fill_launch<T>(value, (T*)p[0], count, st); });
+}
+
+// dir: ARM_SORT_DESCENDING (0) or ARM_SORT_ASCENDING (1), anything else is refused.
+arm_status sp_sort(int dir, const float* src, float* dst, uint32_t n, bool sync, uint32_t batch, void* stream,
+                   const char* what) {
+  const size_t bytes = sizeof(float) * n * batch;
+  const VecCall c{what, sync, stream, 0, 2, {{src, bytes, kIn | kExactOk}, {dst, bytes, kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if ((dir != 0 && dir != 1) || n > 0x80000000u) return refuse(sync, what);
+  if (n == 0 || batch == 0) return ARM_MATH_SUCCESS;
+  return c.run([&](void* const* p, hipStream_t st) {
+    return sort_launch((const uint32_t*)p[0], (uint32_t*)p[1], n, dir == 1, batch, st);
+  });
+}
+
+arm_status sp_wavg(const float* a, const float* w, uint32_t wStride, uint32_t n, float* result, bool sync,
+                   uint32_t batch, void* stream, const char* what) {
+  return strided_reduce(1, a, w, wStride, n, result, (float*)nullptr, sync, batch, stream, what,
+                        [&](const float* da, const float* dw, float* dr, float*, hipStream_t st) {
+                          return weighted_average_launch(da, dw, wStride, n, dr, batch, st);
+                        });
+}
+
+// wStride (words; the drop-in passes nbVectors): 0 shares one weight vector, otherwise >= nbVectors.  vecDim == 0
+// writes nothing; nbVectors == 0 stores 0 / 0.
+arm_status sp_barycenter(const float* in, const float* w, uint32_t wStride, float* out, uint32_t nv, uint32_t dim,
+                         bool sync, uint32_t batch, void* stream, const char* what) {
+  const VecCall c{what, sync, stream, 0, 3,
+                  {{in, sizeof(float) * nv * dim * batch, kIn},
+                   {w, sizeof(float) * ((size_t)wStride * (batch - 1) + nv), kIn},
+                   {out, sizeof(float) * dim * batch, kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (wStride != 0 && wStride < nv) return refuse(sync, what);
+  if (batch == 0 || dim == 0) return ARM_MATH_SUCCESS;
+  return c.run([&](void* const* p, hipStream_t st) {
+    return barycenter_launch((const float*)p[0], (const float*)p[1], wStride, (float*)p[2], nv, dim, batch, st);
+  });
+}
+}  // namespace
+
+extern "C" {
+#define MI355X_SP_TO(SN, ST, SCT, DN, DT, DCT)                                                                   \
+  void arm_##SN##_to_##DN(const ST* pSrc, DT* pDst, uint32_t blockSize) {                                        \
+    sp_convert<SCT, DCT>((const SCT*)pSrc, (DCT*)pDst, blockSize, true, 1, nullptr, "arm_" #SN "_to_" #DN);      \
+  }                                                                                                              \
+  arm_status arm_##SN##_to_##DN##_batch(const ST* d_src, DT* d_dst, uint32_t blockSize, uint32_t batch,          \
+                                        void* stream) {                                                          \
+    return sp_convert<SCT, DCT>((const SCT*)d_src, (DCT*)d_dst, blockSize, false, batch, stream,                 \
+                                "arm_" #SN "_to_" #DN "_batch");                                                 \
+  }
+#define MI355X_SP_COPY(SUF, T, CT)                                                                               \
+  void arm_copy_##SUF(const T* pSrc, T* pDst, uint32_t blockSize) {                                              \
+    sp_convert<CT, CT>((const CT*)pSrc, (CT*)pDst, blockSize, true, 1, nullptr, "arm_copy_" #SUF);               \
+  }                                                                                                              \
+  arm_status arm_copy_##SUF##_batch(const T* d_src, T* d_dst, uint32_t blockSize, uint32_t batch, void* stream) { \
+    return sp_convert<CT, CT>((const CT*)d_src, (CT*)d_dst, blockSize, false, batch, stream,                     \
+                              "arm_copy_" #SUF "_batch");                                                        \
+  }                                                                                                              \
+  void arm_fill_##SUF(T value, T* pDst, uint32_t blockSize) {                                                    \
+    sp_fill<CT>((CT)value, (CT*)pDst, blockSize, true, 1, nullptr, "arm_fill_" #SUF);                            \
+  }                                                                                                              \
+  arm_status arm_fill_##SUF##_batch(T value, T* d_dst, uint32_t blockSize, uint32_t batch, void* stream) {       \
+    return sp_fill<CT>((CT)value, (CT*)d_dst, blockSize, false, batch, stream, "arm_fill_" #SUF "_batch");       \
+  }
+MI355X_SP_TO(float, float32_t, float, q31, q31_t, int32_t)
+MI355X_SP_TO(float, float32_t, float, q15, q15_t, int16_t)
+MI355X_SP_TO(float, float32_t, float, q7, q7_t, int8_t)
+MI355X_SP_TO(q31, q31_t, int32_t, float, float32_t, float)
+MI355X_SP_TO(q31, q31_t, int32_t, q15, q15_t, int16_t)
+MI355X_SP_TO(q31, q31_t, int32_t, q7, q7_t, int8_t)
+MI355X_SP_TO(q15, q15_t, int16_t, float, float32_t, float)
+MI355X_SP_TO(q15, q15_t, int16_t, q31, q31_t, int32_t)
+MI355X_SP_TO(q15, q15_t, int16_t, q7, q7_t, int8_t)
+MI355X_SP_TO(q7, q7_t, int8_t, float, float32_t, float)
+MI355X_SP_TO(q7, q7_t, int8_t, q31, q31_t, int32_t)
+MI355X_SP_TO(q7, q7_t, int8_t, q15, q15_t, int16_t)
+MI355X_SP_COPY(f32, float32_t, float)
+MI355X_SP_COPY(q31, q31_t, int32_t)
+MI355X_SP_COPY(q15, q15_t, int16_t)
+MI355X_SP_COPY(q7, q7_t, int8_t)
+#undef MI355X_SP_COPY
+#undef MI355X_SP_TO
+
+// S->alg selects among equal results: a value of arm_sort_alg sorts, any other is the no-op of the reference's switch.
+void arm_sort_f32(const arm_sort_instance_f32* S, float32_t* pSrc, float32_t* pDst, uint32_t blockSize) {
+  if (!S) { refuse(true, "arm_sort_f32"); return; }
+  if ((int)S->alg < (int)ARM_SORT_BITONIC || (int)S->alg > (int)ARM_SORT_SELECTION) return;
+  sp_sort((int)S->dir, pSrc, pDst, blockSize, true, 1, nullptr, "arm_sort_f32");
+}
+// S->buffer is neither read nor written.
+void arm_merge_sort_f32(const arm_merge_sort_instance_f32* S, float32_t* pSrc, float32_t* pDst, uint32_t blockSize) {
+  if (!S) { refuse(true, "arm_merge_sort_f32"); return; }
+  sp_sort((int)S->dir, pSrc, pDst, blockSize, true, 1, nullptr, "arm_merge_sort_f32");
+}
+arm_status arm_sort_f32_batch(const float32_t* d_src, float32_t* d_dst, uint32_t blockSize, arm_sort_dir dir,
+                              uint32_t batch, void* stream) {
+  return sp_sort((int)dir, d_src, d_dst, blockSize, false, batch, stream, "arm_sort_f32_batch");
+}
+arm_status arm_merge_sort_f32_batch(const float32_t* d_src, float32_t* d_dst, uint32_t blockSize, arm_sort_dir dir,
+                                    uint32_t batch, void* stream) {
+  return sp_sort((int)dir, d_src, d_dst, blockSize, false, batch, stream, "arm_merge_sort_f32_batch");
+}
+float32_t arm_weighted_average_f32(const float32_t* in, const float32_t* weights, uint32_t blockSize) {
+  float32_t r = 0.0f;
+  if (sp_wavg(in, weights, blockSize, blockSize, &r, true, 1, nullptr, "arm_weighted_average_f32") !=
+      ARM_MATH_SUCCESS)
+    return __builtin_nanf("");
+  return r;
+}
+arm_status arm_weighted_average_f32_batch(const float32_t* d_in, const float32_t* d_weights, uint32_t wStride,
+                                          uint32_t blockSize, float32_t* d_result, uint32_t batch, void* stream) {
+  return sp_wavg(d_in, d_weights, wStride, blockSize, d_result, false, batch, stream,
+                 "arm_weighted_average_f32_batch");
+}
+void arm_barycenter_f32(const float32_t* in, const float32_t* weights, float32_t* out, uint32_t nbVectors,
+                        uint32_t vecDim) {
+  sp_barycenter(in, weights, nbVectors, out, nbVectors, vecDim, true, 1, nullptr, "arm_barycenter_f32");
+}
+arm_status arm_barycenter_f32_batch(const float32_t* d_in, const float32_t* d_weights, uint32_t wStride,
+                                    float32_t* d_out, uint32_t nbVectors, uint32_t vecDim, uint32_t batch,
+                                    void* stream) {
+  return sp_barycenter(d_in, d_weights, wStride, d_out, nbVectors, vecDim, false, batch, stream,
+                       "arm_barycenter_f32_batch");
+}
+}  // extern "C"

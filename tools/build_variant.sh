@@ -16,8 +16,11 @@ for src in csrc/*.hip; do
   OBJS="$OBJS $OUT/$f.o"
 done
 SRC_ID=$(cat build/srcid.stamp 2>/dev/null || echo unknown)
-/opt/rocm/bin/hipcc $FLAGS -DMI355X_BUILD_DEFS="\"$DEFS\"" -DMI355X_SRC_ID="\"$SRC_ID\"" -c csrc/api.cpp -o $OUT/api.o &
+for f in api api_vector; do   # both units of the C ABI, so a variant links no entry point built with other macros
+  /opt/rocm/bin/hipcc $FLAGS -DMI355X_BUILD_DEFS="\"$DEFS\"" -DMI355X_SRC_ID="\"$SRC_ID\"" -c csrc/$f.cpp -o $OUT/$f.o &
+  OBJS="$OBJS $OUT/$f.o"
+done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic -o lib/variants/lib_$NAME.so \
-  $OBJS $OUT/api.o build/runtime.o build/init.o build/buffer_sizes.o build/tables_data.o
+  $OBJS build/runtime.o build/init.o build/buffer_sizes.o build/tables_data.o
 echo "lib/variants/lib_$NAME.so"
