@@ -781,6 +781,56 @@ def arm_barycenter_f32(pSrcA, pSrcB, nbVectors, vecDim):
     return _amd.arm_barycenter_f32(_arr(pSrcA, _np.float32), _arr(pSrcB, _np.float32), int(nbVectors), int(vecDim))
 
 
+# ------------------------------------------------------------------ distance functions
+ARM_DTW_SAKOE_CHIBA_WINDOW = _amd.ARM_DTW_SAKOE_CHIBA_WINDOW
+ARM_DTW_SLANTED_BAND_WINDOW = _amd.ARM_DTW_SLANTED_BAND_WINDOW
+
+
+def _distance_f32(name):
+    def run(pSrcA, pSrcB):
+        return float(_amd.arm_distance_f32(name, _arr(pSrcA, _np.float32), _arr(pSrcB, _np.float32)))
+    run.__name__ = f"arm_{name}_distance_f32"
+    run.__doc__ = f"cmsisdsp_distance.c cmsis_arm_{name}_distance_f32 (pSrcA, pSrcB) -> a Python float; blockSize = " \
+                  "len(pSrcA).  The operands are copied (the reference's binding copies them too)."
+    return run
+
+
+def _distance_bool(name):
+    def run(pSrcA, pSrcB, numberOfBools):
+        return float(_amd.arm_boolean_distance(name, _arr(pSrcA, _np.uint32), _arr(pSrcB, _np.uint32),
+                                               int(numberOfBools)))
+    run.__name__ = f"arm_{name}_distance"
+    run.__doc__ = f"cmsisdsp_distance.c cmsis_arm_{name}_distance (pSrcA, pSrcB, numberOfBools) -> a Python float."
+    return run
+
+
+for _n in _amd.DISTANCE_F32:
+    globals()[f"arm_{_n}_distance_f32"] = _distance_f32(_n)
+for _n in _amd.DISTANCE_BOOL:
+    globals()[f"arm_{_n}_distance"] = _distance_bool(_n)
+
+
+def arm_dtw_init_window_q7(windowType, windowSize, pWindow):
+    """cmsisdsp_distance.c cmsis_arm_dtw_init_window_q7 (type, size, window matrix) -> (status, window): the shape is
+    taken from pWindow; an unknown type returns the status and a copy of pWindow."""
+    w = _arr(pWindow, _np.int8)
+    st, out = _amd.arm_dtw_init_window_q7(windowType, windowSize, w.shape[0], w.shape[1])
+    return int(st), (out if st == 0 else w.copy())
+
+
+def arm_dtw_distance_f32(pDistance, pWindow):
+    """cmsisdsp_distance.c cmsis_arm_dtw_distance_f32 (distance matrix, window matrix or None) -> (status, distance,
+    dtw cost matrix)."""
+    st, value, cost = _amd.arm_dtw_distance_f32(_arr(pDistance, _np.float32),
+                                                None if pWindow is None else _arr(pWindow, _np.int8))
+    return int(st), float(value), cost
+
+
+def arm_dtw_path_f32(pDTW):
+    """cmsisdsp_distance.c cmsis_arm_dtw_path_f32 (cost matrix) -> the path as 2 * pathLength int16 words."""
+    return _amd.arm_dtw_path_f32(_arr(pDTW, _np.float32)).reshape(-1)
+
+
 def arm_sqrt_q15(x):
     """cmsisdsp_fastmath.c cmsis_arm_sqrt_q15 (in) -> (status, pOut)."""
     st, v = _amd.arm_sqrt_q15(x)

@@ -58,6 +58,7 @@ def _load():
     _abi.bind(lib, _abi.STATISTICS)
     _abi.bind(lib, _abi.BASIC_MATH)
     _abi.bind(lib, _abi.SUPPORT)
+    _abi.bind(lib, _abi.DISTANCE)
     _abi.bind(lib, _abi.BATCHED)
     return lib
 
@@ -1467,6 +1468,123 @@ def barycenter_batch(src, weights, out, stream=None, w_stride=None):
         w_stride = 0 if weights.dim() == 1 else weights.shape[-1]
     _solve_call("arm_barycenter_f32_batch", _cm_ptr(src), _cm_ptr(weights), int(w_stride), _cm_ptr(out),
                 src.shape[1], src.shape[2], src.shape[0], _stream_ptr(stream))
+
+
+# ---- distance functions: f32, boolean, dynamic time warping ------------------------------------------------------
+ARM_DTW_SAKOE_CHIBA_WINDOW, ARM_DTW_SLANTED_BAND_WINDOW = 1, 3
+DISTANCE_F32 = _abi.DISTANCE_F32
+DISTANCE_BOOL = _abi.DISTANCE_BOOL
+
+
+def arm_distance_f32(name, a, b):
+    """arm_<name>_distance_f32 of two float32 vectors (drop-in, numpy; name in DISTANCE_F32).  correlation works on
+    copies; arm_correlation_distance_f32 below returns the shifted vectors as well."""
+    fn = f"arm_{name}_distance_f32"
+    x, y = np.array(a, dtype=np.float32).reshape(-1), np.array(b, dtype=np.float32).reshape(-1)
+    if x.size != y.size:
+        raise ValueError(f"{fn}: {x.size} and {y.size} words")
+    r = getattr(lib, fn)(x.ctypes.data, y.ctypes.data, x.size)
+    _check_void(fn)
+    return np.float32(r)
+
+
+def arm_correlation_distance_f32(a, b):
+    """(distance, a - mean(a), b - mean(b)): the reference overwrites its operands with the shifted words."""
+    x, y = np.array(a, dtype=np.float32).reshape(-1), np.array(b, dtype=np.float32).reshape(-1)
+    if x.size != y.size:
+        raise ValueError(f"arm_correlation_distance_f32: {x.size} and {y.size} words")
+    r = lib.arm_correlation_distance_f32(x.ctypes.data, y.ctypes.data, x.size)
+    _check_void("arm_correlation_distance_f32")
+    return np.float32(r), x, y
+
+
+def arm_boolean_distance(name, a, b, number_of_bools):
+    """arm_<name>_distance of two vectors of packed uint32 words (drop-in, numpy; name in DISTANCE_BOOL); of a last,
+    partial word the top number_of_bools % 32 bits count."""
+    fn = f"arm_{name}_distance"
+    x, y = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1), np.ascontiguousarray(b, dtype=np.uint32).reshape(-1)
+    words = (int(number_of_bools) + 31) // 32
+    if x.size < words or y.size < words:
+        raise ValueError(f"{fn}: {number_of_bools} booleans need {words} words")
+    r = getattr(lib, fn)(x.ctypes.data, y.ctypes.data, int(number_of_bools))
+    _check_void(fn)
+    return np.float32(r)
+
+
+def arm_dtw_init_window_q7(window_type, window_size, rows, cols):
+    """(status, window [rows, cols] int8) through arm_dtw_init_window_q7."""
+    w = np.zeros((rows, cols), dtype=np.int8)
+    st = lib.arm_dtw_init_window_q7(int(window_type), int(window_size), C.byref(_mat("q7", w)))
+    _check_void("arm_dtw_init_window_q7")
+    return st, w
+
+
+def arm_dtw_distance_f32(distance, window=None):
+    """(status, distance value, dtw cost matrix) through arm_dtw_distance_f32; window: int8 [rows, cols] or None.
+    The value is NaN where the status is ARM_MATH_ARGUMENT_ERROR (no path inside the window)."""
+    d = np.ascontiguousarray(distance, dtype=np.float32)
+    cost = np.zeros_like(d)
+    value = np.full(1, np.nan, dtype=np.float32)
+    w = None if window is None else np.ascontiguousarray(window, dtype=np.int8)
+    st = lib.arm_dtw_distance_f32(C.byref(_matf(d)), None if w is None else C.byref(_mat("q7", w)),
+                                  C.byref(_matf(cost)), value.ctypes.data)
+    _check_void("arm_dtw_distance_f32")
+    return st, value[0], cost
+
+
+def arm_dtw_path_f32(dtw):
+    """The warping path [length, 2] int16 of (query, template) index pairs through arm_dtw_path_f32."""
+    c = np.ascontiguousarray(dtw, dtype=np.float32)
+    path = np.zeros(2 * (c.shape[0] + c.shape[1]), dtype=np.int16)
+    length = np.zeros(1, dtype=np.uint32)
+    lib.arm_dtw_path_f32(C.byref(_matf(c)), path.ctypes.data, length.ctypes.data)
+    _check_void("arm_dtw_path_f32")
+    return path[:2 * int(length[0])].reshape(-1, 2)
+
+
+def distance_batch(name, a, b, result, stream=None, b_stride=None):
+    """result[i] = arm_<name>_distance_f32 of a[i] and b_i for float32 device tensors a [batch, N], b [N] (one vector
+    for every item: one query against many stored vectors) or [batch, N], result [batch].  b_stride (words) overrides
+    the distance between the items' b vectors.  The sources are only read."""
+    if b_stride is None:
+        b_stride = 0 if b.dim() == 1 else b.shape[-1]
+    _solve_call(f"arm_{name}_distance_f32_batch", _cm_ptr(a), _cm_ptr(b), int(b_stride), a.shape[-1], _cm_ptr(result),
+                a.shape[0], _stream_ptr(stream))
+
+
+def boolean_distance_batch(name, a, b, number_of_bools, result, stream=None, b_stride=None):
+    """result[i] = arm_<name>_distance of the number_of_bools booleans packed in a[i] and b_i: int32 device tensors a
+    [batch, ceil(number_of_bools / 32)], b the same or one row for every item; result float32 [batch]."""
+    if b_stride is None:
+        b_stride = 0 if b.dim() == 1 else b.shape[-1]
+    _solve_call(f"arm_{name}_distance_batch", _cm_ptr(a), _cm_ptr(b), int(b_stride), int(number_of_bools),
+                _cm_ptr(result), a.shape[0], _stream_ptr(stream))
+
+
+def dtw_init_window_batch(window_type, window_size, window, stream=None):
+    """Fills every item of the int8 device tensor window [batch, rows, cols] (arm_dtw_init_window_q7_batch)."""
+    _solve_call("arm_dtw_init_window_q7_batch", int(window_type), int(window_size), _cm_ptr(window), window.shape[-2],
+                window.shape[-1], window.numel() // max(1, window.shape[-2] * window.shape[-1]), _stream_ptr(stream))
+
+
+def dtw_distance_batch(distance, window, dtw, result, status=None, stream=None, w_stride=None):
+    """dtw[i], result[i] = the cost matrix and the DTW distance of distance[i] for float32 device tensors [batch, rows,
+    cols] (arm_dtw_distance_f32_batch); window: None, int8 [rows, cols] (one for every item) or [batch, rows, cols].
+    Returns the per-item int32 status tensor as mat_inverse_batch does; result[i] is written where it is 0."""
+    status, ps = _solve_status(distance, status)
+    if w_stride is None:
+        w_stride = 0 if window is None or window.dim() == 2 else window.shape[-2] * window.shape[-1]
+    _solve_call("arm_dtw_distance_f32_batch", _cm_ptr(distance), C.c_void_p(None if window is None else window.data_ptr()),
+                int(w_stride), _cm_ptr(dtw), distance.shape[-2], distance.shape[-1], _cm_ptr(result), ps,
+                distance.shape[0], _stream_ptr(stream))
+    return None if status is False else status
+
+
+def dtw_path_batch(dtw, path, path_length, stream=None):
+    """path[i] (int16 [batch, rows + cols, 2]) and path_length[i] (int32 [batch]) = the warping path of the cost
+    matrix dtw[i] (arm_dtw_path_f32_batch); a length of 0 marks a matrix without a path."""
+    _solve_call("arm_dtw_path_f32_batch", _cm_ptr(dtw), dtw.shape[-2], dtw.shape[-1], _cm_ptr(path),
+                _cm_ptr(path_length), dtw.shape[0], _stream_ptr(stream))
 
 
 def mat_mult_batch(a, b, c, stream=None, fast=False):

@@ -474,6 +474,27 @@ SUPPORT["arm_weighted_average_f32_batch"] = (C.c_int, [_vp, _vp, _u32, _u32, _vp
 SUPPORT["arm_barycenter_f32"] = (None, [_vp, _vp, _vp, _u32, _u32])
 SUPPORT["arm_barycenter_f32_batch"] = (C.c_int, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp])
 
+# Distance functions: 20 drop-ins (the reference's signatures) with their _batch forms.  The product only
+# (tests/golden/distance.npz holds the reference's outputs).  arm_dtw_window is a C enum (int).
+DISTANCE = {}
+DISTANCE_F32 = ("braycurtis", "canberra", "chebyshev", "cityblock", "correlation", "cosine", "euclidean",
+                "jensenshannon")
+DISTANCE_BOOL = ("dice", "hamming", "jaccard", "kulsinski", "rogerstanimoto", "russellrao", "sokalmichener",
+                 "sokalsneath", "yule")
+for _n in DISTANCE_F32:
+    DISTANCE[f"arm_{_n}_distance_f32"] = (C.c_float, [_vp, _vp, _u32])
+    DISTANCE[f"arm_{_n}_distance_f32_batch"] = (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp])
+for _n in DISTANCE_BOOL:
+    DISTANCE[f"arm_{_n}_distance"] = (C.c_float, [_vp, _vp, _u32])
+    DISTANCE[f"arm_{_n}_distance_batch"] = (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp])
+DISTANCE["arm_dtw_init_window_q7"] = (C.c_int, [C.c_int, C.c_int32, P(arm_matrix_instance_q7)])
+DISTANCE["arm_dtw_init_window_q7_batch"] = (C.c_int, [C.c_int, C.c_int32, _vp, _u32, _u32, _u32, _vp])
+DISTANCE["arm_dtw_distance_f32"] = (C.c_int, [P(arm_matrix_instance_f32), P(arm_matrix_instance_q7),
+                                              P(arm_matrix_instance_f32), _vp])
+DISTANCE["arm_dtw_distance_f32_batch"] = (C.c_int, [_vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _u32, _vp])
+DISTANCE["arm_dtw_path_f32"] = (None, [P(arm_matrix_instance_f32), _vp, _vp])
+DISTANCE["arm_dtw_path_f32_batch"] = (C.c_int, [_vp, _u32, _u32, _vp, _vp, _u32, _vp])
+
 # per-length MFCC init functions (the product and the reference build; the oracle has the
 # generic init only)
 MFCC_LEN = {f"arm_mfcc_init_{n}_f32": (C.c_int, [P(arm_mfcc_instance_f32), C.c_uint32, C.c_uint32, C.c_void_p,

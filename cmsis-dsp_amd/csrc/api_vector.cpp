@@ -927,3 +927,199 @@ arm_status arm_barycenter_f32_batch(const float32_t* d_in, const float32_t* d_we
                        "arm_barycenter_f32_batch");
 }
 }  // extern "C"
+
+// ---- distance functions (distance.hip) ------------------------------------------------------------
+// distance_functions.h.  The two-source reductions go through strided_reduce (bStride in words, 0: one B vector for
+// every item).  blockSize == 0 stores what the reference's arithmetic gives on empty sums, except chebyshev, which
+// would read element 0 and is refused.  A drop-in returns its float; a failure returns a NaN with the last error set.
+namespace {
+arm_status ds_f32(int op, const float* a, const float* b, uint32_t bStride, uint32_t n, float* result, bool sync,
+                  uint32_t batch, void* stream, const char* what) {
+  if (op == kDsChebyshev && n == 0) return refuse(sync, what);
+  return strided_reduce(1, a, b, bStride, n, result, (float*)nullptr, sync, batch, stream, what,
+                        [&](const float* da, const float* db, float* dr, float*, hipStream_t st) {
+                          return distance_f32_launch(op, da, db, bStride, n, dr, batch, nullptr, nullptr, st);
+                        });
+}
+
+// The drop-in of the correlation distance: pA and pB are results as well (the shifted words).
+arm_status ds_correlation_sync(float* a, float* b, uint32_t n, float* result, const char* what) {
+  const size_t sb = sizeof(float) * n;
+  const VecCall c{what, true, nullptr, 0, 3, {{a, sb, kIn | kOut}, {b, sb, kIn | kOut}, {result, sizeof(float), kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  return c.run([&](void* const* p, hipStream_t st) {
+    return distance_f32_launch(kDsCorrelation, (const float*)p[0], (const float*)p[1], n, n, (float*)p[2], 1,
+                               (float*)p[0], (float*)p[1], st);
+  });
+}
+
+arm_status ds_bool(int op, const uint32_t* a, const uint32_t* b, uint32_t bStride, uint32_t nbools, float* result,
+                   bool sync, uint32_t batch, void* stream, const char* what) {
+  const uint32_t words = (uint32_t)(((uint64_t)nbools + 31) / 32);
+  return strided_reduce(1, a, b, bStride, words, result, (float*)nullptr, sync, batch, stream, what,
+                        [&](const uint32_t* da, const uint32_t* db, float* dr, float*, hipStream_t st) {
+                          return boolean_distance_launch(op, da, db, bStride, nbools, dr, batch, st);
+                        });
+}
+
+bool dtw_length_ok(uint32_t q, uint32_t t) { return q >= 1 && t >= 1 && q <= 32768 && t <= 32768; }
+
+arm_status ds_dtw_window(int type, int32_t size, int8_t* w, uint32_t q, uint32_t t, bool sync, uint32_t batch,
+                         void* stream, const char* what) {
+  const VecCall c{what, sync, stream, 0, 1, {{w, (size_t)q * t * batch, kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if ((type != ARM_DTW_SAKOE_CHIBA_WINDOW && type != ARM_DTW_SLANTED_BAND_WINDOW) || q > 32768 || t > 32768)
+    return ARM_MATH_ARGUMENT_ERROR;                         // the reference's default: a status, no last error
+  if (batch == 0 || q == 0 || t == 0) return ARM_MATH_SUCCESS;
+  return c.run([&](void* const* p, hipStream_t st) {
+    return dtw_init_window_launch(type, size, (int8_t*)p[0], q, t, batch, st);
+  });
+}
+
+// result is staged in as well: an item without a path leaves its word alone.
+arm_status ds_dtw_distance(const float* dist, const int8_t* window, uint32_t wStride, float* dtw, uint32_t q,
+                           uint32_t t, float* result, int32_t* d_status, bool sync, uint32_t batch, void* stream,
+                           const char* what) {
+  const size_t cells = (size_t)q * t;
+  VecCall c{what, sync, stream, 0, window ? 4 : 3,
+            {{dist, sizeof(float) * cells * batch, kIn}, {dtw, sizeof(float) * cells * batch, kOut},
+             {result, sizeof(float) * batch, kIn | kOut}, {window, (size_t)wStride * (batch - 1) + cells, kIn}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (!dtw_length_ok(q, t) || (window && wStride != 0 && wStride < cells)) return refuse(sync, what);
+  if (batch == 0) return ARM_MATH_SUCCESS;
+  return c.run_with_status(d_status, [&](void* const* p, int32_t* ds, hipStream_t st) {
+    // without a window operand 3 is the drop-in's status word
+    return dtw_distance_launch((const float*)p[0], window ? (const int8_t*)p[3] : nullptr, wStride, (float*)p[1], q, t,
+                               (float*)p[2], ds, batch, st);
+  });
+}
+
+arm_status ds_dtw_path(const float* dtw, uint32_t q, uint32_t t, int16_t* path, uint32_t* len, bool sync,
+                       uint32_t batch, void* stream, const char* what) {
+  const VecCall c{what, sync, stream, 0, 3,
+                  {{dtw, sizeof(float) * q * t * batch, kIn},
+                   {path, sizeof(int16_t) * 2 * ((size_t)q + t) * batch, kIn | kOut},
+                   {len, sizeof(uint32_t) * batch, kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (!dtw_length_ok(q, t)) return refuse(sync, what);
+  if (batch == 0) return ARM_MATH_SUCCESS;
+  return c.run([&](void* const* p, hipStream_t st) {
+    return dtw_path_launch((const float*)p[0], q, t, (int16_t*)p[1], (uint32_t*)p[2], batch, st);
+  });
+}
+
+template <typename M>
+bool same_dims(const M* m, uint32_t q, uint32_t t) { return m->numRows == q && m->numCols == t; }
+}  // namespace
+
+extern "C" {
+#define MI355X_DS_F32(NAME, OP)                                                                                  \
+  float32_t arm_##NAME##_distance_f32(const float32_t* pA, const float32_t* pB, uint32_t blockSize) {            \
+    float32_t r = 0.0f;                                                                                          \
+    if (ds_f32(OP, pA, pB, blockSize, blockSize, &r, true, 1, nullptr, "arm_" #NAME "_distance_f32") !=          \
+        ARM_MATH_SUCCESS)                                                                                        \
+      return __builtin_nanf("");                                                                                 \
+    return r;                                                                                                    \
+  }
+#define MI355X_DS_F32_BATCH(NAME, OP)                                                                            \
+  arm_status arm_##NAME##_distance_f32_batch(const float32_t* d_a, const float32_t* d_b, uint32_t bStride,       \
+                                             uint32_t blockSize, float32_t* d_result, uint32_t batch,            \
+                                             void* stream) {                                                     \
+    return ds_f32(OP, d_a, d_b, bStride, blockSize, d_result, false, batch, stream,                              \
+                  "arm_" #NAME "_distance_f32_batch");                                                           \
+  }
+#define MI355X_DS_BOOL(NAME, OP)                                                                                 \
+  float32_t arm_##NAME##_distance(const uint32_t* pA, const uint32_t* pB, uint32_t numberOfBools) {              \
+    float32_t r = 0.0f;                                                                                          \
+    const uint32_t words = (uint32_t)(((uint64_t)numberOfBools + 31) / 32);                                      \
+    if (ds_bool(OP, pA, pB, words, numberOfBools, &r, true, 1, nullptr, "arm_" #NAME "_distance") !=             \
+        ARM_MATH_SUCCESS)                                                                                        \
+      return __builtin_nanf("");                                                                                 \
+    return r;                                                                                                    \
+  }                                                                                                              \
+  arm_status arm_##NAME##_distance_batch(const uint32_t* d_a, const uint32_t* d_b, uint32_t bStride,             \
+                                         uint32_t numberOfBools, float32_t* d_result, uint32_t batch,            \
+                                         void* stream) {                                                         \
+    return ds_bool(OP, d_a, d_b, bStride, numberOfBools, d_result, false, batch, stream,                         \
+                   "arm_" #NAME "_distance_batch");                                                              \
+  }
+MI355X_DS_F32(braycurtis, kDsBraycurtis)
+MI355X_DS_F32(canberra, kDsCanberra)
+MI355X_DS_F32(chebyshev, kDsChebyshev)
+MI355X_DS_F32(cityblock, kDsCityblock)
+MI355X_DS_F32(cosine, kDsCosine)
+MI355X_DS_F32(euclidean, kDsEuclidean)
+MI355X_DS_F32(jensenshannon, kDsJensenshannon)
+MI355X_DS_F32_BATCH(braycurtis, kDsBraycurtis)
+MI355X_DS_F32_BATCH(canberra, kDsCanberra)
+MI355X_DS_F32_BATCH(chebyshev, kDsChebyshev)
+MI355X_DS_F32_BATCH(cityblock, kDsCityblock)
+MI355X_DS_F32_BATCH(correlation, kDsCorrelation)
+MI355X_DS_F32_BATCH(cosine, kDsCosine)
+MI355X_DS_F32_BATCH(euclidean, kDsEuclidean)
+MI355X_DS_F32_BATCH(jensenshannon, kDsJensenshannon)
+MI355X_DS_BOOL(dice, kBdDice)
+MI355X_DS_BOOL(hamming, kBdHamming)
+MI355X_DS_BOOL(jaccard, kBdJaccard)
+MI355X_DS_BOOL(kulsinski, kBdKulsinski)
+MI355X_DS_BOOL(rogerstanimoto, kBdRogerstanimoto)
+MI355X_DS_BOOL(russellrao, kBdRussellrao)
+MI355X_DS_BOOL(sokalmichener, kBdSokalmichener)
+MI355X_DS_BOOL(sokalsneath, kBdSokalsneath)
+MI355X_DS_BOOL(yule, kBdYule)
+#undef MI355X_DS_BOOL
+#undef MI355X_DS_F32_BATCH
+#undef MI355X_DS_F32
+
+float32_t arm_correlation_distance_f32(float32_t* pA, float32_t* pB, uint32_t blockSize) {
+  float32_t r = 0.0f;
+  if (ds_correlation_sync(pA, pB, blockSize, &r, "arm_correlation_distance_f32") != ARM_MATH_SUCCESS)
+    return __builtin_nanf("");
+  return r;
+}
+
+arm_status arm_dtw_init_window_q7(const arm_dtw_window windowType, const int32_t windowSize,
+                                  arm_matrix_instance_q7* pWindow) {
+  if (!pWindow) return ARM_MATH_ARGUMENT_ERROR;
+  return ds_dtw_window((int)windowType, windowSize, pWindow->pData, pWindow->numRows, pWindow->numCols, true, 1,
+                       nullptr, "arm_dtw_init_window_q7");
+}
+arm_status arm_dtw_init_window_q7_batch(arm_dtw_window windowType, int32_t windowSize, q7_t* d_window,
+                                        uint32_t queryLength, uint32_t templateLength, uint32_t batch, void* stream) {
+  return ds_dtw_window((int)windowType, windowSize, d_window, queryLength, templateLength, false, batch, stream,
+                       "arm_dtw_init_window_q7_batch");
+}
+arm_status arm_dtw_distance_f32(const arm_matrix_instance_f32* pDistance, const arm_matrix_instance_q7* pWindow,
+                                arm_matrix_instance_f32* pDTW, float32_t* distance) {
+  if (!pDistance || !pDTW) return ARM_MATH_ARGUMENT_ERROR;
+  const uint32_t q = pDistance->numRows, t = pDistance->numCols;
+  if (!same_dims(pDTW, q, t) || (pWindow && !same_dims(pWindow, q, t))) return ARM_MATH_SIZE_MISMATCH;
+  if (pWindow && !pWindow->pData) return refuse(true, "arm_dtw_distance_f32");
+  return ds_dtw_distance(pDistance->pData, pWindow ? pWindow->pData : nullptr, 0, pDTW->pData, q, t, distance, nullptr,
+                         true, 1, nullptr, "arm_dtw_distance_f32");
+}
+arm_status arm_dtw_distance_f32_batch(const float32_t* d_distance, const q7_t* d_window, uint32_t wStride,
+                                      float32_t* d_dtw, uint32_t queryLength, uint32_t templateLength,
+                                      float32_t* d_result, int32_t* d_status, uint32_t batch, void* stream) {
+  return ds_dtw_distance(d_distance, d_window, wStride, d_dtw, queryLength, templateLength, d_result, d_status, false,
+                         batch, stream, "arm_dtw_distance_f32_batch");
+}
+// *pathLength goes through a local word, so a refusal can clear it and an empty path can be reported.
+void arm_dtw_path_f32(const arm_matrix_instance_f32* pDTW, int16_t* pPath, uint32_t* pathLength) {
+  const char* what = "arm_dtw_path_f32";
+  if (!pDTW || !pathLength) { refuse(true, what); return; }
+  uint32_t len = 0;
+  const arm_status r = ds_dtw_path(pDTW->pData, pDTW->numRows, pDTW->numCols, pPath, &len, true, 1, nullptr, what);
+  if (r == ARM_MATH_SUCCESS && len == 0) set_error(hipErrorInvalidValue, what);   // the reference would not return
+  if (is_device_ptr(pathLength)) {
+    if (hipMemcpy(pathLength, &len, sizeof(len), hipMemcpyHostToDevice) != hipSuccess) set_error(hipErrorInvalidValue, what);
+  } else {
+    *pathLength = len;
+  }
+}
+arm_status arm_dtw_path_f32_batch(const float32_t* d_dtw, uint32_t queryLength, uint32_t templateLength,
+                                  int16_t* d_path, uint32_t* d_pathLength, uint32_t batch, void* stream) {
+  return ds_dtw_path(d_dtw, queryLength, templateLength, d_path, d_pathLength, false, batch, stream,
+                     "arm_dtw_path_f32_batch");
+}
+}  // extern "C"

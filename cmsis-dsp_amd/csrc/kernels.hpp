@@ -389,4 +389,36 @@ constexpr uint32_t kSortLdsMax = 16384;    // padded length up to which one work
 hipError_t sort_launch(const uint32_t* src, uint32_t* dst, uint32_t n, bool ascending, uint32_t batch,
                        hipStream_t st);
 
+// The distance functions, bit-exact with the reference's scalar branches (distance.hip).
+// result[i] = arm_<op>_distance_f32 of a + i * n and b + i * bStride (n words each; bStride 0: one b for every item).
+// The sums are ordered chains.  wa / wb (kDsCorrelation only, both or neither): where the shifted words x + (-mean)
+// of a and b are stored, item for item (the drop-in passes a and b themselves); null: the sources are only read.
+// kDsChebyshev needs n > 0.
+enum : int {
+  kDsBraycurtis = 0, kDsCanberra, kDsChebyshev, kDsCityblock, kDsCorrelation, kDsCosine, kDsEuclidean,
+  kDsJensenshannon
+};
+hipError_t distance_f32_launch(int op, const float* a, const float* b, size_t bStride, uint32_t n, float* result,
+                               uint32_t batch, float* wa, float* wb, hipStream_t st);
+// result[i] = arm_<op>_distance of the n booleans packed at a + i * ceil(n / 32) and b + i * bStride words; of a
+// partial last word the top n % 32 bits count; no word past ceil(n / 32) is read.
+enum : int {
+  kBdDice = 0, kBdHamming, kBdJaccard, kBdKulsinski, kBdRogerstanimoto, kBdRussellrao, kBdSokalmichener,
+  kBdSokalsneath, kBdYule
+};
+hipError_t boolean_distance_launch(int op, const uint32_t* a, const uint32_t* b, size_t bStride, uint32_t n,
+                                   float* result, uint32_t batch, hipStream_t st);
+// arm_dtw_init_window_q7 into `batch` contiguous rows x cols windows; type 1 (Sakoe-Chiba) or 3 (slanted band).
+hipError_t dtw_init_window_launch(int type, int32_t windowSize, int8_t* dst, uint32_t rows, uint32_t cols,
+                                  uint32_t batch, hipStream_t st);
+// arm_dtw_distance_f32 on `batch` contiguous rows x cols matrices (rows, cols > 0): dtw receives every cost cell,
+// status[i] (may be null) 0 or -1 (ARM_MATH_ARGUMENT_ERROR), result[i] the distance where the status is 0.  window:
+// null, or item i's at window + i * wStride bytes (0: one for every item).
+hipError_t dtw_distance_launch(const float* dist, const int8_t* window, size_t wStride, float* dtw, uint32_t rows,
+                               uint32_t cols, float* result, int32_t* status, uint32_t batch, hipStream_t st);
+// arm_dtw_path_f32: path + i * 2 * (rows + cols) and pathLength[i] (0: the walk cannot leave a cell); rows, cols in
+// 1 .. 32768.
+hipError_t dtw_path_launch(const float* dtw, uint32_t rows, uint32_t cols, int16_t* path, uint32_t* pathLength,
+                           uint32_t batch, hipStream_t st);
+
 }  // namespace mi355x

@@ -30,6 +30,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "chain_f32.hpp"
 #include "reduce_lanes.hpp"
 
 #pragma clang fp contract(off)
@@ -204,10 +205,6 @@ __global__ __launch_bounds__(kBlock) void sum_int_kernel(const T* pa, const T* p
 }
 
 // ---- f32 chains ----------------------------------------------------------------------------------------------
-constexpr int kSumChunk = 16;                    // words per item and LDS stage (a 64-byte row segment)
-constexpr uint32_t kSumLaneMinBatch = 4096;      // from here on one lane per item, below one wave per item
-constexpr uint32_t kVarKeep = 1024;              // words of an item the wave form keeps in LDS between var's passes
-
 // The term of the chain's first (or only) pass.  y: the second source's element (mse).
 template <int OP>
 __device__ __forceinline__ float chain_term(float x, float y) {
@@ -223,8 +220,6 @@ __device__ __forceinline__ float chain_term(float x, float y) {
   }
 }
 
-__device__ __forceinline__ float sqrt_or_zero(float v) { return v >= 0.0f ? sqrtf(v) : 0.0f; }   // arm_sqrt_f32
-
 // sum: the last pass's chain; n > 1 for var / std.
 template <int OP>
 __device__ __forceinline__ float chain_finish(float sum, uint32_t n) {
@@ -233,18 +228,6 @@ __device__ __forceinline__ float chain_finish(float sum, uint32_t n) {
   else if constexpr (OP == kStVar) return sum / (float)((float)n - 1.0f);
   else if constexpr (OP == kStStd) return sqrt_or_zero(sum / (float)((float)n - 1.0f));
   else return sum;                                          // power, accumulate, dot_prod
-}
-
-// sum + t[0] + t[1] + ... + t[cnt - 1], lane j holding t[j], in that order.
-__device__ __forceinline__ float chain_lanes(float sum, float t, uint32_t cnt) {
-  if (cnt == 64) {
-#pragma unroll
-    for (int j = 0; j < 64; ++j)
-      sum = sum + __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, t), j));
-  } else {
-    for (uint32_t j = 0; j < cnt; ++j) sum = sum + __shfl(t, (int)j, 64);   // uniform trip count
-  }
-  return sum;
 }
 
 // One wave per item.

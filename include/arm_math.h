@@ -1263,6 +1263,68 @@ MI355X_DECL_SUPPORT_COPY(q15, q15_t)
 MI355X_DECL_SUPPORT_COPY(q7, q7_t)
 #undef MI355X_DECL_SUPPORT_COPY
 
+/* The distance functions of distance_functions.h: the f32 distances, the boolean distances on packed uint32_t words
+ * and dynamic time warping.  Host or device pointers, synchronous.  Every result word equals the reference's scalar
+ * branches (ARM_MATH_LOOPUNROLL, no FMA contraction); NaN results are NaNs, their bits are not pinned.
+ *   f32       every sum is an ordered chain from 0.0f in element order, each term rounded before its add; divisions
+ *             and square roots are correctly rounded; arm_sqrt_f32 gives +0.0 for a negative or NaN argument (so
+ *             euclidean, cosine, correlation and jensenshannon never return the NaN of a square root).  canberra
+ *             skips an element whose two words both compare equal to zero.  chebyshev starts from element 0 and
+ *             replaces on diff > maxVal only.  jensenshannon evaluates x * logf(x / m), m = (a + b) / 2.0f, with the
+ *             glibc logf the MFCC uses.  arm_correlation_distance_f32 writes x + (-mean) back into pA and pB, as the
+ *             reference does (its pointers are not const); pA and pB must not overlap.
+ *             blockSize == 0: chebyshev (which would read element 0) writes nothing, returns a NaN and sets
+ *             arm_mi355x_last_error(); every other function returns what its arithmetic gives on empty sums.
+ *   boolean   an item is ceil(numberOfBools / 32) words and no further word is read (the reference loads one more
+ *             when numberOfBools is a multiple of 32).  Of a last, partial word the top numberOfBools % 32 bits
+ *             count.  The epilogues are the reference's expressions: uint32_t sums and products wrap (yule's from
+ *             about 2^17 booleans on), counts above 2^24 round to nearest even when they become floats.
+ *             numberOfBools == 0 evaluates the epilogue on zero counts (mostly 0 / 0).
+ *   DTW       arm_dtw_distance_f32 writes every word of pDTW (F32_MAX outside the window) and *distance unless it
+ *             returns ARM_MATH_ARGUMENT_ERROR (the last cell is F32_MAX: no path inside the window); pWindow may be
+ *             NULL; a distance word outside the window is never read.  MIN(x, y) is x < y ? x : y, NaNs included.
+ *             arm_dtw_path_f32: the reference's walk; where the reference would never return (a cell with no
+ *             neighbour below F32_MAX) *pathLength is 0 and the last error is set.  arm_dtw_distance_f32 and
+ *             arm_dtw_path_f32 refuse lengths of 0 or above 32768.  arm_dtw_init_window_q7 returns
+ *             ARM_MATH_ARGUMENT_ERROR and writes nothing for an unknown window type or a length above 32768; with 0
+ *             rows or 0 columns it succeeds and writes nothing, as the reference does.
+ * A failure of a function that returns a float returns a NaN and sets the last error.
+ * Left out: arm_minkowski_distance_f32 (the host libm's powf, as arm_entropy_f32 and its kin) and the f16 / f64
+ * forms. */
+typedef enum {
+  ARM_DTW_SAKOE_CHIBA_WINDOW = 1,
+  /*ARM_DTW_ITAKURA_WINDOW = 2,*/
+  ARM_DTW_SLANTED_BAND_WINDOW = 3
+} arm_dtw_window;
+#define MI355X_DECL_DISTANCE_F32(NAME) \
+  float32_t arm_##NAME##_distance_f32(const float32_t *pA, const float32_t *pB, uint32_t blockSize);
+MI355X_DECL_DISTANCE_F32(braycurtis)
+MI355X_DECL_DISTANCE_F32(canberra)
+MI355X_DECL_DISTANCE_F32(chebyshev)
+MI355X_DECL_DISTANCE_F32(cityblock)
+MI355X_DECL_DISTANCE_F32(cosine)
+MI355X_DECL_DISTANCE_F32(euclidean)
+MI355X_DECL_DISTANCE_F32(jensenshannon)
+#undef MI355X_DECL_DISTANCE_F32
+float32_t arm_correlation_distance_f32(float32_t *pA, float32_t *pB, uint32_t blockSize);
+#define MI355X_DECL_DISTANCE_BOOL(NAME) \
+  float32_t arm_##NAME##_distance(const uint32_t *pA, const uint32_t *pB, uint32_t numberOfBools);
+MI355X_DECL_DISTANCE_BOOL(dice)
+MI355X_DECL_DISTANCE_BOOL(hamming)
+MI355X_DECL_DISTANCE_BOOL(jaccard)
+MI355X_DECL_DISTANCE_BOOL(kulsinski)
+MI355X_DECL_DISTANCE_BOOL(rogerstanimoto)
+MI355X_DECL_DISTANCE_BOOL(russellrao)
+MI355X_DECL_DISTANCE_BOOL(sokalmichener)
+MI355X_DECL_DISTANCE_BOOL(sokalsneath)
+MI355X_DECL_DISTANCE_BOOL(yule)
+#undef MI355X_DECL_DISTANCE_BOOL
+arm_status arm_dtw_init_window_q7(const arm_dtw_window windowType, const int32_t windowSize,
+                                  arm_matrix_instance_q7 *pWindow);
+arm_status arm_dtw_distance_f32(const arm_matrix_instance_f32 *pDistance, const arm_matrix_instance_q7 *pWindow,
+                                arm_matrix_instance_f32 *pDTW, float32_t *distance);
+void arm_dtw_path_f32(const arm_matrix_instance_f32 *pDTW, int16_t *pPath, uint32_t *pathLength);
+
 #ifdef __cplusplus
 }
 #endif

@@ -568,6 +568,58 @@ arm_status arm_barycenter_f32_batch(const float32_t *d_in, const float32_t *d_we
                                     float32_t *d_out, uint32_t nbVectors, uint32_t vecDim, uint32_t batch,
                                     void *stream);
 
+/* Batched distance functions (arm_math.h: "The distance functions").  Device pointers, stream-ordered.
+ * f32: d_result[i] = the distance of the blockSize words at d_a + i * blockSize and d_b + i * bStride; boolean: of the
+ * ceil(numberOfBools / 32) words at d_a + i * that count and d_b + i * bStride.  bStride (words) 0 means one B vector
+ * for every item (one query against many stored vectors), otherwise bStride >= the item's word count.  The sources are
+ * only read, arm_correlation_distance_f32_batch included.  Below 4096 items an f32 item gets one wave, from there on
+ * one lane; a boolean item gets the lanes its word count asks for (16-byte loads when both pointers, the item size
+ * and bStride are multiples of 16 bytes).
+ * arm_dtw_init_window_q7_batch fills `batch` contiguous queryLength x templateLength windows (all alike).
+ * arm_dtw_distance_f32_batch: item i is the matrix at d_distance + i * queryLength * templateLength, its cost matrix
+ * at d_dtw + the same offset (every word written), its window at d_window + i * wStride (d_window null: no window;
+ * wStride 0: one window for every item, otherwise >= queryLength * templateLength).  d_status[i] (may be null) is
+ * ARM_MATH_SUCCESS, or ARM_MATH_ARGUMENT_ERROR where no path exists inside the window; d_result[i] is written only
+ * on success.  One wave per item.
+ * arm_dtw_path_f32_batch: d_path + i * 2 * (queryLength + templateLength) receives item i's (query, template) index
+ * pairs from (0, 0) to the last cell and d_pathLength[i] their count, or 0 where the walk cannot leave a cell (the
+ * path words of such an item are unspecified).
+ * ARM_MATH_ARGUMENT_ERROR, nothing written: a null pointer (d_window and d_status excepted), a stride below the item
+ * size, a result that overlaps a source, blockSize 0 for chebyshev, a DTW length of 0 or above 32768, an unknown
+ * window type.  batch == 0 is a successful no-op, and so is arm_dtw_init_window_q7_batch with a length of 0. */
+#define MI355X_DECL_DISTANCE_F32_BATCH(NAME)                                                                     \
+  arm_status arm_##NAME##_distance_f32_batch(const float32_t *d_a, const float32_t *d_b, uint32_t bStride,       \
+                                             uint32_t blockSize, float32_t *d_result, uint32_t batch, void *stream);
+MI355X_DECL_DISTANCE_F32_BATCH(braycurtis)
+MI355X_DECL_DISTANCE_F32_BATCH(canberra)
+MI355X_DECL_DISTANCE_F32_BATCH(chebyshev)
+MI355X_DECL_DISTANCE_F32_BATCH(cityblock)
+MI355X_DECL_DISTANCE_F32_BATCH(correlation)
+MI355X_DECL_DISTANCE_F32_BATCH(cosine)
+MI355X_DECL_DISTANCE_F32_BATCH(euclidean)
+MI355X_DECL_DISTANCE_F32_BATCH(jensenshannon)
+#undef MI355X_DECL_DISTANCE_F32_BATCH
+#define MI355X_DECL_DISTANCE_BOOL_BATCH(NAME)                                                                    \
+  arm_status arm_##NAME##_distance_batch(const uint32_t *d_a, const uint32_t *d_b, uint32_t bStride,             \
+                                         uint32_t numberOfBools, float32_t *d_result, uint32_t batch, void *stream);
+MI355X_DECL_DISTANCE_BOOL_BATCH(dice)
+MI355X_DECL_DISTANCE_BOOL_BATCH(hamming)
+MI355X_DECL_DISTANCE_BOOL_BATCH(jaccard)
+MI355X_DECL_DISTANCE_BOOL_BATCH(kulsinski)
+MI355X_DECL_DISTANCE_BOOL_BATCH(rogerstanimoto)
+MI355X_DECL_DISTANCE_BOOL_BATCH(russellrao)
+MI355X_DECL_DISTANCE_BOOL_BATCH(sokalmichener)
+MI355X_DECL_DISTANCE_BOOL_BATCH(sokalsneath)
+MI355X_DECL_DISTANCE_BOOL_BATCH(yule)
+#undef MI355X_DECL_DISTANCE_BOOL_BATCH
+arm_status arm_dtw_init_window_q7_batch(arm_dtw_window windowType, int32_t windowSize, q7_t *d_window,
+                                        uint32_t queryLength, uint32_t templateLength, uint32_t batch, void *stream);
+arm_status arm_dtw_distance_f32_batch(const float32_t *d_distance, const q7_t *d_window, uint32_t wStride,
+                                      float32_t *d_dtw, uint32_t queryLength, uint32_t templateLength,
+                                      float32_t *d_result, int32_t *d_status, uint32_t batch, void *stream);
+arm_status arm_dtw_path_f32_batch(const float32_t *d_dtw, uint32_t queryLength, uint32_t templateLength,
+                                  int16_t *d_path, uint32_t *d_pathLength, uint32_t batch, void *stream);
+
 /* Multi-GPU complex FFT (SURVEY §8b "a multi-GPU entry point"; per item: arm_cfft_f32 /
  * _q31 / _q15, transform_functions.h:456-460).  Shard s of `nshards` is batch[s] contiguous
  * transforms at DEVICE pointer d_p1[s] on HIP device devices[s] (a device may appear in
