@@ -831,6 +831,107 @@ def arm_dtw_path_f32(pDTW):
     return _amd.arm_dtw_path_f32(_arr(pDTW, _np.float32)).reshape(-1)
 
 
+# ------------------------------------------------------------------ vexp / vlog, log-domain statistics, SVM, Bayes
+def arm_vexp_f32(pSrc):
+    """cmsisdsp_fastmath.c cmsis_arm_vexp_f32 (pSrc) -> pDst; blockSize = len(pSrc)."""
+    return _amd.arm_fast_math_f32("vexp", _arr(pSrc, _np.float32))
+
+
+def arm_vlog_f32(pSrc):
+    """cmsisdsp_fastmath.c cmsis_arm_vlog_f32 (pSrc) -> pDst; blockSize = len(pSrc)."""
+    return _amd.arm_fast_math_f32("vlog", _arr(pSrc, _np.float32))
+
+
+def arm_entropy_f32(pSrc):
+    """cmsisdsp_statistics.c cmsis_arm_entropy_f32 (pSrc) -> a Python float; blockSize = len(pSrc)."""
+    return float(_amd.arm_logdom_f32("entropy", _arr(pSrc, _np.float32)))
+
+
+def arm_logsumexp_f32(pSrc):
+    """cmsisdsp_statistics.c cmsis_arm_logsumexp_f32 (pSrc) -> a Python float; blockSize = len(pSrc)."""
+    return float(_amd.arm_logdom_f32("logsumexp", _arr(pSrc, _np.float32)))
+
+
+def arm_kullback_leibler_f32(pSrcA, pSrcB):
+    """cmsisdsp_statistics.c cmsis_arm_kullback_leibler_f32 (pSrcA, pSrcB) -> a Python float; blockSize = len(pSrcA)."""
+    return float(_amd.arm_logdom_f32("kullback_leibler", _arr(pSrcA, _np.float32), _arr(pSrcB, _np.float32)))
+
+
+def arm_logsumexp_dot_prod_f32(pSrcA, pSrcB):
+    """cmsisdsp_statistics.c cmsis_arm_logsumexp_dot_prod_f32 (pSrcA, pSrcB) -> a Python float; the binding
+    allocates the scratch buffer."""
+    return float(_amd.arm_logdom_f32("logsumexp_dot_prod", _arr(pSrcA, _np.float32), _arr(pSrcB, _np.float32)))
+
+
+class _SvmInstance(_Instance):
+    """cmsisdsp_svm.c: every constructor argument is optional and may be given by keyword; the arrays are copied."""
+    _kind = None
+    _extra = ()
+
+    def __init__(self, nbOfSupportVectors=0, vectorDimension=0, intercept=0.0, dualCoefficients=None,
+                 supportVectors=None, classes=None, **extra):
+        super().__init__()
+        unknown = set(extra) - set(self._extra)
+        if unknown:
+            raise TypeError(f"unexpected keyword argument {sorted(unknown)[0]!r}")
+        if dualCoefficients is not None and supportVectors is not None and classes is not None:
+            _svm_fill(self, nbOfSupportVectors, vectorDimension, intercept, dualCoefficients, supportVectors, classes,
+                      [extra.get(k, 0) for k in self._extra])
+
+
+def _svm_fill(S, nbOfSupportVectors, vectorDimension, intercept, dualCoefficients, supportVectors, classes, extra):
+    nsv, dim = int(nbOfSupportVectors), int(vectorDimension)
+    dual = _arr(dualCoefficients, _np.float32).reshape(-1)[:nsv]
+    vectors = _arr(supportVectors, _np.float32).reshape(-1)[:nsv * dim].reshape(nsv, dim)
+    names = dict(zip(S._extra, extra))
+    S._s, S._keep = _amd.svm_instance(S._kind, intercept, dual, vectors, _arr(classes, _np.int32).reshape(-1)[:2],
+                                      **names)
+
+
+def _svm(kind, extra):
+    inst = type(f"arm_svm_{kind}_instance_f32", (_SvmInstance,),
+                {"_struct": _abi.SVM_KINDS[kind][0], "_kind": kind, "_extra": extra})
+
+    def init(S, nbOfSupportVectors, vectorDimension, intercept, dualCoefficients, supportVectors, classes, *rest):
+        if len(rest) != len(extra):
+            raise TypeError(f"arm_svm_{kind}_init_f32 takes {7 + len(extra)} arguments")
+        _svm_fill(S, nbOfSupportVectors, vectorDimension, intercept, dualCoefficients, supportVectors, classes, rest)
+    init.__name__ = f"arm_svm_{kind}_init_f32"
+    init.__doc__ = f"cmsisdsp_svm.c cmsis_arm_svm_{kind}_init_f32 (S, nbOfSupportVectors, vectorDimension, intercept, " \
+                   f"dualCoefficients, supportVectors, classes{''.join(', ' + e for e in extra)})."
+
+    def predict(S, pSrc):
+        return _amd.arm_svm_predict_f32(kind, S._s, _arr(pSrc, _np.float32))
+    predict.__name__ = f"arm_svm_{kind}_predict_f32"
+    predict.__doc__ = f"cmsisdsp_svm.c cmsis_arm_svm_{kind}_predict_f32 (S, pSrc) -> the class, a Python int."
+    return inst, init, predict
+
+
+for _k, _e in (("linear", ()), ("polynomial", ("degree", "coef0", "gamma")), ("rbf", ("gamma",))):
+    (globals()[f"arm_svm_{_k}_instance_f32"], globals()[f"arm_svm_{_k}_init_f32"],
+     globals()[f"arm_svm_{_k}_predict_f32"]) = _svm(_k, _e)
+del _k, _e
+
+
+class arm_gaussian_naive_bayes_instance_f32(_Instance):
+    """cmsisdsp_bayes.c: (vectorDimension, numberOfClasses, theta, sigma, classPriors, epsilon), all optional and
+    accepted by keyword; the arrays are copied."""
+    _struct = _abi.arm_gaussian_naive_bayes_instance_f32
+
+    def __init__(self, vectorDimension=0, numberOfClasses=0, theta=None, sigma=None, classPriors=None, epsilon=0.0):
+        super().__init__()
+        if theta is not None and sigma is not None and classPriors is not None:
+            c, d = int(numberOfClasses), int(vectorDimension)
+            self._s, self._keep = _amd.bayes_instance(_arr(theta, _np.float32).reshape(-1)[:c * d].reshape(c, d),
+                                                      _arr(sigma, _np.float32).reshape(-1)[:c * d].reshape(c, d),
+                                                      _arr(classPriors, _np.float32).reshape(-1)[:c], epsilon)
+
+
+def arm_gaussian_naive_bayes_predict_f32(S, pSrc):
+    """cmsisdsp_bayes.c cmsis_arm_gaussian_naive_bayes_predict_f32 (S, pSrc) -> (pOutputProbabilities, index)."""
+    return _amd.arm_gaussian_naive_bayes_predict_f32(S._s, _arr(pSrc, _np.float32))
+
+
 def arm_sqrt_q15(x):
     """cmsisdsp_fastmath.c cmsis_arm_sqrt_q15 (in) -> (status, pOut)."""
     st, v = _amd.arm_sqrt_q15(x)

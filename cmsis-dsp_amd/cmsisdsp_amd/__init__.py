@@ -59,6 +59,7 @@ def _load():
     _abi.bind(lib, _abi.BASIC_MATH)
     _abi.bind(lib, _abi.SUPPORT)
     _abi.bind(lib, _abi.DISTANCE)
+    _abi.bind(lib, _abi.ML)
     _abi.bind(lib, _abi.BATCHED)
     return lib
 
@@ -1585,6 +1586,139 @@ def dtw_path_batch(dtw, path, path_length, stream=None):
     matrix dtw[i] (arm_dtw_path_f32_batch); a length of 0 marks a matrix without a path."""
     _solve_call("arm_dtw_path_f32_batch", _cm_ptr(dtw), dtw.shape[-2], dtw.shape[-1], _cm_ptr(path),
                 _cm_ptr(path_length), dtw.shape[0], _stream_ptr(stream))
+
+
+# ---- vexp / vlog, log-domain statistics, SVM, naive Bayes -----------------------------------------------------------
+arm_svm_linear_instance_f32 = _abi.arm_svm_linear_instance_f32
+arm_svm_polynomial_instance_f32 = _abi.arm_svm_polynomial_instance_f32
+arm_svm_rbf_instance_f32 = _abi.arm_svm_rbf_instance_f32
+arm_gaussian_naive_bayes_instance_f32 = _abi.arm_gaussian_naive_bayes_instance_f32
+SVM_KINDS = tuple(_abi.SVM_KINDS)
+LOGDOM_FUNCS = ("entropy", "kullback_leibler", "logsumexp", "logsumexp_dot_prod")
+
+
+def arm_fast_math_f32(name, src):
+    """arm_vexp_f32 / arm_vlog_f32 (name "vexp" / "vlog") of a float32 vector (drop-in, numpy) -> a new array."""
+    x = np.ascontiguousarray(src, dtype=np.float32).reshape(-1)
+    out = np.zeros_like(x)
+    getattr(lib, f"arm_{name}_f32")(x.ctypes.data, out.ctypes.data, x.size)
+    _check_void(f"arm_{name}_f32")
+    return out
+
+
+def arm_logdom_f32(name, a, b=None):
+    """arm_<name>_f32 (name in LOGDOM_FUNCS; drop-in, numpy) -> np.float32.  b: the second vector of kullback_leibler
+    and logsumexp_dot_prod, whose scratch buffer is allocated here."""
+    fn = f"arm_{name}_f32"
+    x = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+    if name in ("entropy", "logsumexp"):
+        r = getattr(lib, fn)(x.ctypes.data, x.size)
+    else:
+        y = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+        if x.size != y.size:
+            raise ValueError(f"{fn}: {x.size} and {y.size} words")
+        if name == "kullback_leibler":
+            r = lib.arm_kullback_leibler_f32(x.ctypes.data, y.ctypes.data, x.size)
+        else:
+            tmp = np.zeros(max(1, x.size), dtype=np.float32)
+            r = lib.arm_logsumexp_dot_prod_f32(x.ctypes.data, y.ctypes.data, x.size, tmp.ctypes.data)
+    _check_void(fn)
+    return np.float32(r)
+
+
+def svm_instance(kind, intercept, dual, vectors, classes, degree=0, coef0=0.0, gamma=0.0):
+    """(instance, keep): an arm_svm_<kind>_instance_f32 filled by arm_svm_<kind>_init_f32 over dual [nSV], vectors
+    [nSV, dim] and classes [2]: float32 / int32 numpy arrays (a drop-in model) or device tensors (a model for
+    svm_predict_batch).  keep holds the arrays the instance points into."""
+    inst, _ = _abi.SVM_KINDS[kind]
+    S = inst()
+    if hasattr(dual, "data_ptr"):
+        keep = [dual.contiguous(), vectors.contiguous(), classes.contiguous()]
+        ptrs = [k.data_ptr() for k in keep]
+    else:
+        keep = [np.ascontiguousarray(dual, dtype=np.float32), np.ascontiguousarray(vectors, dtype=np.float32),
+                np.ascontiguousarray(classes, dtype=np.int32)]
+        ptrs = [k.ctypes.data for k in keep]
+    nsv = int(keep[0].shape[0])
+    dim = int(keep[1].shape[-1]) if len(keep[1].shape) > 1 else 0
+    extra = {"linear": [], "polynomial": [int(degree), float(coef0), float(gamma)], "rbf": [float(gamma)]}[kind]
+    getattr(lib, f"arm_svm_{kind}_init_f32")(C.byref(S), nsv, dim, float(intercept), *ptrs, *extra)   # fills S only
+    return S, keep
+
+
+def arm_svm_predict_f32(kind, S, x):
+    """arm_svm_<kind>_predict_f32 of one float32 vector against a host model (drop-in, numpy) -> the class (int)."""
+    v = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    if v.size != S.vectorDimension:
+        raise ValueError(f"arm_svm_{kind}_predict_f32: {v.size} words for dimension {S.vectorDimension}")
+    out = np.zeros(1, dtype=np.int32)
+    getattr(lib, f"arm_svm_{kind}_predict_f32")(C.byref(S), v.ctypes.data, out.ctypes.data)
+    _check_void(f"arm_svm_{kind}_predict_f32")
+    return int(out[0])
+
+
+def bayes_instance(theta, sigma, priors, epsilon):
+    """(instance, keep): an arm_gaussian_naive_bayes_instance_f32 over theta, sigma [classes, dim] and priors
+    [classes]: float32 numpy arrays or device tensors."""
+    S = arm_gaussian_naive_bayes_instance_f32()
+    if hasattr(theta, "data_ptr"):
+        keep = [theta.contiguous(), sigma.contiguous(), priors.contiguous()]
+        ptrs = [k.data_ptr() for k in keep]
+    else:
+        keep = [np.ascontiguousarray(a, dtype=np.float32) for a in (theta, sigma, priors)]
+        ptrs = [k.ctypes.data for k in keep]
+    S.numberOfClasses = int(keep[2].shape[0])
+    S.vectorDimension = int(keep[0].shape[-1]) if len(keep[0].shape) > 1 else 0
+    S.theta, S.sigma, S.classPriors = ptrs
+    S.epsilon = float(epsilon)
+    return S, keep
+
+
+def arm_gaussian_naive_bayes_predict_f32(S, x):
+    """(the classes' words [numberOfClasses], the class index) through arm_gaussian_naive_bayes_predict_f32."""
+    v = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    if v.size != S.vectorDimension:
+        raise ValueError(f"arm_gaussian_naive_bayes_predict_f32: {v.size} words for dimension {S.vectorDimension}")
+    prob = np.zeros(S.numberOfClasses, dtype=np.float32)
+    idx = lib.arm_gaussian_naive_bayes_predict_f32(C.byref(S), v.ctypes.data, prob.ctypes.data, None)
+    _check_void("arm_gaussian_naive_bayes_predict_f32")
+    return prob, int(idx)
+
+
+def fast_math_batch(name, src, dst, stream=None):
+    """dst = expf(src) (name "vexp") or logf(src) ("vlog") for contiguous float32 device tensors of one shape
+    (arm_vexp_f32_batch / arm_vlog_f32_batch).  dst may be src."""
+    n = src.shape[-1] if src.dim() else 1
+    _solve_call(f"arm_{name}_f32_batch", _cm_ptr(src), _cm_ptr(dst), n, src.numel() // n if n else 0,
+                _stream_ptr(stream))
+
+
+def logdom_batch(name, a, b, result, stream=None, b_stride=None):
+    """result[i] = arm_<name>_f32 (name in LOGDOM_FUNCS) of a[i] (and b_i) for float32 device tensors a [batch, N],
+    result [batch]; b: None for entropy and logsumexp, otherwise [N] (one vector for every item) or [batch, N].
+    b_stride (words) overrides the distance between the items' b vectors."""
+    if name in ("entropy", "logsumexp"):
+        _solve_call(f"arm_{name}_f32_batch", _cm_ptr(a), a.shape[-1], _cm_ptr(result), a.shape[0], _stream_ptr(stream))
+        return
+    if b_stride is None:
+        b_stride = 0 if b.dim() == 1 else b.shape[-1]
+    _solve_call(f"arm_{name}_f32_batch", _cm_ptr(a), _cm_ptr(b), int(b_stride), a.shape[-1], _cm_ptr(result),
+                a.shape[0], _stream_ptr(stream))
+
+
+def svm_predict_batch(kind, S, x, result, decision=None, stream=None):
+    """result[i] (int32 [items]) = the class of x[i] (float32 [items, dim]) under the device model S (svm_instance over
+    device tensors); decision (float32 [items] or None) receives the sums the classes were taken from
+    (arm_svm_<kind>_predict_f32_batch)."""
+    _solve_call(f"arm_svm_{kind}_predict_f32_batch", C.byref(S), _cm_ptr(x), _cm_ptr(result),
+                C.c_void_p(None if decision is None else decision.data_ptr()), x.shape[0], _stream_ptr(stream))
+
+
+def bayes_predict_batch(S, x, probabilities, classes, stream=None):
+    """probabilities[i] (float32 [items, numberOfClasses]) and classes[i] (int32 [items]) of x[i] (float32 [items,
+    dim]) under the device model S (arm_gaussian_naive_bayes_predict_f32_batch)."""
+    _solve_call("arm_gaussian_naive_bayes_predict_f32_batch", C.byref(S), _cm_ptr(x), _cm_ptr(probabilities),
+                _cm_ptr(classes), x.shape[0], _stream_ptr(stream))
 
 
 def mat_mult_batch(a, b, c, stream=None, fast=False):

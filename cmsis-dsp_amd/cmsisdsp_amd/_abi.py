@@ -495,6 +495,61 @@ DISTANCE["arm_dtw_distance_f32_batch"] = (C.c_int, [_vp, _vp, _u32, _vp, _u32, _
 DISTANCE["arm_dtw_path_f32"] = (None, [P(arm_matrix_instance_f32), _vp, _vp])
 DISTANCE["arm_dtw_path_f32_batch"] = (C.c_int, [_vp, _u32, _u32, _vp, _vp, _u32, _vp])
 
+# vexp / vlog, the log-domain statistics, the SVMs and naive Bayes: 10 drop-ins with their _batch forms and the three
+# SVM inits.  The product only (tests/golden/ml.npz holds the reference's outputs).
+class arm_svm_linear_instance_f32(C.Structure):
+    # Include/dsp/svm_functions.h:80-88
+    _fields_ = [("nbOfSupportVectors", C.c_uint32), ("vectorDimension", C.c_uint32), ("intercept", C.c_float),
+                ("dualCoefficients", C.c_void_p), ("supportVectors", C.c_void_p), ("classes", C.c_void_p)]
+
+
+class arm_svm_polynomial_instance_f32(C.Structure):
+    # Include/dsp/svm_functions.h:94-105
+    _fields_ = arm_svm_linear_instance_f32._fields_ + [("degree", C.c_int32), ("coef0", C.c_float),
+                                                       ("gamma", C.c_float)]
+
+
+class arm_svm_rbf_instance_f32(C.Structure):
+    # Include/dsp/svm_functions.h:111-120
+    _fields_ = arm_svm_linear_instance_f32._fields_ + [("gamma", C.c_float)]
+
+
+class arm_svm_sigmoid_instance_f32(C.Structure):
+    # Include/dsp/svm_functions.h:126-136 (the type only: arm_svm_sigmoid_* are left out)
+    _fields_ = arm_svm_linear_instance_f32._fields_ + [("coef0", C.c_float), ("gamma", C.c_float)]
+
+
+class arm_gaussian_naive_bayes_instance_f32(C.Structure):
+    # Include/dsp/bayes_functions.h:57-65
+    _fields_ = [("vectorDimension", C.c_uint32), ("numberOfClasses", C.c_uint32), ("theta", C.c_void_p),
+                ("sigma", C.c_void_p), ("classPriors", C.c_void_p), ("epsilon", C.c_float)]
+
+
+SVM_KINDS = {"linear": (arm_svm_linear_instance_f32, []),
+             "polynomial": (arm_svm_polynomial_instance_f32, [C.c_int32, C.c_float, C.c_float]),
+             "rbf": (arm_svm_rbf_instance_f32, [C.c_float])}
+ML = {
+    "arm_vexp_f32": (None, [_vp, _vp, _u32]),
+    "arm_vlog_f32": (None, [_vp, _vp, _u32]),
+    "arm_vexp_f32_batch": (C.c_int, [_vp, _vp, _u32, _u32, _vp]),
+    "arm_vlog_f32_batch": (C.c_int, [_vp, _vp, _u32, _u32, _vp]),
+    "arm_entropy_f32": (C.c_float, [_vp, _u32]),
+    "arm_logsumexp_f32": (C.c_float, [_vp, _u32]),
+    "arm_kullback_leibler_f32": (C.c_float, [_vp, _vp, _u32]),
+    "arm_logsumexp_dot_prod_f32": (C.c_float, [_vp, _vp, _u32, _vp]),
+    "arm_entropy_f32_batch": (C.c_int, [_vp, _u32, _vp, _u32, _vp]),
+    "arm_logsumexp_f32_batch": (C.c_int, [_vp, _u32, _vp, _u32, _vp]),
+    "arm_kullback_leibler_f32_batch": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp]),
+    "arm_logsumexp_dot_prod_f32_batch": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp]),
+    "arm_gaussian_naive_bayes_predict_f32": (C.c_uint32, [P(arm_gaussian_naive_bayes_instance_f32), _vp, _vp, _vp]),
+    "arm_gaussian_naive_bayes_predict_f32_batch": (C.c_int, [P(arm_gaussian_naive_bayes_instance_f32), _vp, _vp, _vp,
+                                                             _u32, _vp]),
+}
+for _k, (_inst, _extra) in SVM_KINDS.items():
+    ML[f"arm_svm_{_k}_init_f32"] = (None, [P(_inst), _u32, _u32, C.c_float, _vp, _vp, _vp] + _extra)
+    ML[f"arm_svm_{_k}_predict_f32"] = (None, [P(_inst), _vp, _vp])
+    ML[f"arm_svm_{_k}_predict_f32_batch"] = (C.c_int, [P(_inst), _vp, _vp, _vp, _u32, _vp])
+
 # per-length MFCC init functions (the product and the reference build; the oracle has the
 # generic init only)
 MFCC_LEN = {f"arm_mfcc_init_{n}_f32": (C.c_int, [P(arm_mfcc_instance_f32), C.c_uint32, C.c_uint32, C.c_void_p,

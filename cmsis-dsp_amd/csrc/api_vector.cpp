@@ -29,7 +29,7 @@ namespace {
 //     `what`.  The matrix functions and the solves have no overlap rule (kNoOverlapRule).
 enum : unsigned { kIn = 1, kOut = 2, kExactOk = 4 };        // Operand::role: a source, a result, or both
 enum : unsigned { kNoOverlapRule = 1, kQuietNull = 2 };     // VecCall::flags
-constexpr int kMaxOperands = 5;
+constexpr int kMaxOperands = 6;
 
 // One operand of a call: its byte span over the whole call.  A sync call copies a host source in (a span without
 // words is not copied) and a host result out.
@@ -1121,5 +1121,223 @@ arm_status arm_dtw_path_f32_batch(const float32_t* d_dtw, uint32_t queryLength, 
                                   int16_t* d_path, uint32_t* d_pathLength, uint32_t batch, void* stream) {
   return ds_dtw_path(d_dtw, queryLength, templateLength, d_path, d_pathLength, false, batch, stream,
                      "arm_dtw_path_f32_batch");
+}
+}  // extern "C"
+
+// ---- vexp / vlog, log-domain statistics, SVM, naive Bayes (ml.hip) ------------------------------------
+// fast_math_functions.h (arm_vexp_f32, arm_vlog_f32), statistics_functions.h (entropy, kullback_leibler, logsumexp,
+// logsumexp_dot_prod), svm_functions.h and bayes_functions.h.  The two logsumexp forms read element 0 and refuse
+// blockSize == 0; entropy and kullback_leibler return the -0.0f of their empty sums.  A drop-in that returns a float
+// returns a NaN on a failure, arm_gaussian_naive_bayes_predict_f32 returns UINT32_MAX; both set the last error.
+namespace {
+arm_status ml_ew(int op, const float* src, float* dst, uint32_t n, bool sync, uint32_t batch, void* stream,
+                 const char* what) {
+  const size_t count = (size_t)n * batch, bytes = sizeof(float) * count;
+  const VecCall c{what, sync, stream, 0, 2, {{src, bytes, kIn | kExactOk}, {dst, bytes, kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (count == 0) return ARM_MATH_SUCCESS;
+  return c.run([&](void* const* p, hipStream_t st) {
+    return fast_math_launch(op, (const float*)p[0], (float*)p[1], count, st);
+  });
+}
+
+// entropy and logsumexp: one source
+arm_status ml_logdom_1(int op, const float* a, uint32_t n, float* result, bool sync, uint32_t batch, void* stream,
+                       const char* what) {
+  const VecCall c{what, sync, stream, 0, 2, {{a, sizeof(float) * n * batch, kIn}, {result, sizeof(float) * batch, kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (op == kLdLogsumexp && n == 0) return refuse(sync, what);
+  if (batch == 0) return ARM_MATH_SUCCESS;
+  return c.run([&](void* const* p, hipStream_t st) {
+    return logdom_launch(op, (const float*)p[0], nullptr, 0, n, (float*)p[1], batch, nullptr, st);
+  });
+}
+
+// kullback_leibler and the batched logsumexp_dot_prod: two sources, the second at a stride
+arm_status ml_logdom_2(int op, const float* a, const float* b, uint32_t bStride, uint32_t n, float* result, bool sync,
+                       uint32_t batch, void* stream, const char* what) {
+  if (op == kLdLogsumexpDot && n == 0) return refuse(sync, what);
+  return strided_reduce(1, a, b, bStride, n, result, (float*)nullptr, sync, batch, stream, what,
+                        [&](const float* da, const float* db, float* dr, float*, hipStream_t st) {
+                          return logdom_launch(op, da, db, bStride, n, dr, batch, nullptr, st);
+                        });
+}
+
+// The drop-in of logsumexp_dot_prod: pTmpBuffer receives a + b.
+arm_status ml_logsumexp_dot_sync(const float* a, const float* b, uint32_t n, float* tmp, float* result,
+                                 const char* what) {
+  const size_t sb = sizeof(float) * n;
+  const VecCall c{what, true, nullptr, 0, 4, {{a, sb, kIn}, {b, sb, kIn}, {tmp, sb, kOut}, {result, sizeof(float), kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (n == 0) return refuse(true, what);
+  return c.run([&](void* const* p, hipStream_t st) {
+    return logdom_launch(kLdLogsumexpDot, (const float*)p[0], (const float*)p[1], n, n, (float*)p[3], 1, (float*)p[2], st);
+  });
+}
+
+// m's arrays are host or device pointers in a drop-in and device pointers in a batched call.  decision may be null.
+arm_status ml_svm(int kind, SvmModel m, const float* in, int32_t* result, float* decision, bool sync, uint32_t items,
+                  void* stream, const char* what) {
+  const size_t nsv = m.nsv, dim = m.dim;
+  const VecCall c{what, sync, stream, 0, decision ? 6 : 5,
+                  {{m.dual, sizeof(float) * nsv, kIn}, {m.sv, sizeof(float) * nsv * dim, kIn},
+                   {m.classes, 2 * sizeof(int32_t), kIn}, {in, sizeof(float) * dim * items, kIn},
+                   {result, sizeof(int32_t) * items, kOut}, {decision, sizeof(float) * items, kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (nsv * dim > 0xffffffffull) return refuse(sync, what);
+  if (items == 0) return ARM_MATH_SUCCESS;
+  return c.run([&](void* const* p, hipStream_t st) {
+    m.dual = (const float*)p[0];
+    m.sv = (const float*)p[1];
+    m.classes = (const int32_t*)p[2];
+    return svm_predict_launch(kind, m, (const float*)p[3], (int32_t*)p[4], (float*)p[5], items, st);
+  });
+}
+
+arm_status ml_bayes(const arm_gaussian_naive_bayes_instance_f32* S, const float* in, float* prob, uint32_t* cls,
+                    bool sync, uint32_t items, void* stream, const char* what) {
+  if (!S) return refuse(sync, what);
+  const size_t C = S->numberOfClasses, D = S->vectorDimension;
+  BayesModel m{S->vectorDimension, S->numberOfClasses, S->theta, S->sigma, S->classPriors, S->epsilon};
+  const VecCall c{what, sync, stream, 0, 6,
+                  {{m.theta, sizeof(float) * C * D, kIn}, {m.sigma, sizeof(float) * C * D, kIn},
+                   {m.priors, sizeof(float) * C, kIn}, {in, sizeof(float) * D * items, kIn},
+                   {prob, sizeof(float) * C * items, kOut}, {cls, sizeof(uint32_t) * items, kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (C == 0 || C * D > 0xffffffffull) return refuse(sync, what);
+  if (items == 0) return ARM_MATH_SUCCESS;
+  return c.run([&](void* const* p, hipStream_t st) {
+    m.theta = (const float*)p[0];
+    m.sigma = (const float*)p[1];
+    m.priors = (const float*)p[2];
+    return bayes_predict_launch(m, (const float*)p[3], (float*)p[4], (uint32_t*)p[5], items, st);
+  });
+}
+
+SvmModel svm_model(const arm_svm_linear_instance_f32* S) {
+  return {S->nbOfSupportVectors, S->vectorDimension, S->intercept, S->dualCoefficients, S->supportVectors, S->classes,
+          0, 0.0f, 0.0f};
+}
+SvmModel svm_model(const arm_svm_polynomial_instance_f32* S) {
+  return {S->nbOfSupportVectors, S->vectorDimension, S->intercept, S->dualCoefficients, S->supportVectors, S->classes,
+          S->degree, S->coef0, S->gamma};
+}
+SvmModel svm_model(const arm_svm_rbf_instance_f32* S) {
+  return {S->nbOfSupportVectors, S->vectorDimension, S->intercept, S->dualCoefficients, S->supportVectors, S->classes,
+          0, 0.0f, S->gamma};
+}
+}  // namespace
+
+extern "C" {
+#define MI355X_ML_EW(NAME, OP)                                                                                   \
+  void arm_##NAME##_f32(const float32_t* pSrc, float32_t* pDst, uint32_t blockSize) {                            \
+    ml_ew(OP, pSrc, pDst, blockSize, true, 1, nullptr, "arm_" #NAME "_f32");                                     \
+  }                                                                                                              \
+  arm_status arm_##NAME##_f32_batch(const float32_t* d_src, float32_t* d_dst, uint32_t blockSize, uint32_t batch, \
+                                    void* stream) {                                                              \
+    return ml_ew(OP, d_src, d_dst, blockSize, false, batch, stream, "arm_" #NAME "_f32_batch");                  \
+  }
+MI355X_ML_EW(vexp, kFmExp)
+MI355X_ML_EW(vlog, kFmLog)
+#undef MI355X_ML_EW
+
+float32_t arm_entropy_f32(const float32_t* pSrcA, uint32_t blockSize) {
+  float32_t r = 0.0f;
+  if (ml_logdom_1(kLdEntropy, pSrcA, blockSize, &r, true, 1, nullptr, "arm_entropy_f32") != ARM_MATH_SUCCESS)
+    return __builtin_nanf("");
+  return r;
+}
+float32_t arm_logsumexp_f32(const float32_t* in, uint32_t blockSize) {
+  float32_t r = 0.0f;
+  if (ml_logdom_1(kLdLogsumexp, in, blockSize, &r, true, 1, nullptr, "arm_logsumexp_f32") != ARM_MATH_SUCCESS)
+    return __builtin_nanf("");
+  return r;
+}
+float32_t arm_kullback_leibler_f32(const float32_t* pSrcA, const float32_t* pSrcB, uint32_t blockSize) {
+  float32_t r = 0.0f;
+  if (ml_logdom_2(kLdKullbackLeibler, pSrcA, pSrcB, blockSize, blockSize, &r, true, 1, nullptr,
+                  "arm_kullback_leibler_f32") != ARM_MATH_SUCCESS)
+    return __builtin_nanf("");
+  return r;
+}
+float32_t arm_logsumexp_dot_prod_f32(const float32_t* pSrcA, const float32_t* pSrcB, uint32_t blockSize,
+                                     float32_t* pTmpBuffer) {
+  float32_t r = 0.0f;
+  if (ml_logsumexp_dot_sync(pSrcA, pSrcB, blockSize, pTmpBuffer, &r, "arm_logsumexp_dot_prod_f32") != ARM_MATH_SUCCESS)
+    return __builtin_nanf("");
+  return r;
+}
+arm_status arm_entropy_f32_batch(const float32_t* d_src, uint32_t blockSize, float32_t* d_result, uint32_t batch,
+                                 void* stream) {
+  return ml_logdom_1(kLdEntropy, d_src, blockSize, d_result, false, batch, stream, "arm_entropy_f32_batch");
+}
+arm_status arm_logsumexp_f32_batch(const float32_t* d_src, uint32_t blockSize, float32_t* d_result, uint32_t batch,
+                                   void* stream) {
+  return ml_logdom_1(kLdLogsumexp, d_src, blockSize, d_result, false, batch, stream, "arm_logsumexp_f32_batch");
+}
+arm_status arm_kullback_leibler_f32_batch(const float32_t* d_a, const float32_t* d_b, uint32_t bStride,
+                                          uint32_t blockSize, float32_t* d_result, uint32_t batch, void* stream) {
+  return ml_logdom_2(kLdKullbackLeibler, d_a, d_b, bStride, blockSize, d_result, false, batch, stream,
+                     "arm_kullback_leibler_f32_batch");
+}
+arm_status arm_logsumexp_dot_prod_f32_batch(const float32_t* d_a, const float32_t* d_b, uint32_t bStride,
+                                            uint32_t blockSize, float32_t* d_result, uint32_t batch, void* stream) {
+  return ml_logdom_2(kLdLogsumexpDot, d_a, d_b, bStride, blockSize, d_result, false, batch, stream,
+                     "arm_logsumexp_dot_prod_f32_batch");
+}
+
+void arm_svm_linear_init_f32(arm_svm_linear_instance_f32* S, uint32_t nbOfSupportVectors, uint32_t vectorDimension,
+                             float32_t intercept, const float32_t* dualCoefficients, const float32_t* supportVectors,
+                             const int32_t* classes) {
+  if (!S) { refuse(true, "arm_svm_linear_init_f32"); return; }
+  *S = {nbOfSupportVectors, vectorDimension, intercept, dualCoefficients, supportVectors, classes};
+}
+void arm_svm_polynomial_init_f32(arm_svm_polynomial_instance_f32* S, uint32_t nbOfSupportVectors,
+                                 uint32_t vectorDimension, float32_t intercept, const float32_t* dualCoefficients,
+                                 const float32_t* supportVectors, const int32_t* classes, int32_t degree,
+                                 float32_t coef0, float32_t gamma) {
+  if (!S) { refuse(true, "arm_svm_polynomial_init_f32"); return; }
+  *S = {nbOfSupportVectors, vectorDimension, intercept, dualCoefficients, supportVectors, classes, degree, coef0, gamma};
+}
+void arm_svm_rbf_init_f32(arm_svm_rbf_instance_f32* S, uint32_t nbOfSupportVectors, uint32_t vectorDimension,
+                          float32_t intercept, const float32_t* dualCoefficients, const float32_t* supportVectors,
+                          const int32_t* classes, float32_t gamma) {
+  if (!S) { refuse(true, "arm_svm_rbf_init_f32"); return; }
+  *S = {nbOfSupportVectors, vectorDimension, intercept, dualCoefficients, supportVectors, classes, gamma};
+}
+
+#define MI355X_ML_SVM(NAME, KIND)                                                                                \
+  void arm_svm_##NAME##_predict_f32(const arm_svm_##NAME##_instance_f32* S, const float32_t* in,                 \
+                                    int32_t* pResult) {                                                          \
+    const char* what = "arm_svm_" #NAME "_predict_f32";                                                          \
+    if (!S) { refuse(true, what); return; }                                                                      \
+    ml_svm(KIND, svm_model(S), in, pResult, nullptr, true, 1, nullptr, what);                                    \
+  }                                                                                                              \
+  arm_status arm_svm_##NAME##_predict_f32_batch(const arm_svm_##NAME##_instance_f32* S, const float32_t* d_in,   \
+                                                int32_t* d_result, float32_t* d_decision, uint32_t nbItems,      \
+                                                void* stream) {                                                  \
+    if (!S) return ARM_MATH_ARGUMENT_ERROR;                                                                      \
+    return ml_svm(KIND, svm_model(S), d_in, d_result, d_decision, false, nbItems, stream,                        \
+                  "arm_svm_" #NAME "_predict_f32_batch");                                                        \
+  }
+MI355X_ML_SVM(linear, kSvmLinear)
+MI355X_ML_SVM(polynomial, kSvmPolynomial)
+MI355X_ML_SVM(rbf, kSvmRbf)
+#undef MI355X_ML_SVM
+
+uint32_t arm_gaussian_naive_bayes_predict_f32(const arm_gaussian_naive_bayes_instance_f32* S, const float32_t* in,
+                                              float32_t* pOutputProbabilities, float32_t* pBufferB) {
+  (void)pBufferB;                                            // unused, as in the reference's scalar branch
+  uint32_t index = 0;
+  if (ml_bayes(S, in, pOutputProbabilities, &index, true, 1, nullptr, "arm_gaussian_naive_bayes_predict_f32") !=
+      ARM_MATH_SUCCESS)
+    return 0xffffffffu;
+  return index;
+}
+arm_status arm_gaussian_naive_bayes_predict_f32_batch(const arm_gaussian_naive_bayes_instance_f32* S,
+                                                      const float32_t* d_in, float32_t* d_probabilities,
+                                                      uint32_t* d_class, uint32_t nbItems, void* stream) {
+  return ml_bayes(S, d_in, d_probabilities, d_class, false, nbItems, stream,
+                  "arm_gaussian_naive_bayes_predict_f32_batch");
 }
 }  // extern "C"

@@ -421,4 +421,45 @@ hipError_t dtw_distance_launch(const float* dist, const int8_t* window, size_t w
 hipError_t dtw_path_launch(const float* dtw, uint32_t rows, uint32_t cols, int16_t* path, uint32_t* pathLength,
                            uint32_t batch, hipStream_t st);
 
+// vexp / vlog, the log-domain statistics, the SVMs and naive Bayes, bit-exact with the reference's scalar branches
+// and the pinned glibc's expf / logf (ml.hip).
+// d[i] = expf(a[i]) or logf(a[i]) over `count` words (the whole batch as one flat array); d may be a exactly.
+enum : int { kFmExp = 0, kFmLog = 1 };
+hipError_t fast_math_launch(int op, const float* a, float* d, size_t count, hipStream_t st);
+// result[i] = arm_entropy_f32 / arm_kullback_leibler_f32 / arm_logsumexp_f32 / arm_logsumexp_dot_prod_f32 of a + i * n
+// (and b + i * bStride: the second source of kLdKullbackLeibler and kLdLogsumexpDot; bStride 0: one b for every
+// item).  The two logsumexp forms need n > 0.  tmp (kLdLogsumexpDot only, may be null): where a + b is stored, item
+// for item (the drop-in's pTmpBuffer).
+enum : int { kLdEntropy = 0, kLdKullbackLeibler, kLdLogsumexp, kLdLogsumexpDot };
+hipError_t logdom_launch(int op, const float* a, const float* b, size_t bStride, uint32_t n, float* result,
+                         uint32_t batch, float* tmp, hipStream_t st);
+// arm_svm_<kind>_predict_f32 of the `items` vectors at in + i * dim against one model (device pointers): result[i] =
+// classes[sum <= 0 ? 0 : 1], decision[i] (may be null) = the final sum.  degree, coef0: polynomial; gamma: polynomial
+// and rbf.  svm_model_staged: whether the kernel holds the model in LDS (otherwise it reads it from global memory).
+enum : int { kSvmLinear = 0, kSvmPolynomial, kSvmRbf };
+struct SvmModel {
+  uint32_t nsv, dim;
+  float intercept;
+  const float* dual;
+  const float* sv;
+  const int32_t* classes;
+  int32_t degree;
+  float coef0, gamma;
+};
+hipError_t svm_predict_launch(int kind, const SvmModel& m, const float* in, int32_t* result, float* decision,
+                              uint32_t items, hipStream_t st);
+bool svm_model_staged(uint32_t nsv, uint32_t dim);
+// arm_gaussian_naive_bayes_predict_f32 of the `items` vectors at in + i * dim: prob + i * classes receives the
+// classes' words, cls[i] the index arm_max_f32 gives on them.  classes > 0.
+struct BayesModel {
+  uint32_t dim, classes;
+  const float* theta;
+  const float* sigma;
+  const float* priors;
+  float eps;
+};
+hipError_t bayes_predict_launch(const BayesModel& m, const float* in, float* prob, uint32_t* cls, uint32_t items,
+                                hipStream_t st);
+bool bayes_model_staged(uint32_t classes, uint32_t dim);
+
 }  // namespace mi355x

@@ -1108,8 +1108,9 @@ void arm_min_q7(const q7_t *pSrc, uint32_t blockSize, q7_t *pResult, uint32_t *p
  * max / min_no_idx_f32 their start value; every other function would divide an integer by zero or read pSrc[0]:
  * nothing is written and arm_mi355x_last_error() is set, as for a null pointer.  blockSize 1 gives 0 in var / std.
  * With device pointers a result that overlaps a source, or the index, is refused in the same way.
- * Left out: arm_entropy_f32, arm_kullback_leibler_f32, arm_logsumexp_f32, arm_logsumexp_dot_prod_f32 (they rest on
- * the host libm's expf / logf) and every f16 / f64 form. */
+ * arm_entropy_f32, arm_kullback_leibler_f32, arm_logsumexp_f32 and arm_logsumexp_dot_prod_f32 (they rest on the host
+ * libm's expf / logf) are declared further down, with the SVM and naive Bayes functions.
+ * Left out: every f16 / f64 form. */
 #define MI355X_DECL_STAT(SUF, T, PR)                                                     \
   void arm_mean_##SUF(const T *pSrc, uint32_t blockSize, T *pResult);                    \
   void arm_power_##SUF(const T *pSrc, uint32_t blockSize, PR *pResult);                  \
@@ -1289,8 +1290,8 @@ MI355X_DECL_SUPPORT_COPY(q7, q7_t)
  *             ARM_MATH_ARGUMENT_ERROR and writes nothing for an unknown window type or a length above 32768; with 0
  *             rows or 0 columns it succeeds and writes nothing, as the reference does.
  * A failure of a function that returns a float returns a NaN and sets the last error.
- * Left out: arm_minkowski_distance_f32 (the host libm's powf, as arm_entropy_f32 and its kin) and the f16 / f64
- * forms. */
+ * Left out: arm_minkowski_distance_f32 (the host libm's powf, of which there is no device restatement) and the
+ * f16 / f64 forms. */
 typedef enum {
   ARM_DTW_SAKOE_CHIBA_WINDOW = 1,
   /*ARM_DTW_ITAKURA_WINDOW = 2,*/
@@ -1324,6 +1325,100 @@ arm_status arm_dtw_init_window_q7(const arm_dtw_window windowType, const int32_t
 arm_status arm_dtw_distance_f32(const arm_matrix_instance_f32 *pDistance, const arm_matrix_instance_q7 *pWindow,
                                 arm_matrix_instance_f32 *pDTW, float32_t *distance);
 void arm_dtw_path_f32(const arm_matrix_instance_f32 *pDTW, int16_t *pPath, uint32_t *pathLength);
+
+/* arm_vexp_f32 / arm_vlog_f32 (fast_math_functions.h), arm_entropy_f32, arm_kullback_leibler_f32, arm_logsumexp_f32,
+ * arm_logsumexp_dot_prod_f32 (statistics_functions.h), the linear, polynomial and rbf SVMs (svm_functions.h) and the
+ * Gaussian naive Bayes estimator (bayes_functions.h).  Host or device pointers, synchronous.  Every result word
+ * equals the reference's scalar branches built without FMA contraction on a host whose libm is glibc 2.35: expf and
+ * logf are that libm's, restated operation for operation and proven equal on all 2^32 inputs.  NaN results are NaNs,
+ * their bits are not pinned.
+ *   vexp, vlog    element-wise; pDst may be pSrc exactly; blockSize == 0 writes nothing.
+ *   entropy       accum += p * logf(p) in element order from 0.0f, returns -accum (p == 0 gives a NaN, blockSize == 0
+ *                 gives -0.0f).  kullback_leibler: accum += pA * logf(pB / pA), returns -accum.
+ *   logsumexp     the maximum by strict > from in[0] (a NaN there stays, a later NaN never wins), accum += expf(x - max)
+ *                 in element order, returns max + logf(accum).  logsumexp_dot_prod: arm_add_f32 into pTmpBuffer
+ *                 (blockSize words, written), then logsumexp of it.  blockSize == 0 would read element 0: nothing is
+ *                 written, a NaN is returned and arm_mi355x_last_error() is set.
+ *   SVM           per support vector, in row order, dot is an ordered chain over the dimensions (linear, polynomial:
+ *                 dot + in[j] * sv[j]; rbf: dot + (in[j] - sv[j])^2), then from sum = intercept: sum += dual[i] * dot,
+ *                 dual[i] * arm_exponent_f32(gamma * dot + coef0, degree) (degree < 1 as degree 1) or dual[i] *
+ *                 expf(-gamma * dot).  *pResult = classes[sum <= 0 ? 0 : 1]: a NaN sum gives classes[1].
+ *                 nbOfSupportVectors == 0 classifies the intercept.  The init functions only fill the instance.
+ *   naive Bayes   per class, over the dimensions: sigma = S->sigma[] + epsilon, acc1 += logf((2.0f * PI_F) * sigma),
+ *                 acc2 += ((in - theta) * (in - theta)) / sigma; the class's word is (-0.5f * acc1 - 0.5f * acc2) +
+ *                 logf(prior), stored to pOutputProbabilities; the return value is arm_max_f32's index over them.
+ *                 pBufferB is not used and may be NULL.  numberOfClasses == 0, or any other failure, returns
+ *                 UINT32_MAX and sets the last error.
+ * Left out: arm_svm_sigmoid_* (the host libm's tanhf, glibc's expm1f path, which would need a restatement of its
+ * own) and the f16 / f64 forms. */
+typedef struct {
+  uint32_t nbOfSupportVectors;
+  uint32_t vectorDimension;
+  float32_t intercept;
+  const float32_t *dualCoefficients;
+  const float32_t *supportVectors;
+  const int32_t *classes;
+} arm_svm_linear_instance_f32;
+typedef struct {
+  uint32_t nbOfSupportVectors;
+  uint32_t vectorDimension;
+  float32_t intercept;
+  const float32_t *dualCoefficients;
+  const float32_t *supportVectors;
+  const int32_t *classes;
+  int32_t degree;
+  float32_t coef0;
+  float32_t gamma;
+} arm_svm_polynomial_instance_f32;
+typedef struct {
+  uint32_t nbOfSupportVectors;
+  uint32_t vectorDimension;
+  float32_t intercept;
+  const float32_t *dualCoefficients;
+  const float32_t *supportVectors;
+  const int32_t *classes;
+  float32_t gamma;
+} arm_svm_rbf_instance_f32;
+typedef struct {                       /* the type only: arm_svm_sigmoid_* are left out */
+  uint32_t nbOfSupportVectors;
+  uint32_t vectorDimension;
+  float32_t intercept;
+  const float32_t *dualCoefficients;
+  const float32_t *supportVectors;
+  const int32_t *classes;
+  float32_t coef0;
+  float32_t gamma;
+} arm_svm_sigmoid_instance_f32;
+typedef struct {
+  uint32_t vectorDimension;
+  uint32_t numberOfClasses;
+  const float32_t *theta;
+  const float32_t *sigma;
+  const float32_t *classPriors;
+  float32_t epsilon;
+} arm_gaussian_naive_bayes_instance_f32;
+void arm_vexp_f32(const float32_t *pSrc, float32_t *pDst, uint32_t blockSize);
+void arm_vlog_f32(const float32_t *pSrc, float32_t *pDst, uint32_t blockSize);
+float32_t arm_entropy_f32(const float32_t *pSrcA, uint32_t blockSize);
+float32_t arm_kullback_leibler_f32(const float32_t *pSrcA, const float32_t *pSrcB, uint32_t blockSize);
+float32_t arm_logsumexp_f32(const float32_t *in, uint32_t blockSize);
+float32_t arm_logsumexp_dot_prod_f32(const float32_t *pSrcA, const float32_t *pSrcB, uint32_t blockSize,
+                                     float32_t *pTmpBuffer);
+void arm_svm_linear_init_f32(arm_svm_linear_instance_f32 *S, uint32_t nbOfSupportVectors, uint32_t vectorDimension,
+                             float32_t intercept, const float32_t *dualCoefficients, const float32_t *supportVectors,
+                             const int32_t *classes);
+void arm_svm_polynomial_init_f32(arm_svm_polynomial_instance_f32 *S, uint32_t nbOfSupportVectors,
+                                 uint32_t vectorDimension, float32_t intercept, const float32_t *dualCoefficients,
+                                 const float32_t *supportVectors, const int32_t *classes, int32_t degree,
+                                 float32_t coef0, float32_t gamma);
+void arm_svm_rbf_init_f32(arm_svm_rbf_instance_f32 *S, uint32_t nbOfSupportVectors, uint32_t vectorDimension,
+                          float32_t intercept, const float32_t *dualCoefficients, const float32_t *supportVectors,
+                          const int32_t *classes, float32_t gamma);
+void arm_svm_linear_predict_f32(const arm_svm_linear_instance_f32 *S, const float32_t *in, int32_t *pResult);
+void arm_svm_polynomial_predict_f32(const arm_svm_polynomial_instance_f32 *S, const float32_t *in, int32_t *pResult);
+void arm_svm_rbf_predict_f32(const arm_svm_rbf_instance_f32 *S, const float32_t *in, int32_t *pResult);
+uint32_t arm_gaussian_naive_bayes_predict_f32(const arm_gaussian_naive_bayes_instance_f32 *S, const float32_t *in,
+                                              float32_t *pOutputProbabilities, float32_t *pBufferB);
 
 #ifdef __cplusplus
 }

@@ -620,6 +620,47 @@ arm_status arm_dtw_distance_f32_batch(const float32_t *d_distance, const q7_t *d
 arm_status arm_dtw_path_f32_batch(const float32_t *d_dtw, uint32_t queryLength, uint32_t templateLength,
                                   int16_t *d_path, uint32_t *d_pathLength, uint32_t batch, void *stream);
 
+/* Batched vexp / vlog, log-domain statistics, SVMs and naive Bayes (arm_math.h: "arm_vexp_f32 / arm_vlog_f32 ...").
+ * Device pointers, stream-ordered.
+ * arm_vexp_f32_batch / arm_vlog_f32_batch: blockSize * batch words; d_dst may be d_src exactly.
+ * The statistics give one word per item: d_result[i] of the blockSize words at d_src (d_a) + i * blockSize and, for
+ * kullback_leibler and logsumexp_dot_prod, d_b + i * bStride; bStride (words) 0 means one B vector for every item,
+ * otherwise bStride >= blockSize.  logsumexp_dot_prod takes no scratch: a + b is formed in registers.  Below 4096
+ * items an item gets one wave, from there on one lane.
+ * The classifiers share one model among the nbItems vectors at d_in + i * vectorDimension; the arrays of S are device
+ * pointers (S itself is host memory).  SVM: d_result[i] is the class, d_decision[i] (d_decision may be null) the
+ * final sum the class was taken from.  Bayes: d_probabilities + i * numberOfClasses receives the classes' words,
+ * d_class[i] the index.  An item's chains (one per support vector or class) run in the lanes of a group of 1 to 64
+ * lanes; the model is held in LDS where it fits 64 KiB (SVM: nbOfSupportVectors * (vectorDimension | 1) +
+ * nbOfSupportVectors words; Bayes: 2 * numberOfClasses * ((vectorDimension | 1) + 1) words) and is read from global
+ * memory otherwise.
+ * ARM_MATH_ARGUMENT_ERROR, nothing written: a null pointer (d_decision excepted), a stride below blockSize, a result
+ * that overlaps a source or another result, blockSize 0 for the logsumexp forms, numberOfClasses 0.  batch == 0 or
+ * nbItems == 0 is a successful no-op. */
+arm_status arm_vexp_f32_batch(const float32_t *d_src, float32_t *d_dst, uint32_t blockSize, uint32_t batch,
+                              void *stream);
+arm_status arm_vlog_f32_batch(const float32_t *d_src, float32_t *d_dst, uint32_t blockSize, uint32_t batch,
+                              void *stream);
+arm_status arm_entropy_f32_batch(const float32_t *d_src, uint32_t blockSize, float32_t *d_result, uint32_t batch,
+                                 void *stream);
+arm_status arm_logsumexp_f32_batch(const float32_t *d_src, uint32_t blockSize, float32_t *d_result, uint32_t batch,
+                                   void *stream);
+arm_status arm_kullback_leibler_f32_batch(const float32_t *d_a, const float32_t *d_b, uint32_t bStride,
+                                          uint32_t blockSize, float32_t *d_result, uint32_t batch, void *stream);
+arm_status arm_logsumexp_dot_prod_f32_batch(const float32_t *d_a, const float32_t *d_b, uint32_t bStride,
+                                            uint32_t blockSize, float32_t *d_result, uint32_t batch, void *stream);
+arm_status arm_svm_linear_predict_f32_batch(const arm_svm_linear_instance_f32 *S, const float32_t *d_in,
+                                            int32_t *d_result, float32_t *d_decision, uint32_t nbItems,
+                                            void *stream);
+arm_status arm_svm_polynomial_predict_f32_batch(const arm_svm_polynomial_instance_f32 *S, const float32_t *d_in,
+                                                int32_t *d_result, float32_t *d_decision, uint32_t nbItems,
+                                                void *stream);
+arm_status arm_svm_rbf_predict_f32_batch(const arm_svm_rbf_instance_f32 *S, const float32_t *d_in, int32_t *d_result,
+                                         float32_t *d_decision, uint32_t nbItems, void *stream);
+arm_status arm_gaussian_naive_bayes_predict_f32_batch(const arm_gaussian_naive_bayes_instance_f32 *S,
+                                                      const float32_t *d_in, float32_t *d_probabilities,
+                                                      uint32_t *d_class, uint32_t nbItems, void *stream);
+
 /* Multi-GPU complex FFT (SURVEY §8b "a multi-GPU entry point"; per item: arm_cfft_f32 /
  * _q31 / _q15, transform_functions.h:456-460).  Shard s of `nshards` is batch[s] contiguous
  * transforms at DEVICE pointer d_p1[s] on HIP device devices[s] (a device may appear in
