@@ -70,7 +70,7 @@ bool cfft_prepare(uint32_t n, const void* pTwiddle, const uint16_t* pBitRev, uin
   out.flags = (ifftFlag == 1u ? kIfft : 0u) | (bitReverseFlag ? kBitrev : 0u);   // arm_cfft_f32.c:1252,1282
   if (bitReverseFlag) {
     bool canon = true, ok = true;
-    out.perm = device_perm((int)n, pBitRev, bitRevLen, kind == 0 ? 0 : 1, &canon, &ok);
+    out.perm = device_perm((int)n, pBitRev, bitRevLen, kind == 0 ? 0 : 1, &canon, &ok, st);
     if (!ok) { set_error(hipErrorInvalidValue, "bit-reversal table"); return false; }
   }
   return true;
@@ -359,12 +359,17 @@ struct MfccDev {
   const uint32_t* off = nullptr;
 };
 
+// st: the call's stream.  A device-resident table is read on it and the host waits for that stream
+// alone, so the read is ordered after whatever the caller enqueued there (the table's own upload on
+// a non-blocking stream), which a null-stream copy is not (as device_split_records, runtime.cpp).
 template <typename T>
-bool host_copy(const T* p, size_t count, std::vector<T>& out) {
+bool host_copy(const T* p, size_t count, std::vector<T>& out, hipStream_t st) {
   out.resize(count);
   if (!count) return true;
   if (!p) return false;
-  if (is_device_ptr(p)) return hipMemcpy(out.data(), p, sizeof(T) * count, hipMemcpyDeviceToHost) == hipSuccess;
+  if (is_device_ptr(p))
+    return hipMemcpyAsync(out.data(), p, sizeof(T) * count, hipMemcpyDeviceToHost, st) == hipSuccess &&
+           hipStreamSynchronize(st) == hipSuccess;
   memcpy(out.data(), p, sizeof(T) * count);
   return true;
 }
@@ -382,9 +387,9 @@ struct MfccLayout {
 // a filter past it is reported under.
 template <typename T, typename Inst>
 bool mfcc_pack(const Inst* S, uint32_t bound, const char* beyond, std::vector<uint8_t>& blob,
-               std::vector<uint32_t>& pos, std::vector<uint32_t>& len, MfccLayout& lay) {
+               std::vector<uint32_t>& pos, std::vector<uint32_t>& len, MfccLayout& lay, hipStream_t st) {
   const uint32_t n = S->fftLen, nm = S->nbMelFilters, nd = S->nbDctOutputs;
-  if (!host_copy(S->filterPos, nm, pos) || !host_copy(S->filterLengths, nm, len)) {
+  if (!host_copy(S->filterPos, nm, pos, st) || !host_copy(S->filterLengths, nm, len, st)) {
     set_error(hipErrorInvalidValue, "mfcc filter tables");
     return false;
   }
@@ -405,11 +410,11 @@ bool mfcc_pack(const Inst* S, uint32_t bound, const char* beyond, std::vector<ui
   lay.end = lay.off + b_u;
   blob.assign(lay.end, 0);
   std::vector<T> tmp;
-  if (!host_copy(S->dctCoefs, (size_t)nm * nd, tmp)) { set_error(hipErrorInvalidValue, "mfcc dct"); return false; }
+  if (!host_copy(S->dctCoefs, (size_t)nm * nd, tmp, st)) { set_error(hipErrorInvalidValue, "mfcc dct"); return false; }
   memcpy(blob.data(), tmp.data(), sizeof(T) * tmp.size());
-  if (!host_copy(S->filterCoefs, (size_t)total, tmp)) { set_error(hipErrorInvalidValue, "mfcc coefs"); return false; }
+  if (!host_copy(S->filterCoefs, (size_t)total, tmp, st)) { set_error(hipErrorInvalidValue, "mfcc coefs"); return false; }
   memcpy(blob.data() + lay.coefs, tmp.data(), sizeof(T) * tmp.size());
-  if (!host_copy(S->windowCoefs, (size_t)n, tmp)) { set_error(hipErrorInvalidValue, "mfcc window"); return false; }
+  if (!host_copy(S->windowCoefs, (size_t)n, tmp, st)) { set_error(hipErrorInvalidValue, "mfcc window"); return false; }
   memcpy(blob.data() + lay.win, tmp.data(), sizeof(T) * tmp.size());
   memcpy(blob.data() + lay.pos, pos.data(), sizeof(uint32_t) * nm);
   memcpy(blob.data() + lay.len, len.data(), sizeof(uint32_t) * nm);
@@ -429,14 +434,14 @@ void mfcc_bind(MfccDev<T>& d, const uint8_t* dev, const MfccLayout& lay) {
   d.off = (const uint32_t*)(dev + lay.off);
 }
 
-bool mfcc_prepare(const arm_mfcc_instance_f32* S, MfccDev<float>& d) {
+bool mfcc_prepare(const arm_mfcc_instance_f32* S, MfccDev<float>& d, hipStream_t st) {
   const uint32_t n = S->fftLen, nm = S->nbMelFilters;
   if (!rfft_len_ok(n) || S->rfft.fftLenRFFT != n) { set_error(hipErrorInvalidValue, "mfcc instance"); return false; }
   if (mfcc_f32_post_lds((int)n, (int)nm) > 65536) { set_error(hipErrorInvalidValue, "mfcc: too many Mel filters"); return false; }
   std::vector<uint8_t> blob;
   std::vector<uint32_t> pos, len;
   MfccLayout lay;
-  if (!mfcc_pack<float>(S, n, "mfcc filter beyond fftLen", blob, pos, len, lay)) return false;
+  if (!mfcc_pack<float>(S, n, "mfcc filter beyond fftLen", blob, pos, len, lay, st)) return false;
   blob.resize(lay.end + 16, 0);
   const uint8_t* dev = (const uint8_t*)device_blob(blob.data(), blob.size());
   if (!dev) return false;
@@ -454,7 +459,7 @@ bool mfcc_run(const arm_mfcc_instance_f32* S, const MfccDev<float>& d, float* x,
   const arm_cfft_instance_f32& in = S->rfft.Sint;
   BlobScope hold(st);
   bool canon = true, ok = true;
-  if (in.pBitRevTable) (void)device_perm((int)in.fftLen, in.pBitRevTable, in.bitRevLength, 0, &canon, &ok);
+  if (in.pBitRevTable) (void)device_perm((int)in.fftLen, in.pBitRevTable, in.bitRevLength, 0, &canon, &ok, st);
   if (ok && canon && nm <= n / 2 && in.fftLen == (uint32_t)n / 2) {
     const void* tw = device_table(in.pTwiddle, 8u * in.fftLen);
     const void* twr = device_table(S->rfft.pTwiddleRFFT, sizeof(float) * n);
@@ -486,7 +491,7 @@ struct MfccFxDev : MfccDev<T> {
 // the blob: mfcc_pack's parts, then [bf | split twiddle records] (the records' packing is what
 // mfcc_fixed_post.hpp reads)
 template <typename T, typename Inst>
-bool mfcc_prepare(const Inst* S, MfccFxDev<T>& d) {
+bool mfcc_prepare(const Inst* S, MfccFxDev<T>& d, hipStream_t st) {
   const uint32_t n = S->fftLen, nm = S->nbMelFilters;
   if (!rfft_len_ok(n) || S->rfft.fftLenReal != n || S->rfft.ifftFlagR != 0) {
     set_error(hipErrorInvalidValue, "mfcc q31 instance");
@@ -496,7 +501,7 @@ bool mfcc_prepare(const Inst* S, MfccFxDev<T>& d) {
   std::vector<uint8_t> blob;
   std::vector<uint32_t> pos, len;
   MfccLayout lay;
-  if (!mfcc_pack<T>(S, n / 2 + 1, "mfcc q31 filter beyond fftLen/2", blob, pos, len, lay)) return false;
+  if (!mfcc_pack<T>(S, n / 2 + 1, "mfcc q31 filter beyond fftLen/2", blob, pos, len, lay, st)) return false;
   const uint64_t total = lay.total;
   if (nm > 0xFFFFu || total > 0x7FFFFFFFull) { set_error(hipErrorInvalidValue, "mfcc: too many Mel coefficients"); return false; }
   {
@@ -514,7 +519,7 @@ bool mfcc_prepare(const Inst* S, MfccFxDev<T>& d) {
   {   // the split's twiddle records (arm_rfft_q31.c:293-326 index 2 * modifier * k)
     const uint32_t mod = S->rfft.twidCoefRModifier, words = mod * n;
     std::vector<T> ta, tb;
-    if (!host_copy(S->rfft.pTwiddleAReal, words, ta) || !host_copy(S->rfft.pTwiddleBReal, words, tb)) {
+    if (!host_copy(S->rfft.pTwiddleAReal, words, ta, st) || !host_copy(S->rfft.pTwiddleBReal, words, tb, st)) {
       set_error(hipErrorInvalidValue, "mfcc rfft tables");
       return false;
     }
@@ -1307,7 +1312,7 @@ arm_status mfcc_sync(const Inst* S, T* pSrc, T* pDst, const char* what) {
   hipStream_t st = sync_stream();
   BlobScope hold(st);
   Dev d;
-  if (!mfcc_prepare(S, d)) return ARM_MATH_ARGUMENT_ERROR;
+  if (!mfcc_prepare(S, d, st)) return ARM_MATH_ARGUMENT_ERROR;
   const uint32_t n = S->fftLen, nd = S->nbDctOutputs;
   T* x = (T*)scratch(sizeof(T) * n, 0);
   T* y = (T*)scratch(sizeof(T) * 2 * n, 1);
@@ -1330,7 +1335,7 @@ arm_status mfcc_batch(const Inst* S, T* d_src, T* d_dst, T* d_tmp, uint32_t batc
   if (batch == 0 || S->nbDctOutputs == 0) return ARM_MATH_SUCCESS;
   BlobScope hold((hipStream_t)stream);
   Dev d;
-  if (!mfcc_prepare(S, d)) return ARM_MATH_ARGUMENT_ERROR;
+  if (!mfcc_prepare(S, d, (hipStream_t)stream)) return ARM_MATH_ARGUMENT_ERROR;
   return mfcc_run(S, d, d_src, d_tmp, d_dst, batch, (hipStream_t)stream) ? ARM_MATH_SUCCESS : ARM_MATH_ARGUMENT_ERROR;
 }
 }  // namespace

@@ -536,7 +536,8 @@ BlobScope::~BlobScope() {
   release_blobs(victims);
 }
 
-const uint16_t* device_perm(int n, const uint16_t* table, uint16_t len, int kind, bool* canonical, bool* ok) {
+const uint16_t* device_perm(int n, const uint16_t* table, uint16_t len, int kind, bool* canonical, bool* ok,
+                            hipStream_t st) {
   *ok = true;
   *canonical = true;
   if (!table) { return nullptr; }
@@ -564,7 +565,12 @@ const uint16_t* device_perm(int n, const uint16_t* table, uint16_t len, int kind
     std::vector<uint16_t> tmp;
     if (is_device_ptr(table)) {
       tmp.resize(len);
-      if (hipMemcpy(tmp.data(), table, len * sizeof(uint16_t), hipMemcpyDeviceToHost) != hipSuccess) { *ok = false; return nullptr; }
+      // on the call's stream, as device_split_records: ordered after the caller's own upload of the table
+      if (hipMemcpyAsync(tmp.data(), table, len * sizeof(uint16_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+          hipStreamSynchronize(st) != hipSuccess) {
+        *ok = false;
+        return nullptr;
+      }
       host = tmp.data();
     }
     a.resize(n);

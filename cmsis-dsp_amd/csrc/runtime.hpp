@@ -76,8 +76,10 @@ class BlobScope {
 // Device permutation implementing a bit-reversal swap table of a non-canonical instance.
 // *canonical is set when the table induces the reference's own permutation (then the
 // kernels compute it on the fly and nullptr is returned).  kind: 0 = f32 tables
-// (mixed-radix digit reversal), 1 = fixed-point tables (binary bit reversal).
-const uint16_t* device_perm(int n, const uint16_t* table, uint16_t len, int kind, bool* canonical, bool* ok);
+// (mixed-radix digit reversal), 1 = fixed-point tables (binary bit reversal).  st: the call's
+// stream; a device-resident table is read on it and the host waits for that stream.
+const uint16_t* device_perm(int n, const uint16_t* table, uint16_t len, int kind, bool* canonical, bool* ok,
+                            hipStream_t st);
 
 // Per-thread device scratch for the synchronous host-pointer path (grown on demand).
 void* scratch(size_t bytes, int slot);
