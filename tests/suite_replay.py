@@ -1,0 +1,1522 @@
+"""The reference's own test suites (Testing/Source/Tests/*.cpp, driven by Testing/desc.txt), restated as one table.
+
+A row is one `Test` line of a suite: the patterns its setUp case loads (and how many samples of each), the scalars it
+sets, the call its test method makes, and the ASSERT_* lines of that method with the suite's own thresholds
+(tests/metrics.py).  run_row() replays a row against a "library": any object whose arm_* attributes take host numpy
+buffers (a pointer argument is a contiguous array, written in place when it is an output) and C scalars, in the order
+of arm_math.h.  Three libraries exist: the reference build (tools/make_golden_suites.py), the numpy restatements
+(RestatementLibrary, tests/test_suites.py) and the GPU drop-ins (CtypesLibrary over cmsisdsp_amd.lib,
+tests/test_gpu_suites.py).
+
+Patterns are data: tests/golden/suites_<family>.npz, keyed <SuiteClass>/<pattern file stem>, extracted by
+tools/make_golden_suites.py together with the reference build's output words (<SuiteClass>/<NN>_<method>/<label>/
+ref_words) and tests/golden/suites_manifest.json, one entry per `Test` line.
+
+The framework's buffers (Testing/FrameworkSource/ArrayMemory.cpp:69-138) are followed by a 16-byte tail that
+ASSERT_EMPTY_TAIL wants untouched; here an output buffer is followed by TAIL marker words (at least 16 bytes for every
+type), and the marker is not zero, so that a stray zero shows as well."""
+import ctypes
+import json
+import os
+import types
+from collections import namedtuple
+
+import numpy as np
+
+import basic_math_ref as br
+import biquad_ref as bq
+import cmplx_mat_ref as cmat
+import cmplx_math_ref as cm
+import distance_ref as dr
+import f32_classes
+import metrics
+import mat_basic_ref as mb
+import mat_solve_ref as ms
+import ml_ref
+import statistics_ref as st
+import support_ref as sup
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+TAIL = 16                                                   # marker words after every output buffer
+FAMILIES = {"BasicTestsF32": "basic", "BasicTestsQ31": "basic", "BasicTestsQ15": "basic", "BasicTestsQ7": "basic",
+            "BIQUADF32": "biquad", "BIQUADQ31": "biquad", "BIQUADQ15": "biquad", "FastMathF32": "fastmath",
+            "SVMF32": "ml", "BayesF32": "ml", "DistanceTestsF32": "distance", "DistanceTestsU32": "distance",
+            "UnaryTestsF32": "unary", "UnaryTestsQ31": "unary", "UnaryTestsQ15": "unary", "UnaryTestsQ7": "unary",
+            "SupportTestsF32": "support", "SupportTestsQ31": "support", "SupportTestsQ15": "support",
+            "SupportTestsQ7": "support", "SupportBarTestsF32": "support",
+            "BinaryTestsF32": "binary", "BinaryTestsQ31": "binary", "BinaryTestsQ15": "binary", "BinaryTestsQ7": "binary",
+            "ComplexTestsF32": "complex", "ComplexTestsQ31": "complex", "ComplexTestsQ15": "complex",
+            "StatsTestsF32": "stats", "StatsTestsQ31": "stats", "StatsTestsQ15": "stats", "StatsTestsQ7": "stats"}
+DT = dict(br.MDT)                                           # type name -> numpy dtype (f32 ... q63, u32, u16, u8)
+# pattern file suffix -> the type of its words (Testing/PatternGeneration/Tools.py writes one suffix per type)
+SUFFIX = {"f32": "f32", "q63": "q63", "q31": "q31", "q15": "q15", "q7": "q7", "s32": "q31", "s16": "q15", "s8": "q7",
+          "u32": "u32", "u16": "u16", "u8": "u8"}
+
+# A row of the table.  load: {buffer name: (pattern file stem, count)}; count None: the whole file (the framework's
+# MAX_NB_SAMPLES), an int: the first count samples, a buffer name: as many as that buffer holds.  view: {buffer name:
+# type} where the test reads a pattern as another type of the same width (the bitwise tests read _s32 files as
+# uint32_t).  call(lib, bufs, row) -> {output name: Out}.  checks: [(form, output, reference buffer, bound)].
+Row = namedtuple("Row", "suite index method label func cite load view params call checks exact")
+SCRATCH = ("tmp", "tmpA", "tmpB", "tmpC", "outputa", "outputb")   # ... or that the test derives itself, in double                                        # outputs whose words nobody reads
+
+
+def row_id(suite, index, method, label):
+    return f"{suite}/{index:02d}_{method}/{label or '-'}"
+
+
+def ref_key(row, name="output"):
+    """The fixture key of what the reference build wrote into the row's output `name`."""
+    return f"{row.id}/ref_words" if name == "output" else f"{row.id}/ref_{name}"
+
+
+Row.id = property(lambda r: row_id(r.suite, r.index, r.method, r.label))
+
+
+class Out:
+    """An output buffer of n words of type t and its marked tail (Client::AnyPattern::create + isTailEmpty)."""
+
+    def __init__(self, t, n):
+        self.t, self.n = t, n
+        self.buf = br.marked(t, n + TAIL)
+        self.words = self.buf[:n]
+        self.violations = []                                # what a call function saw go wrong between two calls
+
+    def tail_empty(self):
+        return self.buf[self.n:].tobytes() == br.marked(self.t, TAIL).tobytes()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# libraries
+class CtypesLibrary:
+    """arm_* of a ctypes library whose functions carry _abi's argtypes: arrays go in as their addresses."""
+
+    def __init__(self, lib, abi, after=None):
+        self.lib, self.abi, self.after = lib, abi, after
+
+    def instance(self, func):
+        """A zeroed instance structure of the processing function func (arm_math.h's, mirrored in _abi)."""
+        if func in self.abi.BIQUAD_FUNCS:
+            return self.abi.BIQUAD_FUNCS[func][0]()
+        if func.startswith("arm_svm_"):
+            return self.abi.SVM_KINDS[func[len("arm_svm_"):-len("_predict_f32")]][0]()
+        return {"arm_gaussian_naive_bayes_predict_f32": self.abi.arm_gaussian_naive_bayes_instance_f32,
+                "arm_sort_f32": self.abi.arm_sort_instance_f32, "arm_merge_sort_f32": self.abi.arm_merge_sort_instance_f32}[func]()
+
+    @staticmethod
+    def pointer(x):
+        """What a pointer member of an instance structure is set to."""
+        return x.ctypes.data
+
+    def matrix(self, t, rows, cols, data):
+        """arm_matrix_instance_<t> over the words of data."""
+        inst = getattr(self.abi, f"arm_matrix_instance_{t}")
+        return inst(rows, cols, ctypes.cast(data.ctypes.data, dict(inst._fields_)["pData"]))
+
+    def __getattr__(self, name):
+        fn = getattr(self.lib, name)
+
+        def call(*args):
+            keep = [np.ascontiguousarray(a) if isinstance(a, np.ndarray) else a for a in args]
+            assert all(k is a for k, a in zip(keep, args)), (name, "a buffer is not contiguous")
+            st = fn(*[a.ctypes.data if isinstance(a, np.ndarray) else
+                      ctypes.byref(a) if isinstance(a, ctypes.Structure) else a for a in keep])
+            if self.after:
+                self.after(name)
+            return st
+        return call
+
+
+def basic_args(func, args):
+    """The C argument list of arm_<func> (arm_math.h) -> (a, b, scalars, out, n)."""
+    args = list(args)
+    two = br.two_sources(func)
+    a, b = args[0], (args[1] if two else None)
+    rest = args[2 if two else 1:]
+    if br.is_dot(func):
+        n, out = rest
+        return a, b, (), out, n
+    n, k = rest[-1], br.n_scalars(func)
+    if br.split(func)[0] == "clip":
+        return a, b, tuple(rest[1:1 + k]), rest[0], n
+    return a, b, tuple(rest[:k]), rest[k], n
+
+
+def _m2(M, words=1):
+    """The [rows, words * cols] view of a restatement matrix instance."""
+    return M.data[:M.rows * M.cols * words].reshape(M.rows, M.cols * words)
+
+
+def _support_funcs():
+    """arm_copy_* / arm_fill_* / the conversions / the sorts / the weighted average / the barycenter from support_ref."""
+    f = {}
+    names = {"float": "f32", "q31": "q31", "q15": "q15", "q7": "q7"}
+    for a, s in names.items():
+        f[f"copy_{s}"] = lambda src, dst, n: dst.__setitem__(slice(0, n), src[:n])
+        f[f"fill_{s}"] = lambda val, dst, n: dst.__setitem__(slice(0, n), val)
+        for b, d in names.items():
+            if a != b:
+                f[f"{a}_to_{b}"] = lambda src, dst, n, s=s, d=d: dst.__setitem__(slice(0, n), sup.convert(s, d, src[:n]))
+
+    def sort(S, src, dst, n):
+        dst[:n] = sup.total_order_sort(src[:n], S.dir == 1)
+    f["sort_f32"] = f["merge_sort_f32"] = sort
+    f["sort_init_f32"] = lambda S, alg, direction: (setattr(S, "alg", alg), setattr(S, "dir", direction)) and None
+    f["merge_sort_init_f32"] = lambda S, direction, buf: setattr(S, "dir", direction)
+    f["weighted_average_f32"] = lambda a, w, n: float(sup.weighted_average(a[None, :n], w[None, :n])[0])
+    f["barycenter_f32"] = lambda a, w, out, nv, dim: out.__setitem__(
+        slice(0, dim), sup.barycenter(a[:nv * dim].reshape(1, nv, dim), w[None, :nv])[0])
+    return f
+
+
+_SUPPORT_FUNCS = _support_funcs()
+_MAT_OPS = ("add", "sub", "scale", "trans", "cmplx_trans", "vec_mult", "inverse", "cholesky", "ldlt",
+            "solve_upper_triangular", "solve_lower_triangular")
+
+
+def _mat_op(op, t):
+    """arm_mat_<op>_<t> from mat_basic_ref / mat_solve_ref, behind the C signature."""
+    def call(A, *rest):
+        if op in ("add", "sub"):
+            B, Cm = rest
+            _m2(Cm)[:] = mb.add(t, _m2(A), _m2(B), 1 if op == "add" else -1)
+        elif op == "scale":
+            _m2(rest[-1])[:] = mb.scale(t, _m2(A), *rest[:-1])
+        elif op == "trans":
+            _m2(rest[0])[:] = mb.trans(_m2(A))
+        elif op == "cmplx_trans":
+            _m2(rest[0], 2)[:] = mb.cmplx_trans(_m2(A, 2))
+        elif op == "vec_mult":
+            rest[1][:A.rows] = mb.vec_mult(t, _m2(A), rest[0][:A.cols])
+            return None
+        elif op == "inverse":
+            status, src, dst = ms.inverse(_m2(A))
+            _m2(A)[:], _m2(rest[0])[:] = src, dst
+            return status
+        elif op == "cholesky":
+            status, dst = ms.cholesky(_m2(A), dst=_m2(rest[0]).copy())
+            _m2(rest[0])[:] = dst
+            return status
+        elif op == "ldlt":
+            L, D, pp = rest
+            status, l, d, p = ms.ldlt(_m2(A))
+            _m2(L)[:], _m2(D)[:], pp[:A.rows] = l, d, p
+            return status
+        else:
+            B, Cm = rest
+            status, dst = ms.solve(_m2(A), _m2(B), "lower" in op, dst=_m2(Cm).copy())
+            _m2(Cm)[:] = dst
+            return status
+        return 0
+    return call
+
+
+class RestatementLibrary:
+    """The numpy restatements behind the C signatures."""
+
+    def instance(self, func):
+        return types.SimpleNamespace()
+
+    @staticmethod
+    def pointer(x):
+        return x
+
+    @staticmethod
+    def matrix(t, rows, cols, data):
+        return types.SimpleNamespace(rows=rows, cols=cols, data=data)      # .data: the words, row after row
+
+    def __getattr__(self, name):
+        func = name[len("arm_"):]
+        if func in _SUPPORT_FUNCS:
+            return _SUPPORT_FUNCS[func]
+        if name.startswith("arm_mat_cmplx_mult_"):
+            def call(A, B, Cm, scratch=None):
+                t = name[-3:]
+                got = cmat.mult_f32_ref(_m2(A, 2), _m2(B, 2)) if t == "f32" else cmat.mult_fixed(t, _m2(A, 2), _m2(B, 2))
+                _m2(Cm, 2)[:] = got
+                if scratch is not None:
+                    scratch[:2 * B.rows * B.cols] = cmat.scratch_q15(_m2(B, 2))
+                return 0
+            return call
+        if name.startswith("arm_mat_") and func[len("mat_"):].rsplit("_", 1)[0] in _MAT_OPS:
+            return _mat_op(func[len("mat_"):].rsplit("_", 1)[0], name[-3:].lstrip("_"))
+        if name.startswith("arm_mat_mult_"):                 # the CPU restatement in C (oracle/src)
+            def call(A, B, Cm, state=None):
+                import refs
+                kind = name[len("arm_mat_mult_"):]
+                o = refs.oracle_lib()
+                status, got = o.mat_mult_fmaf(_m2(A), _m2(B)) if kind == "f32" else o.mat_mult_fixed(kind, _m2(A), _m2(B))
+                _m2(Cm)[:] = got
+                return status
+            return call
+        if name.endswith("_distance_f32") and name != "arm_dtw_distance_f32":
+            def call(a, b, n):
+                got = dr.distance_f32(func[:-len("_distance_f32")], a[:n], b[:n])
+                if isinstance(got, tuple):                   # correlation: the inputs leave with their means taken off
+                    got, a[:n], b[:n] = got
+                return float(got)
+            return call
+        if name.endswith("_distance") and func[:-len("_distance")] in dr.BOOL_FUNCS:
+            def call(a, b, n):
+                return float(dr.boolean_distance(func[:-len("_distance")], a, b, n))
+            return call
+        if name == "arm_dtw_distance_f32":
+            def call(D, W, Cm, res):
+                status, r, c = dr.dtw_distance(_m2(D), None if W is None else _m2(W))
+                _m2(Cm)[:] = c
+                if status == 0:
+                    res[0] = r
+                return status
+            return call
+        if name == "arm_dtw_path_f32":
+            def call(Cm, path, length):
+                p = dr.dtw_path(_m2(Cm))
+                path[:p.size], length[0] = p.reshape(-1), len(p)
+            return call
+        if name == "arm_dtw_init_window_q7":
+            def call(kind, size, W):
+                w = dr.init_window(kind, size, W.rows, W.cols)
+                if w is None:
+                    return -1
+                _m2(W)[:] = w
+                return 0
+            return call
+        if name.startswith("arm_svm_") and name.endswith("_init_f32"):
+            def call(S, nsv, dim, intercept, dual, sv, classes, *extra):
+                S.m = {"sv": sv[:nsv * dim].reshape(nsv, dim), "dual": dual[:nsv], "classes": classes,
+                       "intercept": np.float32(intercept), "degree": 0, "coef0": np.float32(0), "gamma": np.float32(0)}
+                if "polynomial" in name:
+                    S.m.update(degree=np.int32(extra[0]), coef0=np.float32(extra[1]), gamma=np.float32(extra[2]))
+                elif "rbf" in name:
+                    S.m.update(gamma=np.float32(extra[0]))
+            return call
+        if name.startswith("arm_svm_"):
+            def call(S, x, res):
+                kind = name[len("arm_svm_"):-len("_predict_f32")]
+                dim = S.m["sv"].shape[1]
+                res[0] = ml_ref.svm_classes(S.m, ml_ref.svm_sums(kind, S.m, x[None, :dim]))[0]
+            return call
+        if name == "arm_gaussian_naive_bayes_predict_f32":
+            def call(S, x, buf, tmp):
+                c, d = S.numberOfClasses, S.vectorDimension
+                m = {"theta": S.theta[:c * d].reshape(c, d), "sigma": S.sigma[:c * d].reshape(c, d),
+                     "priors": S.classPriors[:c], "eps": np.float32(S.epsilon)}
+                prob, idx = ml_ref.bayes_predict(m, x[None, :d])
+                buf[:c] = prob[0]
+                return int(idx[0])
+            return call
+        if name in bq.FUNCS:                                 # y, state' = run(func, coeffs, postShift, x, state)
+            def call(S, src, dst, n):
+                ch = bq.FUNCS[name][4]
+                y, new = bq.run(name, S.coeffs, S.post_shift, src[None, :ch * n], S.state[None, :])
+                dst[:ch * n], S.state[:] = y[0], new[0]
+            return call
+        if "biquad" in name and "_init_" in name:            # the init zeroes the state words of numStages stages
+            def call(S, stages, coeffs, state, post_shift=0):
+                words = 4 * stages if "stereo" in name or "df2T" not in name else 2 * stages
+                S.coeffs, S.post_shift, S.state = coeffs, post_shift, state[:words]
+                S.state[:] = 0
+            return call
+        if func in br.FUNCS:
+            def call(*args):
+                a, b, scalars, out, n = basic_args(func, args)
+                t = br.split(func)[1]
+                scalars = tuple(np.float32(s) if t == "f32" else int(np.asarray(s).astype(br.DT[t])) for s in scalars)
+                if func in br.SHIFT_RANGE:                   # the shift count is an int8_t whatever the data type
+                    scalars = scalars[:-1] + (int(args[-3]),)
+                got = br.run(func, a[:n], None if b is None else b[:n], scalars)
+                if br.is_dot(func):
+                    out[0] = got["value"]
+                else:
+                    out[:n] = got["dst"]
+            return call
+        op, t = func.rsplit("_", 1)
+        if op in ("max", "min"):                             # with index: cmplx_math_ref
+            def call(a, n, res, idx):
+                v, i = cm.extreme(op, a[None, :n])
+                res[0], idx[0] = v[0], i[0]
+            return call
+        if func in st.STAT_FUNCS:
+            def call(*args):
+                if op == "mse":
+                    a, b, n, res = args
+                    got = st.run(func, a[:n], b[:n])
+                else:
+                    a, n, res = args[:3]
+                    got = st.run(func, a[:n])
+                res[0] = got["value"]
+                if st.has_index(func):
+                    args[3][0] = got["index"]
+            return call
+        if func == "cmplx_mag_fast_q15":
+            def call(a, dst, n):
+                dst[:n] = st.cmplx_mag_fast_q15(a[:2 * n])
+            return call
+        if func.startswith("cmplx_"):
+            def call(a, *rest):
+                if "dot_prod" in func:
+                    b, n, re, im = rest
+                    got = cm.run(func, {"a": a[:2 * n], "b": b[:2 * n]})
+                    re[0], im[0] = got["re"], got["im"]
+                elif "mult" in func:
+                    b, dst, n = rest
+                    dst[:2 * n] = cm.run(func, {"a": a[:2 * n], "b": b[:2 * n], "r": b[:n]})["dst"]
+                else:
+                    dst, n = rest
+                    got = cm.run(func, {"a": a[:2 * n]})["dst"]
+                    dst[:got.size] = got
+            return call
+        if func in ("vlog_f32", "vexp_f32"):                 # the host libm's logf / expf on every word
+            def call(src, dst, n):
+                dst[:n] = (ml_ref.logf if op == "vlog" else ml_ref.expf)(src[:n])
+            return call
+        if t == "f32" and op in ml_ref.LOGDOM_FUNCS:
+            def call(a, *rest):
+                two = op in ("kullback_leibler", "logsumexp_dot_prod")
+                n = rest[1] if two else rest[0]
+                return float(ml_ref.logdom(op, a[:n], rest[0][:n] if two else None))
+            return call
+        raise AttributeError(name)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the checks (Testing/FrameworkInclude/Error.h:165-179)
+def _snr(out, ref, thr):
+    """ASSERT_SNR(a, b, thr) takes the signal energy from a; the suites write (output, ref) in most places and (ref,
+    output) in some, so the check must hold both ways."""
+    return metrics.snr_passes(_real(ref), _real(out), thr) and metrics.snr_passes(_real(out), _real(ref), thr)
+
+
+def _real(x):
+    """Words -> the values arm_snr_* compare (q types scaled to [-1, 1), Error.cpp:583-705)."""
+    x = np.asarray(x)
+    if x.dtype.kind == "f":
+        return x.astype(np.float64)
+    return x.astype(np.float64) / 2.0 ** (8 * x.itemsize - 1)
+
+
+def _rel(out, ref, thr):
+    return metrics.rel_error(out, ref, thr) and metrics.relative_error(out, ref, thr)
+
+
+CHECKS = {
+    "snr": _snr,                                                                    # ASSERT_SNR
+    "near_eq": lambda out, ref, thr: metrics.near_eq(out, ref, thr),                # ASSERT_NEAR_EQ
+    "rel": _rel,                                                                    # ASSERT_REL_ERROR
+    # ASSERT_CLOSE_ERROR (abs, rel); the suites pass (ref, output) as often as (output, ref): both ways must hold
+    "close": lambda out, ref, thr: (metrics.close_error(out, ref, thr[0], thr[1]) and
+                                    metrics.close_error(ref, out, thr[0], thr[1])),
+    "eq": lambda out, ref, thr: metrics.equal(out, ref),                            # ASSERT_EQ
+    "eq_s16": lambda out, ref, thr: metrics.equal(out.astype(np.int16), ref),       # ASSERT_EQ((int16_t)index, ...)
+    "eq_partial": lambda out, ref, thr: metrics.equal(out, ref),                    # ASSERT_EQ_PARTIAL(n, out, ref)
+    # ASSERT_NEAR_EQ on float32 words: fabs(a - b) <= bound, in float (Error.cpp:73-82)
+    "near": lambda out, ref, thr: bool(np.all(np.abs(out.astype(np.float32) - ref) <= np.float32(thr))),
+    # ASSERT_TRUE(fabs(c - result) < bound), in float as the test computes it
+    "within": lambda out, ref, thr: bool(np.all(np.abs(ref.astype(np.float32) - out) < np.float32(thr))),
+}
+
+
+def load(row, patterns):
+    """The row's input and reference buffers, as the suite's setUp leaves them."""
+    bufs = {}
+    for name, (stem, count) in row.load.items():
+        x = patterns[f"{row.suite}/{stem}"]
+        if isinstance(count, str):
+            count = bufs[count].size
+        x = x if count is None else x[:count]                # PatternMgr.cpp:68: at most count samples
+        if name in row.view:
+            x = x.view(DT[row.view[name]])
+        bufs[name] = np.ascontiguousarray(x).copy()
+    for name, x in row.params.get("consts", {}).items():     # data the test method holds itself
+        bufs[name] = np.array(x).copy()
+    return bufs
+
+
+def reference(row, bufs, ref):
+    """The words a check compares with: the reference buffer, or refp[this->refOffset] where the test indexes it."""
+    want = bufs[ref]
+    if "refOffset" in row.params:
+        want = want[row.params["refOffset"]:row.params["refOffset"] + 1]
+    return want
+
+
+def run_row(row, lib, patterns, tamper=None):
+    """Replays the row -> ({output name: words}, [failed checks]).  tamper(outs), if given, runs between the call and
+    the checks (the negative controls plant their defects there)."""
+    bufs = load(row, patterns)
+    kept = {k: v.copy() for k, v in bufs.items()}
+    outs = row.call(lib, bufs, row)
+    if tamper:
+        tamper(outs)
+    failed = []
+    for k, v in kept.items():
+        if bufs[k].tobytes() != v.tobytes():
+            failed.append(("input changed", k))
+    for name, o in outs.items():
+        if not o.tail_empty():
+            failed.append(("tail", name))
+        failed += [(what, name, where) for what, where in o.violations]
+    for form, name, ref, thr in row.checks:
+        want = outs[ref].words if ref in outs else reference(row, bufs, ref)      # LDLT compares two outputs
+        got = outs[name].words
+        if form == "eq_partial":                             # the first words, as many as the output holds
+            want = want[:got.size]
+        if got.shape != want.shape or not CHECKS[form](got, want, thr):
+            failed.append((form, name, thr))
+    return {k: o.words.copy() for k, o in outs.items()}, failed
+
+
+_LOADED = {}
+
+
+def patterns_of(family):
+    """The family's fixture, read once and shared; run_row copies what it hands to a library."""
+    if family not in _LOADED:
+        with np.load(os.path.join(GOLDEN, f"suites_{family}.npz")) as z:
+            _LOADED[family] = {k: z[k] for k in z.files}
+    return _LOADED[family]
+
+
+def patterns(row):
+    return patterns_of(FAMILIES[row.suite])
+
+
+def same_words(got, want, what):
+    """Bit for bit; f32 NaNs by position (f32_classes.assert_same_words)."""
+    if got.dtype == np.float32:
+        f32_classes.assert_same_words(got, want, what)
+    else:
+        assert got.dtype == want.dtype and got.tobytes() == want.tobytes(), (what, got[:8], want[:8])
+
+
+def exported_names(abi):
+    """Every arm_* name of the tables of cmsisdsp_amd/_abi.py: what the library exports and the headers declare."""
+    names = set()
+    for v in vars(abi).values():
+        if isinstance(v, dict):
+            names |= {k for k in v if isinstance(k, str) and k.startswith("arm_")}
+    return names
+
+
+def manifest():
+    with open(os.path.join(GOLDEN, "suites_manifest.json")) as f:
+        return json.load(f)
+
+
+def summary():
+    """The manifest in one sentence, as README.md and DESIGN.md quote it (tools/make_golden_suites.py prints it)."""
+    lines = manifest()
+    suites = list(dict.fromkeys(e["suite"] for e in lines))
+    skipped = [e["status"][len("skipped: "):] for e in lines if e["status"] != "replayed"]
+    why = f" ({'; '.join(sorted(set(skipped)))})" if skipped else ""
+    return f"{len(lines)} test lines of {len(suites)} suites: {len(lines) - len(skipped)} replayed, {len(skipped)} skipped{why}"
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Basic Tests F32 / Q31 / Q15 / Q7 (Testing/Source/Tests/BasicTests{F32,Q31,Q15,Q7}.cpp, desc.txt:1069-1556)
+def _basic_call(lib, bufs, row):
+    """test_<op>_<t>: one call on input1 (and input2); the output is created with the reference's length; the scalar
+    arguments are this->scalar (with shift 0 for arm_scale_q*), 1 for arm_shift_q*, this->min / this->max."""
+    func = row.func[len("arm_"):]
+    out = Out(br.result_type(func), bufs["ref"].size)
+    a = bufs["input1"]
+    srcs = [a, bufs["input2"]] if br.two_sources(func) else [a]
+    n = a.size
+    p = row.params
+    fn = getattr(lib, row.func)
+    op = br.split(func)[0]
+    if br.is_dot(func):
+        fn(*srcs, n, out.words)                              # arm_dot_prod_*(inp1, inp2, nb, &r); outp[0] = r
+    elif op == "clip":
+        fn(*srcs, out.words, p["min"], p["max"], n)
+    elif op in ("offset", "shift") or func == "scale_f32":
+        fn(*srcs, p["scalar"], out.words, n)
+    elif op == "scale":
+        fn(*srcs, p["scalar"], 0, out.words, n)
+    else:
+        fn(*srcs, out.words, n)
+    return {"output": out}
+
+
+def _signed(v, bits):
+    """A C initialiser such as 0x8ccccccd as the q31_t / q15_t / q7_t it becomes."""
+    return v - (1 << bits) if v >= 1 << (bits - 1) else v
+
+
+def _basic_rows(t):
+    T = t.upper()
+    suite = f"BasicTests{T}"
+    tol = metrics.BASIC_TOL[t]
+    bits = {"f32": 32, "q31": 32, "q15": 16, "q7": 8}[t]
+    u = f"u{bits}"
+    src = f"Testing/Source/Tests/{suite}.cpp"
+    s = f"s{bits}"
+    dot_t = br.DOT_OUT[t]
+    lengths = {"f32": (3, 8, 11), "q31": (3, 8, 11), "q15": (7, 16, 23), "q7": (15, 32, 47)}[t]
+    labels = {"f32": ("nb=3", "nb=4n", "nb=4n+1"), "q31": ("nb=3", "nb=4n", "nb=4n+1"),
+              "q15": ("nb=7", "nb=8n", "nb=8n+1"), "q7": ("nb=15", "nb=16n", "nb=16n+1")}[t]
+    half = np.float32(0.5) if t == "f32" else 1 << (bits - 2)          # 0.5 / ONEHALF
+    ops = ("add", "sub", "mult", "negate", "offset", "scale", "dot_prod", "abs")
+    refs = {op: f"Reference{k}_{t}" for op, k in (("add", 1), ("sub", 2), ("mult", 3), ("negate", 4), ("offset", 5),
+                                                  ("scale", 6), ("abs", 10))}
+    dot_refs = [f"Reference{k}_{dot_t}" for k in (7, 8, 9)]
+    rows = []
+
+    def checks(op, method=None):
+        if t == "f32":
+            return [("snr", "output", "ref", tol["snr"]), ("rel", "output", "ref", tol["rel"])]
+        snr = tol["snr"]
+        if t == "q15" and op in ("mult", "dot_prod"):
+            snr = tol["snr_mult"]
+        if method == "test_mult_short_q7":
+            snr = tol["snr_mult_short"]
+        return [("snr", "output", "ref", snr),
+                ("near_eq", "output", "ref", tol["abs_dot"] if op == "dot_prod" else tol["abs"])]
+
+    def add(method, label, func, load, params=None, view=None, chk=None, lines=""):
+        op = br.split(func)[0]
+        rows.append(Row(suite, len(rows) + 1, method, label, "arm_" + func, f"{src}:{lines}", load, view or {},
+                        params or {}, _basic_call, chk or checks(op, method), True))
+
+    def plain(op, label, nb):
+        """TEST_<OP>_1 ... _24 and the `long` tests: the first nb samples (all of them when nb is None)."""
+        ld = {"ref": (refs[op], nb)} if op != "dot_prod" else {}
+        ld["input1"] = (f"Input1_{t}", nb)
+        if op in ("add", "sub", "mult", "dot_prod"):
+            ld["input2"] = (f"Input2_{t}", nb)
+        method = f"test_{op}_{t}"
+        if t == "q7" and op == "mult" and nb == 15:
+            method = "test_mult_short_q7"
+        return method, ld
+
+    for op in ops:                                           # tests 1 ... 24
+        for k, (label, nb) in enumerate(zip(labels, lengths)):
+            method, ld = plain(op, label, nb)
+            if op == "dot_prod":
+                ld["ref"] = (dot_refs[k], None)
+            if t == "q7" and op == "add":                    # desc.txt:1493-1495 labels these three 15 / 15n / 15n+1
+                label = ("nb=15", "nb=15n", "nb=15n+1")[k]
+            add(method, label, f"{op}_{t}", ld, {"scalar": half},
+                lines=f" {method}, setUp case {method[5:].upper()}_{len(rows) + 1}")
+    if t != "f32":
+        mx, mn, mn2 = f"MaxPosInput12_{s}", f"MaxNegInput12_{s}", f"MaxNeg2Input12_{s}"
+
+        def sat(label, op, ref, in1, in2=None, scalar=half):
+            ld = {"ref": (f"{ref}_{t}", None), "input1": (in1, None)}
+            if in2:
+                ld["input2"] = (in2, None)
+            add(f"test_{op}_{t}", label, f"{op}_{t}", ld, {"scalar": scalar}, lines=f"setUp tests 25-36 ({label})")
+        sat("add sat pos", "add", "PosSat12", mx, mx)
+        sat("add sat neg", "add", "NegSat13", mn, mn)
+        sat("sub sat pos", "sub", "PosSat14", mx, mn)
+        sat("sub sat neg", "sub", "NegSat15", mn, mx)
+        sat("mul sat", "mult", "PosSat16", mn2, mn2)
+        sat("neg sat", "negate", "PosSat17", mn2)
+        # this->scalar: 0.9 (0x73333333 / 0x7333 / 0x73), -0.9 (0x8ccccccd / 0x8ccd / 0x8d), minus max
+        sat("offset pos sat", "offset", "PosSat18", mx, scalar={32: 0x73333333, 16: 0x7333, 8: 0x73}[bits])
+        sat("offset neg sat", "offset", "NegSat19", mn, scalar=_signed({32: 0x8ccccccd, 16: 0x8ccd, 8: 0x8d}[bits], bits))
+        sat("scale pos sat", "scale", "PosSat20", mn2, scalar=-(1 << (bits - 1)))
+        sat("shift", "shift", "Shift21", f"Input12_{t}", scalar=1)
+        sat("shift pos sat", "shift", "Shift22", mx, scalar=1)
+        sat("shift neg sat", "shift", "Shift23", mn, scalar=1)
+        blabels = {"q31": ("nb=3", "nb=4n", "nb=4n+3"), "q15": ("nb=7", "nb=8n", "nb=8n+7"),
+                   "q7": ("nb=15", "nb=16n", "nb=16n+15")}[t]
+        for op, ref in (("and", "And24"), ("or", "Or25"), ("not", "Not26"), ("xor", "Xor27")):   # tests 37 ... 48
+            for label, nb in zip(blabels, lengths):
+                ld = {"ref": (f"{ref}_{s}", nb), "input1": (f"BitwiseInput24_{s}", nb)}
+                if op != "not":
+                    ld["input2"] = (f"BitwiseInput25_{s}", nb)
+                add(f"test_{op}_{u}", label, f"{op}_{u}", ld, view={k: u for k in ld},
+                    chk=[("eq", "output", "ref", None)], lines=f"setUp TEST_{op.upper()}_{u.upper()}")
+    for op in ops:                                           # `long`: nb = MAX_NB_SAMPLES, the whole patterns
+        method, ld = plain(op, "long", None)
+        if op == "dot_prod":
+            ld["ref"] = (f"Reference11_{dot_t}", None)
+        add(method, "long", f"{op}_{t}", ld, {"scalar": half}, lines="setUp `long` tests")
+    clip_in, first = (("Input12_f32", 12) if t == "f32" else (f"Input28_{t}", 28))
+    # "Must be coherent with Python script used to generate test patterns": min / max of tests 1, 2, 3
+    bounds = {"f32": ((-0.5, -0.1), (-0.5, 0.5), (0.1, 0.5)),
+              "q31": ((0xC0000000, 0xF3333333), (0xC0000000, 0x40000000), (0x0CCCCCCD, 0x40000000)),
+              "q15": ((0xC000, 0xF333), (0xC000, 0x4000), (0x0CCD, 0x4000)),
+              "q7": ((0xC0, 0xF3), (0xC0, 0x40), (0x0D, 0x40))}[t]
+    for k, (lo, hi) in enumerate(bounds):
+        p = {"min": np.float32(lo), "max": np.float32(hi)} if t == "f32" else \
+            {"min": _signed(lo, bits), "max": _signed(hi, bits)}
+        add(f"test_clip_{t}", str(k + 1), f"clip_{t}", {"ref": (f"Reference{first + k}_{t}", None),
+                                                         "input1": (clip_in, "ref")}, p, lines="setUp TEST_CLIP_*")
+    return rows
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Statistics Tests F32 / Q31 / Q15 / Q7 (Testing/Source/Tests/StatsTests{F32,Q31,Q15,Q7}.cpp, desc.txt:143-565)
+INDEXED = ("max", "min", "absmax", "absmin")
+LOGDOM = ("entropy", "logsumexp", "kullback_leibler", "logsumexp_dot_prod")
+
+
+def stat_result_type(func):
+    op, t = func.rsplit("_", 1)
+    return st.POWER_OUT[t] if op == "power" else t
+
+
+def _stat_call(lib, bufs, row):
+    """test_<op>_<t>: one call on inputA (arm_mse_*: and inputB) over inputA.nbSamples(); result -> outp[0], indexval
+    -> ind[0] (an int16_t buffer; here the uint32_t the function writes, compared as (int16_t)indexval)."""
+    func = row.func[len("arm_"):]
+    op = func.rsplit("_", 1)[0]
+    a = bufs["inputA"]
+    outs = {"output": Out(stat_result_type(func), 1)}
+    fn = getattr(lib, row.func)
+    if op in INDEXED:
+        outs["index"] = Out("u32", 1)
+        fn(a, a.size, outs["output"].words, outs["index"].words)
+    elif op == "mse":
+        fn(a, bufs["inputB"], a.size, outs["output"].words)
+    else:
+        fn(a, a.size, outs["output"].words)
+    return outs
+
+
+def _logdom_call(lib, bufs, row):
+    """test_entropy_f32 ... test_logsumexp_dot_prod_f32: dims[0] patterns of dims[i + 1] words each, one after the
+    other in inputA (and inputB); the value each call returns goes to the next output word.  tmp holds 12 words, "max
+    vecDim as defined in Python script generating the data"."""
+    op = row.func[len("arm_"):-len("_f32")]
+    dims = bufs["dims"]
+    out = Out("f32", bufs["ref"].size)
+    outs = {"output": out}
+    if op == "logsumexp_dot_prod":
+        outs["tmp"] = Out("f32", 12)
+    fn = getattr(lib, row.func)
+    at = 0
+    for i in range(int(dims[0])):
+        n = int(dims[i + 1])
+        srcs = [bufs[k][at:at + n] for k in ("inputA", "inputB") if k in bufs]
+        out.words[i] = fn(*srcs, n, *([outs["tmp"].words] if "tmp" in outs else []))
+        at += n
+    return outs
+
+
+def _accumulate_call(lib, bufs, row):
+    """test_accumulate_f32: dims[0] calls over the first dims[i + 1] words of inputA (inp does not advance)."""
+    dims = bufs["dims"]
+    out = Out("f32", bufs["ref"].size)
+    for i in range(int(dims[0])):
+        lib.arm_accumulate_f32(bufs["inputA"], int(dims[i + 1]), out.words[i:i + 1])
+    return {"output": out}
+
+
+def _stats_rows(t):
+    suite = f"StatsTests{t.upper()}"
+    src = f"Testing/Source/Tests/{suite}.cpp"
+    tol = metrics.STATS_TOL[t]
+    lengths = {"f32": (3, 8, 11), "q31": (3, 8, 11), "q15": (7, 16, 23), "q7": (15, 32, 47)}[t]
+    labels = {"f32": ("nb=3", "nb=4n", "nb=4n+1"), "q31": ("nb=3", "nb=4n", "nb=4n+1"),
+              "q15": ("nb=7", "nb=8n", "nb=8n+1"), "q7": ("nb=15", "nb=16n", "nb=16n+1")}[t]
+    new = 26 if t == "f32" else 8                            # AbsMaxVals26 / AbsMaxVals8 ...
+    pt = st.POWER_OUT[t]
+    # op -> (input pattern, reference values, reference indexes)
+    pat = {"max": ("Input1", "MaxVals1", "MaxIndexes1"), "min": ("Input1", "MinVals3", "MinIndexes3"),
+           "mean": ("Input2", "MeanVals2", None), "power": ("Input1", f"PowerVals4_{pt}", None),
+           "rms": ("Input1", "RmsVals5", None), "std": ("Input1", "StdVals6", None), "var": ("Input1", "VarVals7", None),
+           "absmax": ("InputNew1", f"AbsMaxVals{new}", f"AbsMaxIndexes{new}"),
+           "absmin": ("InputNew1", f"AbsMinVals{new + 1}", f"AbsMinIndexes{new + 1}"),
+           "max_no_idx": ("Input1", "MaxVals1", None), "min_no_idx": ("Input1", "MinVals3", None),
+           "absmax_no_idx": ("InputNew1", f"AbsMaxVals{new}", None),
+           "absmin_no_idx": ("InputNew1", f"AbsMinVals{new + 1}", None),
+           "mse": ("InputNew1", f"MSEVals{new + 2}", None)}
+    rows = []
+
+    def checks(op):
+        if op in INDEXED:
+            return [("eq", "output", "ref", None), ("eq_s16", "index", "refind", None)]
+        if op.endswith("_no_idx"):
+            return [("eq", "output", "ref", None)]
+        if t == "f32":
+            return [("snr", "output", "ref", tol["snr"]), ("rel", "output", "ref", tol["rel"])]
+        snr = tol.get(f"snr_{op}", tol["snr"])
+        return [("snr", "output", "ref", snr), ("near_eq", "output", "ref", tol.get(f"abs_{op}", tol["abs"]))]
+
+    def add(op, label, nb, offset, inp=None, method=None):
+        i, r, ri = pat[op]
+        ld = {"inputA": (f"{inp or i}_{t}", nb), "ref": (r if r.rsplit("_", 1)[-1] in SUFFIX else f"{r}_{t}", None)}
+        if op == "mse":
+            ld["inputB"] = (f"InputNew2_{t}", nb)
+        if ri:
+            ld["refind"] = (f"{ri}_s16", None)
+        rows.append(Row(suite, len(rows) + 1, method or f"test_{op}_{t}", label, f"arm_{op}_{t}",
+                        f"{src}: test_{op}_{t}, setUp case {len(rows) + 1}", ld, {}, {"refOffset": offset}, _stat_call,
+                        checks(op), True))
+
+    def three(*ops):
+        for op in ops:
+            for k in range(3):
+                add(op, labels[k], lengths[k], k)
+
+    if t == "f32":
+        three("max", "mean", "min", "power", "rms", "std", "var")
+        for op, k, two in (("entropy", 22, False), ("logsumexp", 23, False), ("kullback_leibler", 24, True),
+                           ("logsumexp_dot_prod", 25, True)):
+            ref = {"entropy": "RefEntropy22", "logsumexp": "RefLogSumExp23", "kullback_leibler": "RefKL24",
+                   "logsumexp_dot_prod": "RefLogSumExpDot25"}[op]
+            ld = ({"inputA": (f"InputA{k}_f32", None), "inputB": (f"InputB{k}_f32", None)} if two else
+                  {"inputA": (f"Input{k}_f32", None)})
+            ld.update(dims=(f"Dims{k}_s16", None), ref=(f"{ref}_f32", None))
+            rows.append(Row(suite, len(rows) + 1, f"test_{op}_f32", "", f"arm_{op}_f32", f"{src}:355-436, setUp case {k}",
+                            ld, {}, {}, _logdom_call,
+                            [("snr", "output", "ref", tol["snr"]), ("rel", "output", "ref", tol["rel"])], True))
+        three("max_no_idx")
+        for op in ("mean", "rms", "std", "var"):
+            add(op, "long", 100, 3)
+        c, bound = tol["stability"]
+        # in[4] = {4, 7, 13, 16}, each += 3.0e4f: the textbook variance would go negative (StatsTestsF32.cpp:311-353)
+        x = np.array([4.0, 7.0, 13.0, 16.0], dtype=np.float32) + np.float32(3.0e4)
+        rows.append(Row(suite, len(rows) + 1, "test_std_stability_f32", "stability", "arm_std_f32", f"{src}:311-353", {},
+                        {}, {"consts": {"inputA": x, "ref": np.array([c], dtype=np.float32)}}, _stat_call,
+                        [("within", "output", "ref", bound)], True))
+        three("absmax", "absmin", "min_no_idx", "absmax_no_idx", "absmin_no_idx", "mse")
+        add("mse", "long", 100, 3)
+        rows.append(Row(suite, len(rows) + 1, "test_accumulate_f32", "combined", "arm_accumulate_f32",
+                        f"{src}:462-479, setUp case 53",
+                        {"inputA": ("InputAccumulate1_f32", None), "dims": ("InputAccumulateConfig1_s16", None),
+                         "ref": ("RefAccumulate1_f32", None)}, {}, {}, _accumulate_call,
+                        [("snr", "output", "ref", tol["snr"]), ("rel", "output", "ref", tol["rel"])], True))
+        return rows
+    if t == "q7":
+        three("max", "mean", "min", "power")
+        add("max", "big index", 280, 3, inp="InputMaxIndexMax1")
+        add("min", "big index", 280, 3, inp="InputMinIndexMax3")
+        three("absmax", "absmin")
+        add("absmax", "big index", 280, 4, inp="InputAbsMaxIndexMax8")
+        add("absmin", "big index", 280, 3, inp="InputAbsMinIndexMax9")
+    else:
+        three("max", "mean", "min", "power", "rms", "std", "var", "absmax", "absmin")
+    three("max_no_idx", "min_no_idx", "absmax_no_idx", "absmin_no_idx", "mse")
+    add("mse", "long", 100, 3)
+    add("absmax_no_idx", "saturation", None, 3)
+    add("absmax", "saturation", None, 3)
+    return rows
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# BIQUAD F32 / Q31 / Q15 (Testing/Source/Tests/BIQUAD{F32,Q31,Q15}.cpp, desc.txt:3268-3333)
+def _biquad_ref_call(lib, bufs, row):
+    """test_biquad_cascade_df1(_ref) / _df2T_ref: 3 stages (postShift 2 for q31 / q15), the inputs filtered as two
+    blocks of inputs.nbSamples() >> 1 so that the state carries over.  test_biquad_cascade_df1_32x64 filters them one
+    sample per call instead (delta = 1, BIQUADQ31.cpp:131-149) and wants the words after each call's output untouched
+    (checkInnerTail)."""
+    dt, sdt, ks, nc, ch = bq.FUNCS[row.func]
+    out = Out(row.params["t"], bufs["ref"].size)
+    state = Out(row.params["state_t"], row.params["state_words"])
+    S = lib.instance(row.func)
+    init = getattr(lib, row.params["init"])
+    init(S, 3, bufs["coefs"], state.words, *row.params["post_shift"])
+    x = bufs["inputs"]
+    block = x.size >> 1
+    fn = getattr(lib, row.func)
+    steps = [1] * (2 * block) if row.params.get("delta") else [block, block]
+    at = 0
+    for n in steps:
+        fn(S, x[at:at + n], out.words[at:at + n], n)
+        at += n
+        if row.params.get("delta") and out.buf[at:].tobytes() != br.marked(out.t, out.buf.size - at).tobytes():
+            out.violations.append(("inner tail", at))
+    return {"output": out, "state": state}
+
+
+def _biquad_rand_call(lib, bufs, row):
+    """test_biquad_cascade_{df1,df2T,stereo_df2T}_rand: configs holds (numStages, blockSize) pairs; every pair inits
+    the filter anew on the next numStages * 5 coefficients and filters one block (stereo: 2 * blockSize words)."""
+    dt, sdt, ks, nc, ch = bq.FUNCS[row.func]
+    out = Out("f32", bufs["ref"].size)
+    state = Out("f32", row.params["state_words"])
+    S = lib.instance(row.func)
+    init, fn = getattr(lib, row.params["init"]), getattr(lib, row.func)
+    cfg = bufs["configs"]
+    at = c = 0
+    for i in range(0, cfg.size, 2):
+        stages, block = int(cfg[i]), int(cfg[i + 1])
+        init(S, stages, bufs["coefs"][c:c + 5 * stages], state.words)
+        fn(S, bufs["inputs"][at:at + ch * block], out.words[at:at + ch * block], block)
+        at += ch * block
+        c += 5 * stages
+    return {"output": out, "state": state}
+
+
+def _biquad_rows():
+    rows = []
+
+    def add(suite, index, method, label, func, load, call, checks, lines, **params):
+        init = {"arm_biquad_cas_df1_32x64_q31": "arm_biquad_cas_df1_32x64_init_q31"}.get(
+            func, func.replace("_fast", "")[:-4] + "_init" + func[-4:])
+        rows.append(Row(suite, index, method, label, func, f"Testing/Source/Tests/{suite}.cpp:{lines}", load, {},
+                        dict(params, init=init), call, checks, True))
+
+    tol = metrics.BIQUAD_TOL
+    f32 = [("snr", "output", "ref", tol["f32"]["snr"]), ("rel", "output", "ref", tol["f32"]["rel"])]
+    one = {"inputs": ("BiquadInput1_f32", None), "coefs": ("BiquadCoefs1_f32", None), "ref": ("BiquadOutput1_f32", None)}
+    every = {"inputs": ("AllBiquadInputs2_f32", None), "coefs": ("AllBiquadCoefs2_f32", None),
+             "ref": ("AllBiquadRefs2_f32", None), "configs": ("AllBiquadConfigs2_s16", None)}
+    stereo = dict(every, inputs=("AllBiquadStereoInputs2_f32", None), ref=("AllBiquadStereoRefs2_f32", None))
+    kw = dict(t="f32", state_t="f32", state_words=128, post_shift=())
+    add("BIQUADF32", 1, "test_biquad_cascade_df1_ref", "arm_biquad_cascade_df1 ref pattern",
+        "arm_biquad_cascade_df1_f32", one, _biquad_ref_call, f32, "15-86,409-419", **kw)
+    add("BIQUADF32", 2, "test_biquad_cascade_df2T_ref", "arm_biquad_cascade_df2T ref pattern",
+        "arm_biquad_cascade_df2T_f32", one, _biquad_ref_call, f32, "88-163,421-427", **kw)
+    add("BIQUADF32", 3, "test_biquad_cascade_df1_rand", "arm_biquad_cascade_df1 random pattern",
+        "arm_biquad_cascade_df1_f32", every, _biquad_rand_call, f32, "165-240,429-439", **kw)
+    add("BIQUADF32", 4, "test_biquad_cascade_df2T_rand", "arm_biquad_cascade_df2T random pattern",
+        "arm_biquad_cascade_df2T_f32", every, _biquad_rand_call, f32, "242-330,441-448", **kw)
+    add("BIQUADF32", 5, "test_biquad_cascade_stereo_df2T_rand", "arm_biquad_cascade_stereo_df2T random pattern",
+        "arm_biquad_cascade_stereo_df2T_f32", stereo, _biquad_rand_call, f32, "332-401,450-456", **kw)
+    q31 = {"inputs": ("BiquadInput1_q31", None), "coefs": ("BiquadCoefs1_q31", None), "ref": ("BiquadOutput1_q31", None)}
+    add("BIQUADQ31", 1, "test_biquad_cascade_df1", "", "arm_biquad_cascade_df1_q31", q31, _biquad_ref_call,
+        [("snr", "output", "ref", tol["q31"]["snr"]), ("near_eq", "output", "ref", tol["q31"]["abs"])], "22-80",
+        t="q31", state_t="q31", state_words=32, post_shift=(2,))
+    add("BIQUADQ31", 2, "test_biquad_cascade_df1_32x64", "", "arm_biquad_cas_df1_32x64_q31", q31, _biquad_ref_call,
+        [("snr", "output", "ref", tol["q31"]["snr_32x64"]), ("near_eq", "output", "ref", tol["q31"]["abs_32x64"])],
+        "14-20,83-159", t="q31", state_t="q63", state_words=32, post_shift=(2,), delta=1)
+    q15 = {"inputs": ("BiquadInput1_q15", None), "coefs": ("BiquadCoefs1_q15", None), "ref": ("BiquadOutput1_q15", None)}
+    add("BIQUADQ15", 1, "test_biquad_cascade_df1", "", "arm_biquad_cascade_df1_q15", q15, _biquad_ref_call,
+        [("snr", "output", "ref", tol["q15"]["snr"]), ("near_eq", "output", "ref", tol["q15"]["abs"])], "16-74",
+        t="q15", state_t="q15", state_words=32, post_shift=(2,))
+    return rows
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# FastMathF32 (Testing/Source/Tests/FastMathF32.cpp, desc.txt:1828-1862): arm_vlog_f32 and arm_vexp_f32.  The other
+# lines name no function in desc.txt; CALLS says which one their test method calls (FastMathF32.cpp:35,56,72,89).
+CALLS = {("FastMathF32", "test_cos_f32"): "arm_cos_f32", ("FastMathF32", "test_sin_f32"): "arm_sin_f32",
+         ("FastMathF32", "test_sqrt_f32"): "arm_sqrt_f32", ("FastMathF32", "test_atan2_scalar_f32"): "arm_atan2_f32"}
+
+
+def _vector_call(lib, bufs, row):
+    """test_vlog_f32 / test_vexp_f32: one call over ref.nbSamples() words."""
+    out = Out("f32", bufs["ref"].size)
+    getattr(lib, row.func)(bufs["input"], out.words, bufs["ref"].size)
+    return {"output": out}
+
+
+def _fastmath_rows():
+    tol = metrics.FASTMATH_TOL["f32"]
+    checks = [("snr", "output", "ref", tol["snr"]), ("close", "output", "ref", (tol["abs"], tol["rel"]))]
+    rows = []
+    for first, op, stem, ref, lines in ((4, "vlog", "LogInput1_f32", "Log1_f32", "100-111"),
+                                        (8, "vexp", "ExpInput1_f32", "Exp1_f32", "113-124")):
+        for k, (label, nb) in enumerate((("", None), ("nb=3", 3), ("nb=4n", 8), ("nb=4n+1", 11))):
+            rows.append(Row("FastMathF32", first + k, f"test_{op}_f32", f"test_{op}_f32 {label}".strip(),
+                            f"arm_{op}_f32", f"Testing/Source/Tests/FastMathF32.cpp:{lines}, setUp case {first + k}",
+                            {"input": (stem, nb), "ref": (ref, nb)}, {}, {}, _vector_call, checks, True))
+    return rows
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# ComplexTests F32 / Q31 / Q15 (Testing/Source/Tests/ComplexTests{F32,Q31,Q15}.cpp, desc.txt:1619-1790)
+def _complex_call(lib, bufs, row):
+    """test_cmplx_<op>_<t>: one call over input1.nbSamples() >> 1 complex samples; the dot product's re and im go to
+    the two words of the output."""
+    func = row.func[len("arm_"):]
+    op, t = (func[len("cmplx_"):].rsplit("_", 1)) if func != "cmplx_mag_fast_q15" else ("mag_fast", "q15")
+    out = Out(cm.DOT_OUT[t] if op == "dot_prod" else t, bufs["ref"].size)
+    a, n = bufs["input1"], bufs["input1"].size >> 1
+    fn = getattr(lib, row.func)
+    if op == "dot_prod":
+        fn(a, bufs["input2"], n, out.words[0:1], out.words[1:2])
+    elif op in ("mult_cmplx", "mult_real"):
+        fn(a, bufs["input2"], out.words, n)
+    else:
+        fn(a, out.words, n)
+    return {"output": out}
+
+
+def _complex_rows(t):
+    suite = f"ComplexTests{t.upper()}"
+    tol = metrics.COMPLEX_TOL[t]
+    lengths = {"f32": (3, 8, 11), "q31": (3, 8, 11), "q15": (7, 16, 23)}[t]
+    labels = ("nb=3", "nb=4n", "nb=4n+1")                    # desc.txt keeps these labels for q15's 7 / 16 / 23
+    long_nb = None if t == "f32" else 256                    # f32: MAX_NB_SAMPLES, the whole patterns
+    dt = cm.DOT_OUT[t]
+    ref = {"conj": (f"Reference1_{t}", 2), "mag": (f"Reference5_{t}", 1), "mag_squared": (f"Reference6_{t}", 1),
+           "mult_cmplx": (f"Reference7_{t}", 2), "mult_real": (f"Reference8_{t}", 2), "mag_fast": (f"Reference5_{t}", 1)}
+    rows = []
+
+    def checks(op):
+        if t == "f32":
+            return [("snr", "output", "ref", tol["snr"]), ("rel", "output", "ref", tol["rel"])]
+        return [("snr", "output", "ref", tol.get(f"snr_{op}", tol["snr"])),
+                ("near_eq", "output", "ref", tol.get(f"abs_{op}", tol["abs"]))]
+
+    def add(op, label, nb, dot_ref=None):
+        scale = lambda k: None if nb is None else nb * k     # noqa: E731
+        ld = {"input1": (f"Input1_{t}", scale(2))}
+        if op in ("dot_prod", "mult_cmplx"):
+            ld["input2"] = (f"Input2_{t}", scale(2))
+        if op == "mult_real":
+            ld["input2"] = (f"Input3_{t}", scale(1))
+        ld["ref"] = (dot_ref, None) if op == "dot_prod" else (ref[op][0], scale(ref[op][1]))
+        func = "arm_cmplx_mag_fast_q15" if op == "mag_fast" else f"arm_cmplx_{op}_{t}"
+        rows.append(Row(suite, len(rows) + 1, "test_" + func[len("arm_"):], label, func,
+                        f"Testing/Source/Tests/{suite}.cpp: test_{func[4:]}, setUp case {len(rows) + 1}", ld, {}, {},
+                        _complex_call, checks(op), True))
+
+    for op in ("conj", "dot_prod", "mag", "mag_squared", "mult_cmplx", "mult_real"):
+        for k in range(3):
+            add(op, labels[k], lengths[k], f"Reference{2 + k}_{dt}")
+    for op in ("conj", "dot_prod", "mag", "mag_squared", "mult_cmplx", "mult_real"):
+        if op != "dot_prod" or t == "f32":
+            add(op, "long", long_nb, "Reference9_f32")
+    if t == "q15":
+        for k in range(3):
+            add("mag_fast", labels[k], lengths[k])
+        add("mag_fast", "long", 256)
+    return rows
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# SVMF32 and BayesF32 (Testing/Source/Tests/SVMF32.cpp, BayesF32.cpp; desc.txt:1971-2037): models fitted by
+# scikit-learn (Testing/PatternGeneration/SVM.py, Bayes.py), their parameters packed into one pattern
+def _svm_call(lib, bufs, row):
+    """setUp (SVMF32.cpp:148-246): dims = kind, the two classes, nbTestSamples, vecDim, nbSupportVectors (, degree);
+    params = the support vectors, the dual coefficients, the intercept (, coef0, gamma | gamma).  The test method
+    predicts one sample per call."""
+    kind = row.params["kind"]
+    dims, p = bufs["dims"], bufs["params"]
+    n, dim, nsv = int(dims[3]), int(dims[4]), int(dims[5])
+    bufs["classes"] = dims[1:3].astype(np.int32)
+    sv, dual, at = p[:dim * nsv], p[dim * nsv:dim * nsv + nsv], dim * nsv + nsv
+    extra = ()
+    if kind == "polynomial":
+        extra = (int(dims[6]), p[at + 1], p[at + 2])         # degree, coef0, gamma
+    elif kind == "rbf":
+        extra = (p[at + 1],)                                 # gamma
+    S = lib.instance(row.func)
+    getattr(lib, f"arm_svm_{kind}_init_f32")(S, nsv, dim, p[at], dual, sv, bufs["classes"], *extra)
+    out = Out("q31", bufs["ref"].size)
+    fn = getattr(lib, row.func)
+    for i in range(n):
+        fn(S, bufs["samples"][i * dim:(i + 1) * dim], out.words[i:i + 1])
+    return {"output": out}
+
+
+def _bayes_call(lib, bufs, row):
+    """setUp (BayesF32.cpp:41-77): dims = nbPatterns, classNb, vecDim; params = theta, sigma, the class priors, epsilon.
+    One prediction per call; the class's log-probabilities go to the next classNb words of outputProbas."""
+    dims, p = bufs["dims"], bufs["params"]
+    n, c, d = int(dims[0]), int(dims[1]), int(dims[2])
+    S = lib.instance(row.func)
+    S.vectorDimension, S.numberOfClasses = d, c
+    S.theta, S.sigma, S.classPriors = (lib.pointer(p[k * c * d:]) for k in range(3))
+    S.epsilon = p[c + 2 * c * d]
+    probas, tmp, predicts = Out("f32", n * c), Out("f32", n * c), Out("q15", n)
+    for i in range(n):
+        predicts.words[i] = lib.arm_gaussian_naive_bayes_predict_f32(S, bufs["input"][i * d:(i + 1) * d],
+                                                                     probas.words[i * c:(i + 1) * c], tmp.words)
+    return {"output": probas, "predicts": predicts, "tmp": tmp}
+
+
+def _ml_rows():
+    rows = []
+    for k, kind in enumerate(("linear", "polynomial", "rbf"), 1):
+        rows.append(Row("SVMF32", k, f"test_svm_{kind}_predict_f32", "", f"arm_svm_{kind}_predict_f32",
+                        "Testing/Source/Tests/SVMF32.cpp:6-62,84-251",
+                        {"samples": (f"Samples{k}_f32", None), "params": (f"Params{k}_f32", None),
+                         "dims": (f"Dims{k}_s16", None), "ref": (f"Reference{k}_s32", None)}, {}, {"kind": kind, "init": f"arm_svm_{kind}_init_f32"},
+                        _svm_call, [("eq", "output", "ref", None)], True))
+    rows.append(Row("BayesF32", 1, "test_gaussian_naive_bayes_predict_f32", "", "arm_gaussian_naive_bayes_predict_f32",
+                    "Testing/Source/Tests/BayesF32.cpp:8-83",
+                    {"input": ("Inputs1_f32", None), "params": ("Params1_f32", None), "dims": ("Dims1_s16", None),
+                     "probas": ("Probas1_f32", None), "ref": ("Predicts1_s16", None)}, {}, {}, _bayes_call,
+                    [("rel", "output", "probas", metrics.BAYES_TOL["rel"]), ("eq", "predicts", "ref", None)], True))
+    return rows
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# DistanceTestsF32 (Testing/Source/Tests/DistanceTestsF32.cpp, desc.txt:2083-2131)
+CALLS[("DistanceTestsF32", "test_minkowski_distance_f32")] = "arm_minkowski_distance_f32"
+
+
+def _distance_call(lib, bufs, row):
+    """dims = nbPatterns, vecDim; one distance per pair of vecDim words.  arm_correlation_distance_f32 changes its
+    inputs, so the test hands it copies in tmpA / tmpB (DistanceTestsF32.cpp:180-203)."""
+    n, d = int(bufs["dims"][0]), int(bufs["dims"][1])
+    step = int(bufs["dims"][2]) if row.params.get("packed") else d       # DistanceTestsU32: bitVecDim words of vecDim bools
+    outs = {"output": Out("f32", n)}
+    fn = getattr(lib, row.func)
+    if "correlation" in row.func:
+        outs["tmpA"], outs["tmpB"] = Out("f32", d), Out("f32", d)
+    for i in range(n):
+        a, b = (bufs[k][i * step:(i + 1) * step] for k in ("inputA", "inputB"))
+        if "tmpA" in outs:
+            outs["tmpA"].words[:], outs["tmpB"].words[:] = a, b
+            a, b = outs["tmpA"].words, outs["tmpB"].words
+        outs["output"].words[i] = fn(a, b, d)
+    return outs
+
+
+def _dtw_call(lib, bufs, row):
+    """test_dtw_distance_f32 (DistanceTestsF32.cpp:8-102): the distance matrix |query[q] - template[t]|; the distance
+    without a window and its path; with a Sakoe-Chiba window of 5; a Sakoe-Chiba window of 3 must be refused
+    (ARM_MATH_ARGUMENT_ERROR: the last cell is outside it); with a slanted band of 1.  The test recomputes the
+    distances inside each window only, which leaves the matrix as it was.  ASSERT_EQ_PARTIAL compares the first
+    2 * pathLength words of the path."""
+    a, b = bufs["inputA"], bufs["inputB"]
+    q, t = a.size, b.size
+    out, path, plen = Out("f32", 3), Out("q15", 2 * (q + t)), Out("u32", 1)
+    tmp = {"tmpA": Out("f32", q * t), "tmpB": Out("f32", q * t), "tmpC": Out("q7", q * t)}
+    tmp["tmpA"].words[:] = np.abs(a[:, None] - b[None, :]).reshape(-1)
+    dist, cost, win = (lib.matrix(k, q, t, tmp[n].words) for k, n in (("f32", "tmpA"), ("f32", "tmpB"), ("q7", "tmpC")))
+
+    def want(step, status, expected=0):
+        if status != expected:
+            out.violations.append(("status", step))
+    want("no window", lib.arm_dtw_distance_f32(dist, None, cost, out.words[0:1]))
+    lib.arm_dtw_path_f32(cost, path.words, plen.words)
+    want("init sakoe 5", lib.arm_dtw_init_window_q7(dr.SAKOE_CHIBA, 5, win))
+    want("sakoe 5", lib.arm_dtw_distance_f32(dist, win, cost, out.words[1:2]))
+    want("init sakoe 3", lib.arm_dtw_init_window_q7(dr.SAKOE_CHIBA, 3, win))
+    want("sakoe 3", lib.arm_dtw_distance_f32(dist, win, cost, out.words[2:3]), -1)
+    want("init slanted 1", lib.arm_dtw_init_window_q7(dr.SLANTED_BAND, 1, win))
+    want("slanted 1", lib.arm_dtw_distance_f32(dist, win, cost, out.words[2:3]))
+    path.words = path.buf[:min(2 * int(plen.words[0]), path.n)]
+    return dict(tmp, output=out, path=path, pathLength=plen)
+
+
+def _distance_rows():
+    rows = []
+    tol = metrics.DISTANCE_TOL["abs"]
+    src = "Testing/Source/Tests/DistanceTestsF32.cpp"
+    for k, name in enumerate(("braycurtis", "canberra", "chebyshev", "cityblock", "correlation", "cosine", "euclidean",
+                              "jensenshannon"), 1):
+        a, b = ("InputA8_f32", "InputB8_f32") if name == "jensenshannon" else ("InputA1_f32", "InputB1_f32")
+        rows.append(Row("DistanceTestsF32", k, f"test_{name}_distance_f32", "", f"arm_{name}_distance_f32",
+                        f"{src}: test_{name}_distance_f32, setUp case {k}",
+                        {"inputA": (a, None), "inputB": (b, None), "dims": ("Dims1_s16", None), "ref": (f"Ref{k}_f32", None)},
+                        {}, {}, _distance_call, [("near", "output", "ref", tol)], True))
+    rows.append(Row("DistanceTestsF32", 10, "test_dtw_distance_f32", "", "arm_dtw_distance_f32", f"{src}:8-102,391-407",
+                    {"inputA": ("Query10_f32", None), "inputB": ("Template10_f32", None), "ref": ("DTWRef10_f32", None),
+                     "refPath": ("PathRef10_s16", None)}, {},
+                    {"needs": ("arm_dtw_path_f32", "arm_dtw_init_window_q7")}, _dtw_call,
+                    [("near", "output", "ref", tol), ("eq_partial", "path", "refPath", None)], True))
+    # DistanceTestsU32 (DistanceTestsU32.cpp, desc.txt:2133-2166): packed booleans; dice is ASSERT_REL_ERROR, the rest
+    # ASSERT_NEAR_EQ, both with ERROR_THRESHOLD
+    tol = metrics.DISTANCE_TOL["bool"]
+    for k, name in enumerate(dr.BOOL_FUNCS, 1):
+        rows.append(Row("DistanceTestsU32", k, f"test_{name}_distance", "", f"arm_{name}_distance",
+                        f"Testing/Source/Tests/DistanceTestsU32.cpp: test_{name}_distance, setUp case {k}",
+                        {"inputA": ("InputA1_u32", None), "inputB": ("InputB1_u32", None), "dims": ("Dims1_s16", None),
+                         "ref": (f"Ref{k}_f32", None)}, {}, {"packed": True}, _distance_call,
+                        [("rel" if name == "dice" else "near", "output", "ref", tol)], True))
+    return rows
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# BinaryTests F32 / Q31 / Q15 / Q7 (Testing/Source/Tests/BinaryTests*.cpp, desc.txt:3641-3779): matrix products
+MAXMATRIXDIM = {"f32": 40, "q31": 40, "q15": 40, "q7": 47}        # BinaryTests*.cpp: the bound of the patterns' dimensions
+
+
+def _binary_call(lib, bufs, row):
+    """LOADDATA2 / PREPAREDATA2: dims holds (rows, internal, columns) per product; every product reads the first words of
+    the two inputs again (the input pointers do not advance), copied into a and b; the outputs follow one another and
+    the words behind each must still be untouched (checkInnerTail).  q15 / q7 / opt_q31 take a scratch buffer."""
+    t, c = row.params["t"], row.params["words"]              # words per element: 2 for the complex products
+    out = Out(t, bufs["ref"].size)
+    top = MAXMATRIXDIM[t] ** 2
+    a, b = Out(t, c * top), Out(t, c * top)
+    outs = {"output": out, "tmpA": a, "tmpB": b}
+    extra = []
+    if row.params["scratch"]:
+        outs["tmp"] = Out(t, 2 * top)
+        extra = [outs["tmp"].words]
+    fn = getattr(lib, row.func)
+    dims = bufs["dims"]
+    at = 0
+    per = 4 if t in ("q15", "q7") else 3                     # q15 / q7: a fourth word, shift, that the tests do not use
+    for i in range(dims.size // per):
+        rows, inner, cols = (int(v) for v in dims[per * i:per * i + 3])
+        a.words[:c * rows * inner] = bufs["input1"][:c * rows * inner]
+        b.words[:c * inner * cols] = bufs["input2"][:c * inner * cols]
+        shift = int(dims[per * i + 3]) if row.params.get("shift") else 0
+        if shift:                                            # test_mat_mult_fast_q15: a >> shift in, the product << shift out
+            lib.arm_shift_q15(bufs["input1"], -shift, a.words, rows * inner)
+        status = fn(lib.matrix(t, rows, inner, a.words), lib.matrix(t, inner, cols, b.words),
+                    lib.matrix(t, rows, cols, out.words[at:]), *extra)
+        if shift:
+            lib.arm_shift_q15(out.words[at:], shift, out.words[at:], rows * cols)
+        if status != 0:
+            out.violations.append(("status", i))
+        if row.func == "arm_mat_cmplx_mult_f32":            # its contract (README): within the fmaf chain's bound
+            A = a.words[:2 * rows * inner].reshape(rows, 2 * inner)
+            B = b.words[:2 * inner * cols].reshape(inner, 2 * cols)
+            got = out.words[at:at + 2 * rows * cols].reshape(rows, 2 * cols).astype(np.float64)
+            if not np.all(np.abs(got - cmat.exact64(A, B)) <= cmat.bound(A, B)):
+                out.violations.append(("fmaf bound", i))
+        at += c * rows * cols
+        if out.buf[at:].tobytes() != br.marked(t, out.buf.size - at).tobytes():
+            out.violations.append(("inner tail", at))
+    return outs
+
+
+RESTATED = ("arm_mat_mult_f32",)                            # not the reference's words: the restatement's
+
+
+def _binary_rows():
+    tol = metrics.BINARY_TOL
+    rows = []
+
+    def add(t, index, method, label, func, cplx, checks, lines, exact=True):
+        s = "C" if cplx else ""
+        rows.append(Row(f"BinaryTests{t.upper()}", index, method, label, func,
+                        f"Testing/Source/Tests/BinaryTests{t.upper()}.cpp:{lines}",
+                        {"input1": (f"InputA{s}1_{t}", None), "input2": (f"InputB{s}1_{t}", None),
+                         "dims": ("DimsBinary1_s16", None), "ref": (f"Ref{'Cmplx' if cplx else ''}Mul1_{t}", None)}, {},
+                        {"t": t, "words": 2 if cplx else 1, "scratch": func.endswith(("q15", "q7", "opt_q31")),
+                         "shift": "fast_q15" in func, "needs": ("arm_shift_q15",) if "fast_q15" in func else ()},
+                        _binary_call, checks, exact))
+
+    f32 = [("close", "output", "ref", (tol["f32"]["abs"], tol["f32"]["rel"])), ("snr", "output", "ref", tol["f32"]["snr"])]
+    # the f32 products run on the matrix cores as a k-ordered fmaf chain (README), not the reference's mul-then-add:
+    # next to the suite's thresholds, arm_mat_cmplx_mult_f32 keeps the chain's error bound (_binary_call) and
+    # arm_mat_mult_f32 the chain's own words, which the restatement gives (RESTATED, checked on the GPU)
+    add("f32", 1, "test_mat_mult_f32", "test mult", "arm_mat_mult_f32", False, f32, "61-88", exact=False)
+    add("f32", 2, "test_mat_cmplx_mult_f32", "test complex mult", "arm_mat_cmplx_mult_f32", True, f32, "93-121", exact=False)
+    q = tol["q31"]
+    q31 = [("snr", "output", "ref", q["snr"]), ("near_eq", "output", "ref", q["abs"])]
+    add("q31", 1, "test_mat_mult_q31", "test mult", "arm_mat_mult_q31", False, q31, "61-98")
+    add("q31", 2, "test_mat_cmplx_mult_q31", "test complex mult", "arm_mat_cmplx_mult_q31", True, q31, "test_mat_cmplx_mult_q31")
+    add("q31", 3, "test_mat_mult_opt_q31", "test mult opt", "arm_mat_mult_opt_q31", False, q31, "test_mat_mult_opt_q31")
+    add("q31", 4, "test_mat_mult_fast_q31", "test mult", "arm_mat_mult_fast_q31", False, q31, "100-137")
+    q = tol["q15"]
+    low = [("snr", "output", "ref", q["snr_low"]), ("near_eq", "output", "ref", q["abs_high"])]
+    add("q15", 1, "test_mat_mult_q15", "test mult", "arm_mat_mult_q15", False, low, "87-131")
+    add("q15", 2, "test_mat_cmplx_mult_q15", "test complex mult", "arm_mat_cmplx_mult_q15", True,
+        [("snr", "output", "ref", q["snr_mult"]), ("near_eq", "output", "ref", q["abs"])], "185-214")
+    add("q15", 3, "test_mat_mult_fast_q15", "test mult", "arm_mat_mult_fast_q15", False, low, "133-180")
+    q = tol["q7"]
+    add("q7", 1, "test_mat_mult_q7", "test mult", "arm_mat_mult_q7", False,
+        [("snr", "output", "ref", q["snr"]), ("near_eq", "output", "ref", q["abs"])], "78-126")
+    return rows
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# UnaryTests F32 / Q31 / Q15 / Q7 (Testing/Source/Tests/UnaryTests*.cpp, desc.txt:3344-3545)
+CALLS[("UnaryTestsF32", "test_householder_f32")] = "arm_householder_f32"
+CALLS[("UnaryTestsF32", "test_mat_qr_f32")] = "arm_mat_qr_f32"
+SINGULAR = -5                                               # ARM_MATH_SINGULAR
+
+
+class Computed:
+    """Words the test method computes itself (no library writes them): they have no tail to watch."""
+
+    def __init__(self, words):
+        self.words, self.n, self.violations = words, words.size, []
+
+    def tail_empty(self):
+        return True
+
+
+def _unary_call(lib, bufs, row):
+    """LOADDATA1 / LOADDATA2 / LOADVECDATA2 and the PREPAREDATA* macros.  shape "ew" (add, sub, scale, transposes,
+    matrix x vector): dims holds (rows, columns) pairs and every call reads the first words of the inputs again.
+    shape "square" (inverse, Cholesky): one dimension per matrix, the inputs advance; the last matrix of the inverse
+    test is singular and must be refused.  shape "solve": (rows, columns) pairs, a rows x rows triangle and a rows x
+    columns right-hand side, both advancing.  The words behind every call's output must be untouched."""
+    p = row.params
+    t, op, c = p["t"], p["op"], p.get("words", 1)
+    top = c * MAXMATRIXDIM[t] ** 2
+    out, a, b = Out(t, bufs["ref"].size), Out(t, top), Out(t, top)
+    fn = getattr(lib, row.func)
+    dims = bufs["dims"]
+    per = 1 if p["shape"] == "square" else 2
+    count = dims.size // per
+    if p.get("zeroed"):                                      # arm_mat_cholesky_f32 writes the lower triangle only: the
+        out.words[:] = 0                                     # pattern's upper triangle is the framework's zeroed memory
+    rest = br.marked(t, out.buf.size)
+    rest[:out.n] = out.words
+    at = i1 = i2 = 0
+    for i in range(count):
+        rows = int(dims[per * i])
+        cols = rows if per == 1 else int(dims[per * i + 1])
+        n1 = rows * rows if p["shape"] == "solve" else c * rows * cols
+        a.words[:n1] = bufs["input1"][i1:i1 + n1]
+        A = lib.matrix(t, rows, rows if p["shape"] == "solve" else cols, a.words)
+        produced, expected = c * rows * cols, 0
+        if op == "vec_mult":
+            b.words[:cols] = bufs["input2"][:cols]
+            fn(A, b.words, out.words[at:])
+            status, produced = 0, rows
+        else:
+            Cm = lib.matrix(t, *((cols, rows) if "trans" in op else (rows, cols)), out.words[at:])
+            if op in ("add", "sub", "solve_upper_triangular", "solve_lower_triangular"):
+                b.words[:c * rows * cols] = bufs["input2"][i2:i2 + c * rows * cols]
+                status = fn(A, lib.matrix(t, rows, cols, b.words), Cm)
+            elif op == "scale":
+                status = fn(A, *p["scalar"], Cm)
+            else:
+                status = fn(A, Cm)
+            if op == "inverse" and i == count - 1:
+                expected = SINGULAR
+        if status != expected:
+            out.violations.append(("status", i))
+        at += produced
+        if p["shape"] != "ew":
+            i1, i2 = i1 + n1, i2 + c * rows * cols
+        if out.buf[at:].tobytes() != rest[at:].tobytes():
+            out.violations.append(("inner tail", at))
+    return {"output": out, "tmpA": a, "tmpB": b}
+
+
+def _ldlt_call(lib, bufs, row):
+    """test_mat_ldl_f32 (UnaryTestsF32.cpp:683-856): per matrix, d and the permutation are cleared, arm_mat_ldlt_f32
+    runs, and the test forms P A P^T and L D L^T in double (compute_ldlt_error); the two must be close."""
+    x, dims = bufs["input1"], bufs["dims"]
+    ll, d, perm = Out("f32", x.size), Out("f32", x.size), Out("u16", int(dims.sum()))
+    a = Out("f32", MAXMATRIXDIM["f32"] ** 2)
+    papt, ldlt = np.zeros(x.size), np.zeros(x.size)
+    at = pa = 0
+    for i, n in enumerate(int(v) for v in dims):
+        a.words[:n * n] = x[at:at + n * n]
+        d.words[at:at + n * n] = 0
+        perm.words[pa:pa + n] = 0
+        status = lib.arm_mat_ldlt_f32(lib.matrix("f32", n, n, a.words), lib.matrix("f32", n, n, ll.words[at:]),
+                                      lib.matrix("f32", n, n, d.words[at:]), perm.words[pa:])
+        if status != 0:
+            ll.violations.append(("status", i))
+        P = np.eye(n)
+        for r in range(n):                                   # SWAP_ROWS(tmpa, r, outpp[r])
+            P[[r, int(perm.words[pa + r])]] = P[[int(perm.words[pa + r]), r]]
+        A, L, D = (w[:n * n].reshape(n, n).astype(np.float64) for w in (a.words, ll.words[at:], d.words[at:]))
+        papt[at:at + n * n] = (P @ (A @ P.T)).reshape(-1)
+        ldlt[at:at + n * n] = (L @ (D @ L.T)).reshape(-1)
+        at, pa = at + n * n, pa + n
+        for o, k in ((ll, at), (d, at), (perm, pa)):
+            if o.buf[k:].tobytes() != br.marked(o.t, o.buf.size - k).tobytes():
+                o.violations.append(("inner tail", k))
+    return {"output": ll, "d": d, "perm": perm, "tmpA": a, "outputa": Computed(papt), "outputb": Computed(ldlt)}
+
+
+def _unary_rows():
+    rows = []
+    tol = metrics.UNARY_TOL
+
+    def add(t, index, method, label, op, load, checks, shape="ew", lines="", **params):
+        func = f"arm_mat_{op}_{t}"
+        rows.append(Row(f"UnaryTests{t.upper()}", index, method, label, func,
+                        f"Testing/Source/Tests/UnaryTests{t.upper()}.cpp: {method}{lines}", load, {},
+                        dict(params, t=t, op=op, shape=shape), _unary_call, checks, True))
+
+    def common(t, first, checks, vec_checks=None):
+        half = {"f32": (np.float32(0.5),), "q31": (0x40000000, 0), "q15": (0x4000, 0)}.get(t)
+        k = first
+        for label, op, ref, two in (("test matrix add", "add", "RefAdd1", True), ("test matrix sub", "sub", "RefSub1", True),
+                                    ("test matrix scale", "scale", "RefScale1", False),
+                                    ("test matrix transpose", "trans", "RefTranspose1", False)):
+            if t == "q7" and op != "trans":
+                continue
+            ld = {"input1": (f"InputA1_{t}", None), "dims": ("DimsUnary1_s16", None), "ref": (f"{ref}_{t}", None)}
+            if two:
+                ld["input2"] = (f"InputB1_{t}", None)
+            add(t, k, f"test_mat_{op}_{t}", label, op, ld, checks, scalar=half)
+            k += 1
+        return k
+
+    def vec(t, k, checks):
+        add(t, k, f"test_mat_vec_mult_{t}", "test mat mult vec", "vec_mult",
+            {"input1": (f"InputA1_{t}", None), "input2": (f"InputVec1_{t}", None), "dims": ("DimsUnary1_s16", None),
+             "ref": (f"RefVecMul1_{t}", None)}, checks)
+
+    def ctrans(t, k, checks):
+        add(t, k, f"test_mat_cmplx_trans_{t}", "test matrix complex transpose", "cmplx_trans",
+            {"input1": (f"InputAC1_{t}", None), "dims": ("DimsUnary1_s16", None), "ref": (f"RefTransposeC1_{t}", None)},
+            checks, words=2)
+
+    def f32(name):
+        q = tol["f32"][name]
+        return [("snr", "output", "ref", q["snr"]), ("close", "output", "ref", (q["abs"], q["rel"]))]
+    common("f32", 1, f32("default"))
+    add("f32", 5, "test_mat_inverse_f32", "test matrix inverse", "inverse",
+        {"input1": ("InputInvert1_f32", None), "dims": ("DimsInvert1_s16", None), "ref": ("RefInvert1_f32", None)},
+        f32("inverse"), shape="square", lines=" (505-562)")
+    vec("f32", 6, f32("default"))
+    ctrans("f32", 7, f32("default"))
+    add("f32", 8, "test_mat_cholesky_dpo_f32", "test matrix cholesky decomposition", "cholesky",
+        {"input1": ("InputCholeskyDPO1_f32", None), "dims": ("DimsCholeskyDPO1_s16", None),
+         "ref": ("RefCholeskyDPO1_f32", None)}, f32("cholesky"), shape="square", lines=" (564-599)", zeroed=True)
+    for k, (op, ref, mat) in enumerate((("solve_upper_triangular", "RefUTSolve1", "InputMatrixUTSolve1"),
+                                        ("solve_lower_triangular", "RefLTSolve1", "InputMatrixLTSolve1")), 9):
+        add("f32", k, f"test_{op}_f32", "test " + op.replace("_", " "), op,
+            {"input1": (f"{mat}_f32", None), "input2": ("InputVectorLTSolve1_f32", None),
+             "dims": ("DimsLTSolve1_s16", None), "ref": (f"{ref}_f32", None)}, f32("default"), shape="solve")
+    for k, kind in ((11, "DPO"), (12, "SDPO")):
+        q = tol["f32"]["ldlt" if kind == "DPO" else "ldlt_sdpo"]
+        rows.append(Row("UnaryTestsF32", k, "test_mat_ldl_f32", f"test matrix LDL decomposition {kind}", "arm_mat_ldlt_f32",
+                        "Testing/Source/Tests/UnaryTestsF32.cpp:683-856",
+                        {"input1": (f"InputCholesky{kind}1_f32", None), "dims": (f"DimsCholesky{kind}1_s16", None)}, {}, {},
+                        _ldlt_call, [("close", "outputa", "outputb", (q["abs"], q["rel"]))], True))
+    for t in ("q31", "q15"):
+        q = tol[t]
+        chk = [("snr", "output", "ref", q["snr"]), ("near_eq", "output", "ref", q["abs"])]
+        k = common(t, 1, chk)
+        vec(t, k, chk)
+        ctrans(t, k + 1, chk)
+    q = tol["q7"]
+    common("q7", 1, [("snr", "output", "ref", q["snr"]), ("near_eq", "output", "ref", q["abs"])])
+    vec("q7", 2, [("snr", "output", "ref", q["snr_low"]), ("near_eq", "output", "ref", q["abs"])])
+    return rows
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# SupportTests F32 / Q31 / Q15 / Q7 and SupportBarTestsF32 (Testing/Source/Tests/Support*.cpp, desc.txt:634-839)
+SUPPORT_T = {"f32": "float", "q31": "q31", "q15": "q15", "q7": "q7"}
+for _s, _m, _f in (("SupportTestsF32", "test_float_to_f64", "arm_float_to_f64"),
+                   ("SupportTestsQ31", "test_q31_f64", "arm_q31_to_f64"), ("SupportTestsQ15", "test_q15_f64", "arm_q15_to_f64"),
+                   ("SupportTestsQ7", "test_q7_f64", "arm_q7_to_f64")):
+    CALLS[(_s, _m)] = _f
+# the inline accessors of arm_math_memory.h (SupportTestsQ15.cpp:105-168, SupportTestsQ7.cpp:105-150)
+for _m in ("read_q15x2", "read_q15x2_ia", "read_q15x2_da", "write_q15x2_ia", "write_q15x2"):
+    CALLS[("SupportTestsQ15", "test_" + _m)] = _m
+for _m in ("read_q7x4_ia", "read_q7x4_da", "write_q7x4_ia"):
+    CALLS[("SupportTestsQ7", "test_" + _m)] = _m
+SORT_ASCENDING = 1                                          # ARM_SORT_ASCENDING
+
+
+def _support_call(lib, bufs, row):
+    """One call over nbSamples words: arm_copy_*, arm_fill_* (val 1.1 / 0x4000 / 0x40), the conversions, the weighted
+    average (its value goes to outp[0] and is compared with refp[offset]), the sorts (init, then one call; `in`: pSrc
+    == pDst on the input buffer, whose tail is then watched; the merge sort's init takes a buffer of nbSamples)."""
+    p = row.params
+    kind, n = p["kind"], p["n"]
+    fn = getattr(lib, row.func)
+    if kind == "fill":
+        out = Out(p["out_t"], n)
+        fn(p["val"], out.words, n)                          # ASSERT_EQ(val, outp[i]) for every i: consts["ref"]
+        return {"output": out}
+    x = bufs["input"]
+    if kind == "weighted_average":
+        out = Out("f32", 1)
+        out.words[0] = fn(x, bufs["coefs"], n)
+        return {"output": out}
+    if kind in ("sort", "merge_sort"):
+        out = Out("f32", n)
+        src = out.words if p["in_place"] else x
+        if p["in_place"]:
+            out.words[:] = x
+        S = lib.instance(row.func)
+        if kind == "sort":
+            lib.arm_sort_init_f32(S, p["alg"], SORT_ASCENDING)
+            fn(S, src, out.words, n)
+            return {"output": out}
+        tmp = Out("f32", n)
+        lib.arm_merge_sort_init_f32(S, SORT_ASCENDING, tmp.words)
+        fn(S, src, out.words, n)
+        return {"output": out, "tmp": tmp}
+    out = Out(p["out_t"], n)
+    fn(x, out.words, n)
+    return {"output": out}
+
+
+def _barycenter_call(lib, bufs, row):
+    """test_barycenter_f32: dims = nbTests, then (nbVecs, vecDim) per test; inputs, weights and outputs advance."""
+    dims = bufs["dims"]
+    out = Out("f32", bufs["ref"].size)
+    ai = ci = oi = 0
+    for i in range(int(dims[0])):
+        nv, dim = int(dims[2 * i + 1]), int(dims[2 * i + 2])
+        lib.arm_barycenter_f32(bufs["input"][ai:], bufs["coefs"][ci:], out.words[oi:], nv, dim)
+        ai, ci, oi = ai + nv * dim, ci + nv, oi + dim
+    return {"output": out}
+
+
+def _support_rows():
+    rows = []
+    tol = metrics.SUPPORT_TOL
+    samples = {"f32": "Samples1_f32", "q15": "Samples3_q15", "q31": "Samples4_q31", "q7": "Samples5_q7"}
+
+    def add(suite, index, method, label, func, load, checks, **params):
+        rows.append(Row(suite, index, method, label, func, f"Testing/Source/Tests/{suite}.cpp: {method}, setUp case {index}",
+                        load, {}, params, _support_call, checks, True))
+
+    def three(suite, first, method, stem, func, lengths, labels, make):
+        for k, (n, lab) in enumerate(zip(lengths, labels)):
+            load, checks, params = make(n)
+            add(suite, first + k, method, f"{stem} {lab}", func, load, checks, n=n, **params)
+
+    nb4, nb8, nb16 = ("nb=3", "nb=4n", "nb=4n+1"), ("nb=7", "nb=8n", "nb=8n+1"), ("nb=15", "nb=16n", "nb=16n+1")
+    # ---- F32
+    s, q = "SupportTestsF32", tol["f32"]
+    for k, n in enumerate((3, 8, 11)):
+        rows.append(Row(s, 1 + k, "test_weighted_average_f32", f"test_weighted_average_f32 {nb4[k]}", "arm_weighted_average_f32",
+                        f"Testing/Source/Tests/{s}.cpp:14-29", {"input": ("Inputs6_f32", n), "coefs": ("Weights6_f32", n),
+                                                                "ref": ("Ref6_f32", None)}, {},
+                        {"kind": "weighted_average", "n": n, "refOffset": k}, _support_call,
+                        [("rel", "output", "ref", q["rel"])], True))
+    three(s, 4, "test_copy_f32", "test_copy_f32", "arm_copy_f32", (3, 8, 11), nb4,
+          lambda n: ({"input": (samples["f32"], n)}, [("eq", "output", "input", None)], {"kind": "copy", "out_t": "f32"}))
+    three(s, 7, "test_fill_f32", "test_fill_f32", "arm_fill_f32", (3, 8, 11), nb4,
+          lambda n: ({}, [("eq", "output", "ref", None)], {"kind": "fill", "out_t": "f32", "val": np.float32(1.1),
+                                                                  "consts": {"ref": np.full(n, 1.1, dtype=np.float32)}}))
+    for first, d, lengths, labels in ((10, "q15", (7, 16, 17), nb8), (13, "q31", (3, 8, 11), nb4), (16, "q7", (15, 32, 33), nb16)):
+        three(s, first, f"test_float_to_{d}", f"test_float_{d}", f"arm_float_to_{d}", lengths, labels,
+              lambda n, d=d: ({"input": (samples["f32"], n), "ref": (samples[d], n)},
+                              [("near_eq", "output", "ref", q[f"abs_{d}"])], {"kind": "convert", "out_t": d}))
+    k = 19
+    sorts = (("bitonic", 0, (("nb=16 outofoplace", "out", 16, "Input8", "Reference8"), ("nb=32 outofplace", "out", 32, "Input9", "Reference9"),
+                             ("nb=32 inplace", "in", 32, "Input9", "Reference9"), ("nb=16 const", "const", 16, "Input10", "Reference10"))),)
+    plain = (("nb=11 outofplace", "out", 11, "Input7", "Reference7"), ("nb=11 inplace", "in", 11, "Input7", "Reference7"),
+             ("nb=16 const", "const", 16, "Input10", "Reference10"))
+    sorts += tuple((name, alg, plain) for name, alg in (("bubble", 1), ("heap", 2), ("insertion", 3)))
+    sorts += (("merge", None, (plain[0], plain[2])),) + tuple((name, alg, plain) for name, alg in (("quick", 4), ("selection", 5)))
+    for name, alg, cases in sorts:
+        for label, how, n, inp, ref in cases:
+            add(s, k, f"test_{name}_sort_{how}_f32", f"test_{name}_sort_f32 {label}",
+                "arm_merge_sort_f32" if alg is None else "arm_sort_f32",
+                {"input": (f"{inp}_f32", n), "ref": (f"{ref}_f32", None)}, [("eq", "output", "ref", None)],
+                kind="merge_sort" if alg is None else "sort", alg=alg, in_place=how == "in", n=n,
+                needs=("arm_merge_sort_init_f32",) if alg is None else ("arm_sort_init_f32",))
+            k += 1
+    # ---- Q31 / Q15 / Q7: copy, fill, to float, to the two other fixed-point types
+    plan = {"q31": (nb4, {"copy": (3, 8, 11), "float": (7, 16, 17), "q15": (3, 8, 11), "q7": (15, 32, 33)}, ("q15", "q7"), 0x4000),
+            "q15": (nb8, {"copy": (7, 16, 23), "float": (7, 16, 23), "q31": (7, 16, 23), "q7": (7, 16, 23)}, ("q31", "q7"), 0x4000),
+            "q7": (nb16, {"copy": (15, 32, 47), "float": (15, 32, 47), "q31": (15, 32, 47), "q15": (15, 32, 47)}, ("q31", "q15"), 0x40)}
+    for t, (labels, lengths, others, val) in plan.items():
+        s, q = f"SupportTests{t.upper()}", tol[t]
+        three(s, 1, f"test_copy_{t}", f"test_copy_{t}", f"arm_copy_{t}", lengths["copy"], labels,
+              lambda n, t=t: ({"input": (samples[t], n)}, [("eq", "output", "input", None)], {"kind": "copy", "out_t": t}))
+        three(s, 4, f"test_fill_{t}", f"test_fill_{t}", f"arm_fill_{t}", lengths["copy"], labels,
+              lambda n, t=t, val=val: ({}, [("eq", "output", "ref", None)], {"kind": "fill", "out_t": t, "val": val,
+                                                                                "consts": {"ref": np.full(n, val, dtype=DT[t])}}))
+        fchk = [("close", "output", "ref", (q["abs_float"], q["rel"]))] if t == "q7" else [("rel", "output", "ref", q["rel"])]
+        three(s, 7, f"test_{t}_float", f"test_{t}_float", f"arm_{t}_to_float", lengths["float"], labels,
+              lambda n, t=t, fchk=fchk: ({"input": (samples[t], n), "ref": (samples["f32"], n)}, fchk,
+                                         {"kind": "convert", "out_t": "f32"}))
+        for j, d in enumerate(others):
+            three(s, 10 + 3 * j, f"test_{t}_{d}", f"test_{t}_{d}", f"arm_{t}_to_{d}", lengths[d], labels,
+                  lambda n, t=t, d=d: ({"input": (samples[t], n), "ref": (samples[d], n)},
+                                       [("near_eq", "output", "ref", q[f"abs_{d}"])], {"kind": "convert", "out_t": d}))
+    rows.append(Row("SupportBarTestsF32", 1, "test_barycenter_f32", "test_barycenter_f32", "arm_barycenter_f32",
+                    "Testing/Source/Tests/SupportBarTestsF32.cpp:6-60",
+                    {"input": ("Inputs1_f32", None), "coefs": ("Weights1_f32", None), "ref": ("Ref1_f32", None),
+                     "dims": ("Dims1_s16", None)}, {}, {}, _barycenter_call, [("near", "output", "ref", tol["bar"])], True))
+    return rows
+
+
+def _all_rows():
+    rows = _biquad_rows() + _unary_rows() + _support_rows() + _fastmath_rows() + _ml_rows() + _distance_rows() + _binary_rows()
+    for t in ("f32", "q31", "q15"):
+        rows += _complex_rows(t)
+    for t in ("f32", "q31", "q15", "q7"):
+        rows += _basic_rows(t)
+    for t in ("f32", "q31", "q15", "q7"):
+        rows += _stats_rows(t)
+    return rows
+
+
+ROWS = _all_rows()
+BY_ID = {r.id: r for r in ROWS}
+assert len(BY_ID) == len(ROWS)
+
+
+def methods():
+    """[(suite, method)] in table order: one GPU pytest case each."""
+    seen = []
+    for r in ROWS:
+        if (r.suite, r.method) not in seen:
+            seen.append((r.suite, r.method))
+    return seen
