@@ -62,8 +62,29 @@ def snr_passes(ref, out, threshold):
 CFFT_TOL = {"f32": dict(snr=120, abs=8e-5, rel=2e-5),     # TransformCF32.cpp:6-8
             "q31": dict(snr=90, abs=53),                   # TransformCQ31.cpp:6-7
             "q15": dict(snr=30, abs=15)}                   # TransformCQ15.cpp:6-7
-FIR_TOL = {"f32": dict(snr=120, rel=3e-5),                 # FIRF32.cpp:5,11
-           "q15": dict(snr=59, abs=2)}                     # FIRQ15.cpp:5-7
+FIR_TOL = {"f32": dict(snr=120, rel=3e-5),                 # FIRF32.cpp:5,13
+           "q31": dict(snr=100, abs=2),                    # FIRQ31.cpp:5-7
+           "q15": dict(snr=59, abs=2),                     # FIRQ15.cpp:5-7
+           "q7": dict(snr=10, abs=2)}                      # FIRQ7.cpp:5-7
+# DECIM F32 / Q31 / Q15: the decimators and the interpolators share each suite's pair
+DECIM_TOL = {"f32": dict(snr=120, rel=8.0e-4),             # DECIMF32.cpp:5,13
+             "q31": dict(snr=100, abs=2),                  # DECIMQ31.cpp:5,13
+             "q15": dict(snr=70, abs=5)}                   # DECIMQ15.cpp:5,13
+# MISC F32 / Q31 / Q15 / Q7: arm_conv_* / arm_correlate_* / arm_conv_partial_*; the fast and opt forms of the partial
+# convolution have ABS_ERROR_FAST_<type>
+MISC_TOL = {"f32": dict(snr=120, abs=1.0e-5, rel=1.0e-6),  # MISCF32.cpp:8,15-16
+            "q31": dict(snr=100, abs=2, abs_fast=11),      # MISCQ31.cpp:8,15-17
+            "q15": dict(snr=65, abs=10, abs_fast=20),      # MISCQ15.cpp:8,15-17
+            "q7": dict(snr=15, abs=5, abs_fast=5)}         # MISCQ7.cpp:8,15-16
+# TransformR F32 / Q31 / Q15.  Q31 asserts no SNR and has a bound of its own for the inverse of 4096 samples
+# (scaling == 12); Q15's inverse has its own pair
+RFFT_TOL = {"f32": dict(snr=120, abs=5.0e-5, rel=1.0e-5),                                    # TransformRF32.cpp:7-9
+            "q31": dict(abs=33, abs_ifft=52000, abs_ifft_long=209000),                       # TransformRQ31.cpp:8-10,90
+            "q15": dict(snr=40, snr_ifft=25, abs=14, abs_ifft=1250)}                         # TransformRQ15.cpp:7-11
+# MFCC F32 / Q31 / Q15
+MFCC_TOL = {"f32": dict(snr=115, abs=1.0e-5, rel=1.2e-3),  # MFCCF32.cpp:7,15-16
+            "q31": dict(snr=66, abs=49000),                # MFCCQ31.cpp:7,15
+            "q15": dict(snr=34, abs=30)}                   # MFCCQ15.cpp:5-6
 MAT_TOL = dict(snr=120, abs=1e-5, rel=1e-6)                # BinaryTestsF32.cpp:5,13-17
 # Basic Tests F32 / Q31 / Q15 / Q7: SNR_THRESHOLD, REL_ERROR / ABS_ERROR_<type>, the dot products' ABS_ERROR_Q63 (q7:
 # ABS_ERROR_Q31), Q15's MULT_SNR_THRESHOLD (mult and dot_prod), Q7's test_mult_short_q7 (SNR_THRESHOLD - 1.0f)

@@ -682,10 +682,23 @@ def test_mat_mult_q7_batch_and_multi(dsp, torch_gpu, ref):
     assert Cm.cpu().numpy().tobytes() == want.tobytes()
 
 
-def test_mat_mult_q7_pingpong_repeatable(dsp, torch_gpu):
+def _q7_tile_rows_against_the_reference(ref, a, b, got):
+    """The first and the last 256-row tile row of one product against arm_mat_mult_q7 of the reference build
+    (oracle/_ref), called on 65536 // numColsB rows at a time: the reference keeps its output offset in a uint16_t
+    (test_mat_mult_q7_bitexact), so a longer call would place later rows over earlier ones."""
+    m, step = a.shape[0], 65536 // b.shape[1]
+    for r0 in sorted({0, m - 256}):
+        for r in range(r0, r0 + 256, step):
+            st, want = ref.mat_mult_fixed("q7", a[r:r + step], b)
+            assert st == 0
+            assert got[r:r + step].tobytes() == want.tobytes(), (r, np.argwhere(got[r:r + step] != want)[:5])
+
+
+def test_mat_mult_q7_pingpong_repeatable(dsp, torch_gpu, ref):
     """The ping-pong kernel's LDS ordering (DMA wait + barrier before a read, refill two phases
     after the last read) screened by repetition: 1024^3 x 16 (one workgroup per CU) run six times
-    must give the same words every time, and two of the matrices the exact int64 products."""
+    must give the same words every time, and two of the matrices the exact int64 products and, on
+    their first and last tile rows, the reference build's words."""
     torch = torch_gpu
     rng = np.random.default_rng(61)
     a = rng.integers(-128, 128, (16, 1024, 1024)).astype(np.int8)
@@ -702,14 +715,17 @@ def test_mat_mult_q7_pingpong_repeatable(dsp, torch_gpu):
     for i in (0, 11):
         s = np.matmul(a[i].astype(np.int32), b[i].astype(np.int32))
         assert got[i].tobytes() == np.clip(s >> 7, -128, 127).astype(np.int8).tobytes(), i
+        _q7_tile_rows_against_the_reference(ref, a[i], b[i], got[i])
 
 
 @pytest.mark.parametrize("batch,m,k,n", [(1, 4608, 256, 4096), (81, 512, 512, 512)])
-def test_mat_mult_q7_pp2_multitile(dsp, torch_gpu, batch, m, k, n):
+def test_mat_mult_q7_pp2_multitile(dsp, torch_gpu, ref, batch, m, k, n):
     """The 128-deep ping-pong kernel with several tiles per persistent workgroup, so the chunk
     stream (and its refills: B one chunk ahead, A0 two) runs across tile boundaries: 288 tiles
     (XCD-contiguous runs, tiles % 8 == 0) and 81 x 4 = 324 tiles (round robin), against exact
-    products (float64 matmul: |sum| < 2^53)."""
+    products (float64 matmul: |sum| < 2^53), and the first and last tile rows against the reference
+    build: of the one matrix, and of the first, the middle and the last of the 81 (the scalar
+    reference manages under a GMAC/s; all 81 would take a quarter of a minute)."""
     torch = torch_gpu
     rng = np.random.default_rng(batch + m + k)
     a = rng.integers(-128, 128, (batch, m, k)).astype(np.int8)
@@ -721,3 +737,5 @@ def test_mat_mult_q7_pp2_multitile(dsp, torch_gpu, batch, m, k, n):
     want = np.clip(s >> 7, -128, 127).astype(np.int8)
     got = Cm.cpu().numpy()
     assert got.tobytes() == want.tobytes(), np.argwhere(got != want)[:5]
+    for i in sorted({0, batch // 2, batch - 1}):
+        _q7_tile_rows_against_the_reference(ref, a[i], b[i], got[i])

@@ -3,14 +3,18 @@
 Every row must pass the suite's thresholds against the double-precision patterns and give the words the reference build
 gave (tests/golden/suites_*.npz, <row>/ref_words; the README states these families bit-exact).  The negative controls
 plant, in a passing output, a defect just outside each check of each row and a written tail word, and want the row to
-fail on that check; the manifest tests hold tests/golden/suites_manifest.json against the table and against what the
+fail on that check; they disturb a word behind a FIR call's block, and plant four kernel defects (a dropped state
+carry, a late decimator phase, an ignored firstIndex, an inverse RFFT one halving short) that must turn exactly the
+rows red that meet them; the manifest tests hold tests/golden/suites_manifest.json against the table and against what the
 library exports."""
+import ctypes as C
 import math
 import os
 
 import numpy as np
 import pytest
 
+import mfcc_cfg
 import suite_replay as sr
 from suite_replay import patterns, same_words
 
@@ -18,12 +22,15 @@ from suite_replay import patterns, same_words
 @pytest.mark.parametrize("suite,method", sr.methods(), ids=lambda v: v)
 def test_restatements_pass_the_suites(suite, method):
     lib = sr.RestatementLibrary()
+    # the restatement of arm_mfcc_f32 calls the host's logf as the reference does: its words are the recorded ones
+    # where that logf is the one of the generating host (tests/mfcc_cfg.py), the suite's thresholds hold anywhere
+    same_libm = suite != "MFCCF32" or mfcc_cfg.host_libm_status()[0]
     for row in (r for r in sr.ROWS if (r.suite, r.method) == (suite, method)):
         pats = patterns(row)
         outs, failed = sr.run_row(row, lib, pats)
         assert not failed, (row.id, row.cite, failed)
         for name, words in outs.items():
-            if row.exact and name not in sr.SCRATCH:
+            if row.exact and same_libm and name not in sr.SCRATCH:
                 same_words(words, pats[sr.ref_key(row, name)], (row.id, name))
 
 
@@ -158,6 +165,96 @@ def test_a_word_written_past_a_call_s_output_is_reported():
     assert not failed
 
 
+def _with(wraps):
+    """The restatements, with the functions named in wraps {name: fn -> defective fn} replaced."""
+    class Defective(sr.RestatementLibrary):
+        def __getattr__(self, name):
+            fn = super().__getattr__(name)
+            return wraps[name](fn) if name in wraps else fn
+    return Defective()
+
+
+def _red(lib, families):
+    """The ids of the rows of these families that the library fails."""
+    return {r.id for r in sr.ROWS if sr.FAMILIES[r.suite] in families and sr.run_row(r, lib, patterns(r))[1]}
+
+
+@pytest.mark.parametrize("t", ["f32", "q31", "q15", "q7"])
+def test_a_disturbed_fir_inner_tail_word_is_reported(t):
+    """FIR*'s checkInnerTail: a word written behind a call's block is reported after that call, even where the next
+    call overwrites it; only the word behind the last block also breaks the buffer's tail."""
+    row = sr.BY_ID[f"FIR{t.upper()}/01_test_fir_{t}/-"]
+
+    def overrun(fn):
+        def call(S, src, dst, n):
+            fn(S, src, dst, n)
+            whole = dst.base
+            whole[(dst.ctypes.data - whole.ctypes.data) // dst.itemsize + n] = 1
+        return call
+    _, failed = sr.run_row(row, _with({row.func: overrun}), patterns(row))
+    first_block = int(patterns(row)[f"{row.suite}/FirConfigs1_s16"][0])
+    assert ("inner tail", "output", first_block) in failed and ("tail", "output") in failed, failed[:3]
+    assert len([f for f in failed if f[0] == "inner tail"]) == patterns(row)[f"{row.suite}/FirConfigs1_s16"].size
+    assert not [f for f in failed if f[0] in ("snr", "near_eq", "rel")], failed   # every such word but the last is rewritten
+
+
+def _fir_without_state_carry(fn):
+    def call(S, src, dst, n):
+        C.memset(C.cast(S.pState, C.c_void_p), 0, (S.numTaps + n - 1) * src.itemsize)     # as the init left it
+        fn(S, src, dst, n)
+    return call
+
+
+def _decimator_one_phase_late(fn):
+    def call(S, src, dst, n):
+        late = np.concatenate([src[1:n], src[n - 1:n]])     # sample k + 1 where sample k belongs
+        fn(S, late, dst, n)
+    return call
+
+
+def _partial_ignoring_first(fn):
+    def call(a, la, b, lb, dst, first, num, *scratch):
+        head = np.zeros(num, dtype=dst.dtype)
+        status = fn(a, la, b, lb, head, 0, num, *scratch)   # outputs 0 ... num - 1, stored where first ... belong
+        dst[first:first + num] = head
+        return status
+    return call
+
+
+def _inverse_rfft_without_a_halving(fn):
+    def call(S, src, dst):
+        fn(S, src, dst)
+        if S.ifftFlagR:
+            dst[:S.fftLenReal] = (dst[:S.fftLenReal].astype(np.int64) << 1).astype(dst.dtype)
+    return call
+
+
+PLANTED = {
+    # defect: (the functions it is planted in, the families replayed, the rows that must turn red)
+    "the FIR state carry dropped between the two calls":
+        ({f"arm_fir_{t}": _fir_without_state_carry for t in ("f32", "q31", "q15", "q7")}, ("fir",),
+         lambda r: True),
+    "the decimator's phase off by one":
+        ({f"arm_fir_decimate_{t}": _decimator_one_phase_late for t in ("f32", "q31", "q15")}, ("decim",),
+         lambda r: "decimate" in r.func),
+    "first ignored in a partial convolution":
+        ({r.func: _partial_ignoring_first for r in sr.ROWS if "first" in r.params}, ("misc",),
+         lambda r: "first" in r.params),
+    "the RFFT inverse scaling omitted":
+        ({"arm_rfft_q31": _inverse_rfft_without_a_halving, "arm_rfft_q15": _inverse_rfft_without_a_halving},
+         ("transform_r",), lambda r: r.func != "arm_rfft_fast_f32" and r.params["ifft"] == 1),
+}
+
+
+@pytest.mark.parametrize("defect", list(PLANTED))
+def test_a_planted_kernel_defect_turns_its_rows_red(defect):
+    """The defects a filter or transform kernel is likeliest to have: exactly the rows that call the defective function
+    that way fail, every other row of the family stays green."""
+    wraps, families, hit = PLANTED[defect]
+    want = {r.id for r in sr.ROWS if sr.FAMILIES[r.suite] in families and hit(r)}
+    assert want and _red(_with(wraps), families) == want
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the manifest
 def test_manifest_lines_are_replayed_or_skipped_for_want_of_the_function(dsp):
@@ -166,6 +263,8 @@ def test_manifest_lines_are_replayed_or_skipped_for_want_of_the_function(dsp):
     lines = sr.manifest()
     assert len({(e["suite"], e["index"]) for e in lines}) == len(lines)
     assert {e["suite"] for e in lines} == set(sr.FAMILIES)
+    disabled = {(f"Transform{c}{t.upper()}", i) for c, table in (("C", sr.CFFT_DISABLED), ("R", sr.RFFT_DISABLED))
+                for t, indexes in table.items() for i in indexes}
     replayed = set()
     for e in lines:
         rid = sr.row_id(e["suite"], e["index"], e["method"], e["label"])
@@ -177,11 +276,35 @@ def test_manifest_lines_are_replayed_or_skipped_for_want_of_the_function(dsp):
         else:
             assert e["status"].startswith("skipped: ") and len(e["status"]) > len("skipped: "), e
             assert rid not in sr.BY_ID, rid
-            # a condition, not a judgement: no skipped line names a function the library has
             assert e["function"] is not None, e
+            if (e["suite"], e["index"]) in disabled:            # the table names the transform lines desc.txt disables
+                assert e["status"] == "skipped: disabled in the reference's own test description", e
+                disabled.remove((e["suite"], e["index"]))
+                continue
+            # a condition, not a judgement: no other skipped line names a function the library has
             assert e["function"] not in exported, e
             assert not hasattr(dsp.lib, e["function"]), e
+    assert not disabled, disabled
     assert replayed == set(sr.BY_ID)                        # and the table has no row the manifest does not know
+
+
+def test_exempted_checks_are_the_ones_the_generator_recorded():
+    """A check the reference build misses itself is recorded in the manifest with what it measured (outside the
+    bound), only on an inverse fixed-point transform, and never all the checks of a row; the recorded words stay."""
+    recorded = {}
+    for e in sr.manifest():
+        if "reference_fails" in e:
+            row = sr.BY_ID[sr.row_id(e["suite"], e["index"], e["method"], e["label"])]
+            assert e["status"] == "replayed" and e["reference_fails"], e
+            assert row.func in ("arm_cfft_q31", "arm_cfft_q15", "arm_rfft_q31", "arm_rfft_q15") and row.params["ifft"] == 1
+            checks = {(c[0], c[1]): c[3] for c in row.checks}
+            for f in e["reference_fails"]:
+                assert checks[f["check"], f["output"]] == f["bound"], (row.id, f)
+                assert f["measured"] < f["bound"] if f["check"] == "snr" else f["measured"] > f["bound"], (row.id, f)
+            recorded[row.id] = {(f["check"], f["output"]) for f in e["reference_fails"]}
+            assert len(recorded[row.id]) == len(e["reference_fails"]) < len(row.checks), row.id
+            assert row.exact and sr.ref_key(row) in patterns(row), row.id
+    assert sr.exemptions() == recorded
 
 
 def test_documents_quote_the_manifest():
