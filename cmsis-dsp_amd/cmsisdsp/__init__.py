@@ -952,6 +952,123 @@ def arm_mat_mult_fast_q15(pSrcA, pSrcB, pState=None):
     return _amd.arm_mat_mult_fixed("fast_q15", _arr(pSrcA, _np.int16), _arr(pSrcB, _np.int16))
 
 
+# ------------------------------------------------------------------ interpolation (cmsisdsp_interpolation.c)
+class arm_linear_interp_instance_f32(_Instance):
+    """cmsisdsp_interpolation.c: (nValues, x1, xSpacing, pYData), each optional and by keyword; the table is copied."""
+    _struct = _abi.arm_linear_interp_instance_f32
+
+    def __init__(self, nValues=0, x1=0.0, xSpacing=0.0, pYData=None):
+        super().__init__()
+        if pYData is not None:
+            self._s, keep = _amd.linear_interp_instance(x1, xSpacing, _arr(pYData, _np.float32).reshape(-1)[:int(nValues)])
+            self._keep = [keep]
+
+
+def _bilinear_instance(kind, dt):
+    class _Bilinear(_Instance):
+        _struct = _abi.arm_bilinear_interp_instance
+
+        def __init__(self, numRows=0, numCols=0, pData=None):
+            super().__init__()
+            if pData is not None:
+                table = _arr(pData, dt).reshape(-1)[:int(numRows) * int(numCols)].reshape(int(numRows), int(numCols))
+                self._s, keep = _amd.bilinear_interp_instance(kind, table)
+                self._keep = [keep]
+    _Bilinear.__name__ = f"arm_bilinear_interp_instance_{kind}"
+    _Bilinear.__doc__ = "cmsisdsp_interpolation.c: (numRows, numCols, pData), each optional and by keyword."
+    return _Bilinear
+
+
+for _k, _dt in (("f32", _np.float32), ("q31", _np.int32), ("q15", _np.int16), ("q7", _np.int8)):
+    globals()[f"arm_bilinear_interp_instance_{_k}"] = _bilinear_instance(_k, _dt)
+
+
+class arm_spline_instance_f32(_Instance):
+    """cmsisdsp_interpolation.c: filled by arm_spline_init_f32."""
+    _struct = _abi.arm_spline_instance_f32
+
+    def __init__(self, type=0, x=None, y=None, n_x=0):
+        super().__init__()
+        self._s.type = int(type)
+
+
+def arm_linear_interp_f32(S, x):
+    """cmsisdsp_interpolation.c cmsis_arm_linear_interp_f32 (S, x) -> a Python float (computed on the host)."""
+    return float(_amd.arm_linear_interp("f32", S._s, x))
+
+
+def arm_bilinear_interp_f32(S, X, Y):
+    """cmsisdsp_interpolation.c cmsis_arm_bilinear_interp_f32 (S, X, Y) -> a Python float (computed on the host)."""
+    return float(_amd.arm_bilinear_interp("f32", S._s, X, Y))
+
+
+def _interp_fixed(kind, dt):
+    def linear(pYData, x, nValues):
+        return int(_amd.arm_linear_interp(kind, _arr(pYData, dt).reshape(-1)[:int(nValues)], x))
+
+    def bilinear(S, X, Y):
+        return int(_amd.arm_bilinear_interp(kind, S._s, X, Y))
+    linear.__name__, bilinear.__name__ = f"arm_linear_interp_{kind}", f"arm_bilinear_interp_{kind}"
+    linear.__doc__ = (f"cmsisdsp_interpolation.c cmsis_arm_linear_interp_{kind} (pYData, x, nValues) -> an int; x is "
+                      "12.20 (computed on the host).")
+    bilinear.__doc__ = (f"cmsisdsp_interpolation.c cmsis_arm_bilinear_interp_{kind} (S, X, Y) -> an int; X and Y are "
+                        "12.20 (computed on the host).")
+    return linear, bilinear
+
+
+for _k, _dt in (("q31", _np.int32), ("q15", _np.int16), ("q7", _np.int8)):
+    globals()[f"arm_linear_interp_{_k}"], globals()[f"arm_bilinear_interp_{_k}"] = _interp_fixed(_k, _dt)
+
+
+def arm_spline_init_f32(S, type, pX, pY):
+    """cmsisdsp_interpolation.c cmsis_arm_spline_init_f32 (S, type, x, y) -> 0; n = len(x); the binding allocates the
+    coefficients and the scratch buffer."""
+    x, y = _arr(pX, _np.float32).reshape(-1), _arr(pY, _np.float32).reshape(-1)
+    n = x.size
+    coeffs, temp = _np.zeros(max(1, 3 * (n - 1)), _np.float32), _np.zeros(max(1, 2 * n - 1), _np.float32)
+    S._s.type = int(type)
+    _lib.arm_spline_init_f32(_C.byref(S._s), int(type), x.ctypes.data, y.ctypes.data, n, coeffs.ctypes.data,
+                             temp.ctypes.data)
+    _check("arm_spline_init_f32")
+    S._keep = [x, y, coeffs]
+    return 0
+
+
+def arm_spline_f32(S, pSrc):
+    """cmsisdsp_interpolation.c cmsis_arm_spline_f32 (S, xq) -> the values; blockSize = len(xq)."""
+    xq = _arr(pSrc, _np.float32).reshape(-1)
+    out = _np.zeros(xq.size, _np.float32)
+    _lib.arm_spline_f32(_C.byref(S._s), xq.ctypes.data, out.ctypes.data, xq.size)
+    _check("arm_spline_f32")
+    return out
+
+
+# ------------------------------------------------------------------ quaternions (cmsisdsp_quaternion.c)
+def _quaternion(name):
+    def run(pSrc):
+        return _amd.arm_quaternion_f32(name, _arr(pSrc, _np.float32))
+    wa, wd = _abi.QUATERNION_FUNCS[name]
+    run.__name__ = f"arm_{name}_f32"
+    run.__doc__ = (f"cmsisdsp_quaternion.c cmsis_arm_{name}_f32 (pSrc) -> {wd} words per item; nbQuaternions = "
+                   f"len(pSrc) // {wa}.")
+    return run
+
+
+for _f in _abi.QUATERNION_FUNCS:
+    globals()[f"arm_{_f}_f32"] = _quaternion(_f)
+
+
+def arm_quaternion_product_f32(pSrcA, pSrcB):
+    """cmsisdsp_quaternion.c cmsis_arm_quaternion_product_f32 (pSrcA, pSrcB) -> 4 words per item; nbQuaternions =
+    len(pSrcA) // 4."""
+    return _amd.arm_quaternion_product_f32(_arr(pSrcA, _np.float32), _arr(pSrcB, _np.float32))
+
+
+def arm_quaternion_product_single_f32(pSrcA, pSrcB):
+    """cmsisdsp_quaternion.c cmsis_arm_quaternion_product_single_f32 (pSrcA, pSrcB) -> the 4 words of one product."""
+    return _amd.arm_quaternion_product_f32(_arr(pSrcA, _np.float32), _arr(pSrcB, _np.float32), single=True)
+
+
 # ------------------------------------------------------------------ convolution
 def _conv(kind, dt):
     def run(pSrcA, srcALen, pSrcB, srcBLen):

@@ -60,6 +60,8 @@ def _load():
     _abi.bind(lib, _abi.SUPPORT)
     _abi.bind(lib, _abi.DISTANCE)
     _abi.bind(lib, _abi.ML)
+    _abi.bind(lib, _abi.QUATERNION)
+    _abi.bind(lib, _abi.INTERP)
     _abi.bind(lib, _abi.BATCHED)
     return lib
 
@@ -1719,6 +1721,151 @@ def bayes_predict_batch(S, x, probabilities, classes, stream=None):
     dim]) under the device model S (arm_gaussian_naive_bayes_predict_f32_batch)."""
     _solve_call("arm_gaussian_naive_bayes_predict_f32_batch", C.byref(S), _cm_ptr(x), _cm_ptr(probabilities),
                 _cm_ptr(classes), x.shape[0], _stream_ptr(stream))
+
+
+# ---- interpolation --------------------------------------------------------------------------------------------------
+arm_linear_interp_instance_f32 = _abi.arm_linear_interp_instance_f32
+arm_bilinear_interp_instance = _abi.arm_bilinear_interp_instance
+arm_spline_instance_f32 = _abi.arm_spline_instance_f32
+INTERP_KINDS = ("f32", "q31", "q15", "q7")
+_INTERP_NP = {"f32": np.float32, "q31": np.int32, "q15": np.int16, "q7": np.int8}
+
+
+def _table(t, kind):
+    """(pointer, keep) of a table: a device tensor as it is, anything else as a contiguous numpy array."""
+    if hasattr(t, "data_ptr"):
+        return t.data_ptr(), t
+    a = np.ascontiguousarray(t, dtype=_INTERP_NP[kind])
+    return a.ctypes.data, a
+
+
+def linear_interp_instance(x1, x_spacing, table):
+    """(instance, keep): an arm_linear_interp_instance_f32 over a float32 table: a numpy array (the scalar drop-in) or a
+    device tensor (linear_interp_batch)."""
+    ptr, keep = _table(table, "f32")
+    return arm_linear_interp_instance_f32(int(np.prod(keep.shape)), float(x1), float(x_spacing), ptr), keep
+
+
+def bilinear_interp_instance(kind, table):
+    """(instance, keep): an arm_bilinear_interp_instance_<kind> over a [numRows, numCols] table: a numpy array (the
+    scalar drop-in) or a device tensor (bilinear_interp_batch)."""
+    ptr, keep = _table(table, kind)
+    return arm_bilinear_interp_instance(int(keep.shape[0]), int(keep.shape[1]), ptr), keep
+
+
+def arm_linear_interp(kind, table_or_instance, x):
+    """arm_linear_interp_<kind> of one sample (computed on the host): an instance for f32, a numpy table otherwise."""
+    if kind == "f32":
+        r = lib.arm_linear_interp_f32(C.byref(table_or_instance), float(x))
+    else:
+        t = np.ascontiguousarray(table_or_instance, dtype=_INTERP_NP[kind])
+        r = getattr(lib, f"arm_linear_interp_{kind}")(t.ctypes.data, int(x), t.size)
+    _check_void(f"arm_linear_interp_{kind}")
+    return r
+
+
+def arm_bilinear_interp(kind, S, X, Y):
+    """arm_bilinear_interp_<kind> of one point (computed on the host)."""
+    r = getattr(lib, f"arm_bilinear_interp_{kind}")(C.byref(S), *((float(X), float(Y)) if kind == "f32" else (int(X), int(Y))))
+    _check_void(f"arm_bilinear_interp_{kind}")
+    return r
+
+
+def arm_spline_f32(spline_type, x, y, xq):
+    """arm_spline_init_f32 and arm_spline_f32 on float32 numpy arrays (drop-ins) -> (the values at xq, coeffs
+    [3 (n - 1)], tempBuffer [2 n - 1])."""
+    x, y, xq = (np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in (x, y, xq))
+    n = x.size
+    coeffs, temp = np.zeros(max(1, 3 * (n - 1)), np.float32), np.zeros(max(1, 2 * n - 1), np.float32)
+    S = arm_spline_instance_f32()
+    lib.arm_spline_init_f32(C.byref(S), int(spline_type), x.ctypes.data, y.ctypes.data, n, coeffs.ctypes.data,
+                            temp.ctypes.data)
+    _check_void("arm_spline_init_f32")
+    out = np.zeros(xq.size, np.float32)
+    lib.arm_spline_f32(C.byref(S), xq.ctypes.data, out.ctypes.data, xq.size)
+    _check_void("arm_spline_f32")
+    return out, coeffs[:3 * (n - 1)], temp[:2 * n - 1]
+
+
+def linear_interp_batch(kind, table_or_instance, x, y, stream=None):
+    """y[i] = arm_linear_interp_<kind>(x[i]) for device tensors x (float32, or int32 in 12.20) and y of one shape; an
+    instance over a device table for f32, a device table otherwise (arm_linear_interp_<kind>_batch)."""
+    if kind == "f32":
+        _solve_call("arm_linear_interp_f32_batch", C.byref(table_or_instance), _cm_ptr(x), _cm_ptr(y), x.numel(),
+                    _stream_ptr(stream))
+    else:
+        _solve_call(f"arm_linear_interp_{kind}_batch", _cm_ptr(table_or_instance), table_or_instance.numel(),
+                    _cm_ptr(x), _cm_ptr(y), x.numel(), _stream_ptr(stream))
+
+
+def bilinear_interp_batch(kind, S, X, Y, out, stream=None):
+    """out[i] = arm_bilinear_interp_<kind>(S, X[i], Y[i]) for device tensors of one shape; S over a device table
+    (arm_bilinear_interp_<kind>_batch)."""
+    _solve_call(f"arm_bilinear_interp_{kind}_batch", C.byref(S), _cm_ptr(X), _cm_ptr(Y), _cm_ptr(out), X.numel(),
+                _stream_ptr(stream))
+
+
+def spline_init_batch(spline_type, x, y, coeffs, temp, stream=None):
+    """The coefficients of `batch` splines: float32 device tensors x [n] (one knot vector for every item) or
+    [batch, n], y [batch, n], coeffs [batch, 3 (n - 1)], temp [batch, 2 n - 1] (arm_spline_init_f32_batch)."""
+    n = y.shape[-1]
+    _solve_call("arm_spline_init_f32_batch", int(spline_type), _cm_ptr(x), 0 if x.dim() == 1 else x.stride(0),
+                _cm_ptr(y), n, _cm_ptr(coeffs), _cm_ptr(temp), y.shape[0], _stream_ptr(stream))
+
+
+def spline_batch(x, y, coeffs, xq, dst, stream=None):
+    """dst[i] = the spline of item i at its queries: x [n] or [batch, n], y [batch, n], coeffs [batch, 3 (n - 1)], xq
+    [blockSize] (one query vector for every item) or [batch, blockSize], dst [batch, blockSize]
+    (arm_spline_f32_batch)."""
+    _solve_call("arm_spline_f32_batch", _cm_ptr(x), 0 if x.dim() == 1 else x.stride(0), _cm_ptr(y), _cm_ptr(coeffs),
+                y.shape[-1], _cm_ptr(xq), 0 if xq.dim() == 1 else xq.stride(0), _cm_ptr(dst), dst.shape[-1],
+                y.shape[0], _stream_ptr(stream))
+
+
+# ---- quaternions ----------------------------------------------------------------------------------------------------
+QUATERNION_FUNCS = tuple(_abi.QUATERNION_FUNCS)
+
+
+def arm_quaternion_f32(name, src):
+    """arm_<name>_f32 (name in QUATERNION_FUNCS) of a flat float32 array of quaternions (4 words each; rotations of 9
+    words for "rotation2quaternion") (drop-in, numpy) -> a new flat array."""
+    wa, wd = _abi.QUATERNION_FUNCS[name]
+    x = np.ascontiguousarray(src, dtype=np.float32).reshape(-1)
+    n = x.size // wa
+    out = np.zeros(n * wd, dtype=np.float32)
+    getattr(lib, f"arm_{name}_f32")(x.ctypes.data, out.ctypes.data, n)
+    _check_void(f"arm_{name}_f32")
+    return out
+
+
+def arm_quaternion_product_f32(a, b, single=False):
+    """arm_quaternion_product_f32 of two flat float32 arrays of quaternions (single=True:
+    arm_quaternion_product_single_f32 of two quaternions) (drop-in, numpy) -> a new flat array."""
+    x = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+    y = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+    n = 1 if single else x.size // 4
+    if x.size < 4 * n or y.size < 4 * n:
+        raise ValueError(f"arm_quaternion_product_f32: {x.size} and {y.size} words for {n} quaternions")
+    out = np.zeros(4 * n, dtype=np.float32)
+    if single:
+        lib.arm_quaternion_product_single_f32(x.ctypes.data, y.ctypes.data, out.ctypes.data)
+    else:
+        lib.arm_quaternion_product_f32(x.ctypes.data, y.ctypes.data, out.ctypes.data, n)
+    _check_void("arm_quaternion_product_f32")
+    return out
+
+
+def quaternion_batch(name, src, dst, stream=None):
+    """dst[i] = arm_<name>_f32 (name in QUATERNION_FUNCS) of src[i] for contiguous float32 device tensors src [n, 4]
+    (or [n, 9] rotations) and dst [n], [n, 4] or [n, 9] (arm_<name>_f32_batch)."""
+    _solve_call(f"arm_{name}_f32_batch", _cm_ptr(src), _cm_ptr(dst), src.shape[0], _stream_ptr(stream))
+
+
+def quaternion_product_batch(a, b, dst, stream=None):
+    """dst[i] = a[i] * b[i] for contiguous float32 device tensors a, dst [n, 4] and b [n, 4], or b [4]: one quaternion
+    for every item (arm_quaternion_product_f32_batch)."""
+    _solve_call("arm_quaternion_product_f32_batch", _cm_ptr(a), _cm_ptr(b), 0 if b.dim() == 1 else 4, _cm_ptr(dst),
+                a.shape[0], _stream_ptr(stream))
 
 
 def mat_mult_batch(a, b, c, stream=None, fast=False):

@@ -550,6 +550,56 @@ for _k, (_inst, _extra) in SVM_KINDS.items():
     ML[f"arm_svm_{_k}_predict_f32"] = (None, [P(_inst), _vp, _vp])
     ML[f"arm_svm_{_k}_predict_f32_batch"] = (C.c_int, [P(_inst), _vp, _vp, _vp, _u32, _vp])
 
+# The quaternion functions: 8 drop-ins and 7 _batch forms (product_single has none).  QUATERNION_FUNCS: name -> (words
+# per source item, words per result item).  The product only (tests/golden/quaternion.npz holds the reference's outputs).
+QUATERNION_FUNCS = {"quaternion_norm": (4, 1), "quaternion_inverse": (4, 4), "quaternion_conjugate": (4, 4),
+                    "quaternion_normalize": (4, 4), "quaternion2rotation": (4, 9), "rotation2quaternion": (9, 4)}
+QUATERNION = {
+    **{f"arm_{f}_f32": (None, [_vp, _vp, _u32]) for f in QUATERNION_FUNCS},
+    **{f"arm_{f}_f32_batch": (C.c_int, [_vp, _vp, _u32, _vp]) for f in QUATERNION_FUNCS},
+    "arm_quaternion_product_f32": (None, [_vp, _vp, _vp, _u32]),
+    "arm_quaternion_product_single_f32": (None, [_vp, _vp, _vp]),
+    "arm_quaternion_product_f32_batch": (C.c_int, [_vp, _vp, _u32, _vp, _u32, _vp]),
+}
+
+# Interpolation: the 8 scalar drop-ins (computed on the host), the 2 spline drop-ins and the 10 _batch forms.
+class arm_linear_interp_instance_f32(C.Structure):
+    # Include/dsp/interpolation_functions.h:53-59
+    _fields_ = [("nValues", C.c_uint32), ("x1", C.c_float), ("xSpacing", C.c_float), ("pYData", C.c_void_p)]
+
+
+class arm_bilinear_interp_instance(C.Structure):
+    # Include/dsp/interpolation_functions.h:64-99 (one layout for f32, q31, q15, q7)
+    _fields_ = [("numRows", C.c_uint16), ("numCols", C.c_uint16), ("pData", C.c_void_p)]
+
+
+arm_bilinear_interp_instance_f32 = arm_bilinear_interp_instance_q31 = arm_bilinear_interp_instance
+arm_bilinear_interp_instance_q15 = arm_bilinear_interp_instance_q7 = arm_bilinear_interp_instance
+
+
+class arm_spline_instance_f32(C.Structure):
+    # Include/dsp/interpolation_functions.h:114-121
+    _fields_ = [("type", C.c_int), ("x", C.c_void_p), ("y", C.c_void_p), ("n_x", C.c_uint32), ("coeffs", C.c_void_p)]
+
+
+INTERP_FIXED = {"q31": C.c_int32, "q15": C.c_int16, "q7": C.c_int8}
+INTERP = {
+    "arm_linear_interp_f32": (C.c_float, [P(arm_linear_interp_instance_f32), C.c_float]),
+    "arm_linear_interp_f32_batch": (C.c_int, [P(arm_linear_interp_instance_f32), _vp, _vp, _u32, _vp]),
+    "arm_bilinear_interp_f32": (C.c_float, [P(arm_bilinear_interp_instance), C.c_float, C.c_float]),
+    "arm_bilinear_interp_f32_batch": (C.c_int, [P(arm_bilinear_interp_instance), _vp, _vp, _vp, _u32, _vp]),
+    **{f"arm_linear_interp_{t}": (ct, [_vp, C.c_int32, _u32]) for t, ct in INTERP_FIXED.items()},
+    **{f"arm_linear_interp_{t}_batch": (C.c_int, [_vp, _u32, _vp, _vp, _u32, _vp]) for t in INTERP_FIXED},
+    **{f"arm_bilinear_interp_{t}": (ct, [P(arm_bilinear_interp_instance), C.c_int32, C.c_int32])
+       for t, ct in INTERP_FIXED.items()},
+    **{f"arm_bilinear_interp_{t}_batch": (C.c_int, [P(arm_bilinear_interp_instance), _vp, _vp, _vp, _u32, _vp])
+       for t in INTERP_FIXED},
+    "arm_spline_init_f32": (None, [P(arm_spline_instance_f32), C.c_int, _vp, _vp, _u32, _vp, _vp]),
+    "arm_spline_f32": (None, [P(arm_spline_instance_f32), _vp, _vp, _u32]),
+    "arm_spline_init_f32_batch": (C.c_int, [C.c_int, _vp, _u32, _vp, _u32, _vp, _vp, _u32, _vp]),
+    "arm_spline_f32_batch": (C.c_int, [_vp, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp]),
+}
+
 # per-length MFCC init functions (the product and the reference build; the oracle has the
 # generic init only)
 MFCC_LEN = {f"arm_mfcc_init_{n}_f32": (C.c_int, [P(arm_mfcc_instance_f32), C.c_uint32, C.c_uint32, C.c_void_p,

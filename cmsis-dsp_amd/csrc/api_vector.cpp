@@ -1,7 +1,8 @@
 // C ABI of the stateless vector and matrix families: the f32 solves, the basic matrix functions, complex math
-// with max / min, statistics, basic math and the support functions, each as the drop-in of arm_math.h and the
-// batched device form of arm_math_mi355x.h.  Every family describes a call as a table of operands and hands it to
-// one driver (VecCall); api.cpp holds the transforms, filters, convolution, MFCC and the matrix multiplies.
+// with max / min, statistics, basic math, the support functions, interpolation and the quaternions, each as the
+// drop-in of arm_math.h and the batched device form of arm_math_mi355x.h.  Every family describes a call as a table
+// of operands and hands it to one driver (VecCall); api.cpp holds the transforms, filters, convolution, MFCC and the
+// matrix multiplies.
 #include <type_traits>
 
 #include "../../include/arm_math.h"
@@ -1339,5 +1340,231 @@ arm_status arm_gaussian_naive_bayes_predict_f32_batch(const arm_gaussian_naive_b
                                                       uint32_t* d_class, uint32_t nbItems, void* stream) {
   return ml_bayes(S, d_in, d_probabilities, d_class, false, nbItems, stream,
                   "arm_gaussian_naive_bayes_predict_f32_batch");
+}
+}  // extern "C"
+
+// ---- quaternions (quaternion.hip) --------------------------------------------------------------------------
+// quaternion_math_functions.h.  One helper: a source of wa words per item, an optional second factor at bStride
+// words (0 or 4), a result of wd words per item.  A result of quaternions may be a source of quaternions exactly;
+// any other overlap is refused.  nbQuaternions == 0 is a successful no-op.
+namespace {
+arm_status qt_call(int op, const float* a, const float* b, uint32_t bStride, float* d, uint32_t n, bool sync,
+                   void* stream, const char* what) {
+  const size_t wa = op == kQtFromRotation ? 9 : 4, wd = op == kQtNorm ? 1 : op == kQtToRotation ? 9 : 4;
+  const bool two = op == kQtProduct;
+  const unsigned in = wa == wd ? kIn | kExactOk : kIn;
+  const size_t bwords = n ? (size_t)bStride * (n - 1) + 4 : 0;
+  const VecCall c{what, sync, stream, 0, two ? 3 : 2,
+                  {{a, sizeof(float) * wa * n, in}, {d, sizeof(float) * wd * n, kOut}, {b, sizeof(float) * bwords, in}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (two && bStride != 0 && bStride != 4) return refuse(sync, what);
+  if (n == 0) return ARM_MATH_SUCCESS;
+  return c.run([&](void* const* p, hipStream_t st) {
+    return quaternion_launch(op, (const float*)p[0], (const float*)p[2], bStride, (float*)p[1], n, st);
+  });
+}
+}  // namespace
+
+extern "C" {
+#define MI355X_QT_1(NAME, OP)                                                                                    \
+  void arm_##NAME##_f32(const float32_t* pSrc, float32_t* pDst, uint32_t nbQuaternions) {                        \
+    qt_call(OP, pSrc, nullptr, 0, pDst, nbQuaternions, true, nullptr, "arm_" #NAME "_f32");                      \
+  }                                                                                                              \
+  arm_status arm_##NAME##_f32_batch(const float32_t* d_src, float32_t* d_dst, uint32_t nbQuaternions,            \
+                                    void* stream) {                                                              \
+    return qt_call(OP, d_src, nullptr, 0, d_dst, nbQuaternions, false, stream, "arm_" #NAME "_f32_batch");       \
+  }
+MI355X_QT_1(quaternion_norm, kQtNorm)
+MI355X_QT_1(quaternion_inverse, kQtInverse)
+MI355X_QT_1(quaternion_conjugate, kQtConjugate)
+MI355X_QT_1(quaternion_normalize, kQtNormalize)
+MI355X_QT_1(quaternion2rotation, kQtToRotation)
+MI355X_QT_1(rotation2quaternion, kQtFromRotation)
+#undef MI355X_QT_1
+
+void arm_quaternion_product_f32(const float32_t* qa, const float32_t* qb, float32_t* qr, uint32_t nbQuaternions) {
+  qt_call(kQtProduct, qa, qb, 4, qr, nbQuaternions, true, nullptr, "arm_quaternion_product_f32");
+}
+void arm_quaternion_product_single_f32(const float32_t* qa, const float32_t* qb, float32_t* qr) {
+  qt_call(kQtProduct, qa, qb, 4, qr, 1, true, nullptr, "arm_quaternion_product_single_f32");
+}
+arm_status arm_quaternion_product_f32_batch(const float32_t* d_qa, const float32_t* d_qb, uint32_t bStride,
+                                            float32_t* d_qr, uint32_t nbQuaternions, void* stream) {
+  return qt_call(kQtProduct, d_qa, d_qb, bStride, d_qr, nbQuaternions, false, stream,
+                 "arm_quaternion_product_f32_batch");
+}
+}  // extern "C"
+
+// ---- interpolation (interp.hip) ----------------------------------------------------------------------------
+// interpolation_functions.h.  The linear and bilinear drop-ins take one sample and are computed on the host from a
+// host-readable table; their _batch forms, and both forms of the spline, run on the GPU.
+namespace {
+// a failed scalar drop-in returns 0 (a NaN from the f32 forms) and records the refusal
+template <typename T>
+T interp_refused(const char* what) {
+  set_error(hipErrorInvalidValue, what);
+  if (std::is_same<T, float>::value) return (T)__builtin_nanf("");
+  return (T)0;
+}
+
+// launch(table, x, y, st)
+template <typename T, typename X, typename Launch>
+arm_status linear_batch(const T* table, uint32_t nValues, const X* x, T* y, uint32_t count, void* stream,
+                        const char* what, Launch&& launch) {
+  const VecCall c{what, false, stream, 0, 3,
+                  {{table, sizeof(T) * (size_t)nValues, kIn}, {x, sizeof(X) * (size_t)count, kIn},
+                   {y, sizeof(T) * (size_t)count, kOut}}};
+  if (nValues == 0) return ARM_MATH_ARGUMENT_ERROR;
+  if (count == 0) return ARM_MATH_SUCCESS;
+  return c.run([&](void* const* p, hipStream_t st) { return launch((const T*)p[0], (const X*)p[1], (T*)p[2], st); });
+}
+
+// launch(table, X, Y, out, st)
+template <typename T, typename X, typename Launch>
+arm_status bilinear_batch(const T* table, uint32_t rows, uint32_t cols, const X* px, const X* py, T* out,
+                          uint32_t count, void* stream, const char* what, Launch&& launch) {
+  const VecCall c{what, false, stream, 0, 4,
+                  {{table, sizeof(T) * (size_t)rows * cols, kIn}, {px, sizeof(X) * (size_t)count, kIn},
+                   {py, sizeof(X) * (size_t)count, kIn}, {out, sizeof(T) * (size_t)count, kOut}}};
+  if ((uint64_t)rows * cols >= 0x80000000ull) return ARM_MATH_ARGUMENT_ERROR;
+  if (count == 0) return ARM_MATH_SUCCESS;
+  return c.run([&](void* const* p, hipStream_t st) {
+    return launch((const T*)p[0], (const X*)p[1], (const X*)p[2], (T*)p[3], st);
+  });
+}
+
+arm_status spline_init(int type, const float* x, uint32_t xStride, const float* y, uint32_t n, float* coeffs,
+                       float* temp, bool sync, uint32_t batch, void* stream, const char* what) {
+  const size_t items = batch, xw = batch ? (size_t)xStride * (items - 1) + n : 0;
+  const size_t cw = n ? 3 * ((size_t)n - 1) : 0, tw = n ? 2 * (size_t)n - 1 : 0;
+  const VecCall c{what, sync, stream, 0, 4,
+                  {{x, sizeof(float) * xw, kIn}, {y, sizeof(float) * n * items, kIn},
+                   {coeffs, sizeof(float) * cw * items, kOut}, {temp, sizeof(float) * tw * items, kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (n < 2 || (type != ARM_SPLINE_NATURAL && type != ARM_SPLINE_PARABOLIC_RUNOUT)) return refuse(sync, what);
+  if (xStride != 0 && xStride < n) return refuse(sync, what);
+  if (batch == 0) return ARM_MATH_SUCCESS;
+  return c.run([&](void* const* p, hipStream_t st) {
+    return spline_init_launch(type, (const float*)p[0], xStride, (const float*)p[1], n, (float*)p[2], (float*)p[3],
+                              batch, st);
+  });
+}
+
+arm_status spline_eval(const float* x, uint32_t xStride, const float* y, const float* coeffs, uint32_t n,
+                       const float* xq, uint32_t xqStride, float* dst, uint32_t blockSize, bool sync, uint32_t batch,
+                       void* stream, const char* what) {
+  const size_t items = batch, xw = batch ? (size_t)xStride * (items - 1) + n : 0;
+  const size_t qw = batch ? (size_t)xqStride * (items - 1) + blockSize : 0, cw = n ? 3 * ((size_t)n - 1) : 0;
+  const VecCall c{what, sync, stream, 0, 5,
+                  {{x, sizeof(float) * xw, kIn}, {y, sizeof(float) * n * items, kIn},
+                   {coeffs, sizeof(float) * cw * items, kIn}, {xq, sizeof(float) * qw, kIn},
+                   {dst, sizeof(float) * blockSize * items, kOut}}};
+  if (c.null_in_sync()) return ARM_MATH_ARGUMENT_ERROR;
+  if (n < 2) return refuse(sync, what);
+  if ((xStride != 0 && xStride < n) || (xqStride != 0 && xqStride < blockSize)) return refuse(sync, what);
+  if (batch == 0 || blockSize == 0) return ARM_MATH_SUCCESS;
+  return c.run([&](void* const* p, hipStream_t st) {
+    return spline_launch((const float*)p[0], xStride, (const float*)p[1], (const float*)p[2], n, (const float*)p[3],
+                         xqStride, (float*)p[4], blockSize, batch, st);
+  });
+}
+}  // namespace
+
+extern "C" {
+float32_t arm_linear_interp_f32(const arm_linear_interp_instance_f32* S, float32_t x) {
+  if (!S || !S->pYData || S->nValues == 0) return interp_refused<float>("arm_linear_interp_f32");
+  return linear_interp_f32_host(S->pYData, S->nValues, S->x1, S->xSpacing, x);
+}
+q31_t arm_linear_interp_q31(const q31_t* pYData, q31_t x, uint32_t nValues) {
+  if (!pYData || nValues == 0) return interp_refused<q31_t>("arm_linear_interp_q31");
+  return linear_interp_q31_host(pYData, nValues, x);
+}
+q15_t arm_linear_interp_q15(const q15_t* pYData, q31_t x, uint32_t nValues) {
+  if (!pYData || nValues == 0) return interp_refused<q15_t>("arm_linear_interp_q15");
+  return linear_interp_q15_host(pYData, nValues, x);
+}
+q7_t arm_linear_interp_q7(const q7_t* pYData, q31_t x, uint32_t nValues) {
+  if (!pYData || nValues == 0) return interp_refused<q7_t>("arm_linear_interp_q7");
+  return linear_interp_q7_host(pYData, nValues, x);
+}
+arm_status arm_linear_interp_f32_batch(const arm_linear_interp_instance_f32* S, const float32_t* d_x, float32_t* d_y,
+                                       uint32_t blockSize, void* stream) {
+  if (!S) return ARM_MATH_ARGUMENT_ERROR;
+  const uint32_t nValues = S->nValues;
+  const float x1 = S->x1, xSpacing = S->xSpacing;
+  return linear_batch(S->pYData, nValues, d_x, d_y, blockSize, stream, "arm_linear_interp_f32_batch",
+                      [&](const float* t, const float* x, float* y, hipStream_t st) {
+                        return linear_interp_f32_launch(t, nValues, x1, xSpacing, x, y, blockSize, st);
+                      });
+}
+#define MI355X_INTERP_Q(T, CT)                                                                                   \
+  arm_status arm_linear_interp_##T##_batch(const CT* d_table, uint32_t nValues, const q31_t* d_x, CT* d_y,       \
+                                           uint32_t blockSize, void* stream) {                                   \
+    return linear_batch(d_table, nValues, d_x, d_y, blockSize, stream, "arm_linear_interp_" #T "_batch",         \
+                        [&](const CT* t, const q31_t* x, CT* y, hipStream_t st) {                                \
+                          return linear_interp_q_launch<CT>(t, nValues, x, y, blockSize, st);                    \
+                        });                                                                                      \
+  }                                                                                                              \
+  CT arm_bilinear_interp_##T(arm_bilinear_interp_instance_##T* S, q31_t X, q31_t Y) {                            \
+    if (!S || !S->pData || (uint64_t)S->numRows * S->numCols >= 0x80000000ull)                                   \
+      return interp_refused<CT>("arm_bilinear_interp_" #T);                                                      \
+    return bilinear_interp_##T##_host(S->pData, S->numRows, S->numCols, X, Y);                                   \
+  }                                                                                                              \
+  arm_status arm_bilinear_interp_##T##_batch(const arm_bilinear_interp_instance_##T* S, const q31_t* d_X,        \
+                                             const q31_t* d_Y, CT* d_out, uint32_t blockSize, void* stream) {    \
+    if (!S) return ARM_MATH_ARGUMENT_ERROR;                                                                      \
+    const uint32_t rows = S->numRows, cols = S->numCols;                                                         \
+    return bilinear_batch(S->pData, rows, cols, d_X, d_Y, d_out, blockSize, stream,                              \
+                          "arm_bilinear_interp_" #T "_batch",                                                    \
+                          [&](const CT* t, const q31_t* x, const q31_t* y, CT* o, hipStream_t st) {              \
+                            return bilinear_interp_q_launch<CT>(t, rows, cols, x, y, o, blockSize, st);          \
+                          });                                                                                    \
+  }
+MI355X_INTERP_Q(q31, q31_t)
+MI355X_INTERP_Q(q15, q15_t)
+MI355X_INTERP_Q(q7, q7_t)
+#undef MI355X_INTERP_Q
+
+float32_t arm_bilinear_interp_f32(const arm_bilinear_interp_instance_f32* S, float32_t X, float32_t Y) {
+  if (!S || !S->pData || (uint64_t)S->numRows * S->numCols >= 0x80000000ull)
+    return interp_refused<float>("arm_bilinear_interp_f32");
+  return bilinear_interp_f32_host(S->pData, S->numRows, S->numCols, X, Y);
+}
+arm_status arm_bilinear_interp_f32_batch(const arm_bilinear_interp_instance_f32* S, const float32_t* d_X,
+                                         const float32_t* d_Y, float32_t* d_out, uint32_t blockSize, void* stream) {
+  if (!S) return ARM_MATH_ARGUMENT_ERROR;
+  const uint32_t rows = S->numRows, cols = S->numCols;
+  return bilinear_batch(S->pData, rows, cols, d_X, d_Y, d_out, blockSize, stream, "arm_bilinear_interp_f32_batch",
+                        [&](const float* t, const float* x, const float* y, float* o, hipStream_t st) {
+                          return bilinear_interp_f32_launch(t, rows, cols, x, y, o, blockSize, st);
+                        });
+}
+
+void arm_spline_init_f32(arm_spline_instance_f32* S, arm_spline_type type, const float32_t* x, const float32_t* y,
+                         uint32_t n, float32_t* coeffs, float32_t* tempBuffer) {
+  if (!S) { refuse(true, "arm_spline_init_f32"); return; }
+  if (spline_init((int)type, x, 0, y, n, coeffs, tempBuffer, true, 1, nullptr, "arm_spline_init_f32") !=
+      ARM_MATH_SUCCESS)
+    return;
+  S->x = x;
+  S->y = y;
+  S->n_x = n;
+  S->coeffs = coeffs;
+}
+void arm_spline_f32(arm_spline_instance_f32* S, const float32_t* xq, float32_t* pDst, uint32_t blockSize) {
+  if (!S) { refuse(true, "arm_spline_f32"); return; }
+  spline_eval(S->x, 0, S->y, S->coeffs, S->n_x, xq, 0, pDst, blockSize, true, 1, nullptr, "arm_spline_f32");
+}
+arm_status arm_spline_init_f32_batch(arm_spline_type type, const float32_t* d_x, uint32_t xStride,
+                                     const float32_t* d_y, uint32_t n, float32_t* d_coeffs, float32_t* d_temp,
+                                     uint32_t batch, void* stream) {
+  return spline_init((int)type, d_x, xStride, d_y, n, d_coeffs, d_temp, false, batch, stream,
+                     "arm_spline_init_f32_batch");
+}
+arm_status arm_spline_f32_batch(const float32_t* d_x, uint32_t xStride, const float32_t* d_y,
+                                const float32_t* d_coeffs, uint32_t n, const float32_t* d_xq, uint32_t xqStride,
+                                float32_t* d_dst, uint32_t blockSize, uint32_t batch, void* stream) {
+  return spline_eval(d_x, xStride, d_y, d_coeffs, n, d_xq, xqStride, d_dst, blockSize, false, batch, stream,
+                     "arm_spline_f32_batch");
 }
 }  // extern "C"

@@ -462,4 +462,46 @@ hipError_t bayes_predict_launch(const BayesModel& m, const float* in, float* pro
                                 hipStream_t st);
 bool bayes_model_staged(uint32_t classes, uint32_t dim);
 
+// Linear, bilinear and cubic-spline interpolation, bit-exact with the reference's scalar code (interp.hip).
+// y[i] = arm_linear_interp_<t>(x[i]) over `count` samples against one table of nValues > 0 words; T is int32_t,
+// int16_t or int8_t and x is in 12.20.  linear_interp_staged: whether the kernel holds the table in LDS.
+hipError_t linear_interp_f32_launch(const float* table, uint32_t nValues, float x1, float xSpacing, const float* x,
+                                    float* y, uint32_t count, hipStream_t st);
+template <typename T>
+hipError_t linear_interp_q_launch(const T* table, uint32_t nValues, const int32_t* x, T* y, uint32_t count,
+                                  hipStream_t st);
+bool linear_interp_staged(uint32_t nValues, uint32_t wordBytes);
+// out[i] = arm_bilinear_interp_<t>(px[i], py[i]) against one rows x cols table, rows * cols < 2^31.
+hipError_t bilinear_interp_f32_launch(const float* table, uint32_t rows, uint32_t cols, const float* px,
+                                      const float* py, float* out, uint32_t count, hipStream_t st);
+template <typename T>
+hipError_t bilinear_interp_q_launch(const T* table, uint32_t rows, uint32_t cols, const int32_t* px, const int32_t* py,
+                                    T* out, uint32_t count, hipStream_t st);
+// arm_spline_init_f32 of `batch` items: knots x + i * xStride (0: one vector for every item), values y + i * n,
+// coeffs + i * 3 (n - 1) (b, c, d) and temp + i * (2 n - 1) (u, z); n >= 2, type 0 or 1.
+hipError_t spline_init_launch(int type, const float* x, size_t xStride, const float* y, uint32_t n, float* coeffs,
+                              float* temp, uint32_t batch, hipStream_t st);
+// arm_spline_f32 of `batch` items: blockSize queries at xq + i * xqStride (0: one vector for every item) into
+// dst + i * blockSize.
+hipError_t spline_launch(const float* x, size_t xStride, const float* y, const float* coeffs, uint32_t n,
+                         const float* xq, size_t xqStride, float* dst, uint32_t blockSize, uint32_t batch,
+                         hipStream_t st);
+// one sample on the host: the scalar drop-ins
+float linear_interp_f32_host(const float* table, uint32_t nValues, float x1, float xSpacing, float x);
+int32_t linear_interp_q31_host(const int32_t* table, uint32_t nValues, int32_t x);
+int16_t linear_interp_q15_host(const int16_t* table, uint32_t nValues, int32_t x);
+int8_t linear_interp_q7_host(const int8_t* table, uint32_t nValues, int32_t x);
+float bilinear_interp_f32_host(const float* table, uint32_t rows, uint32_t cols, float X, float Y);
+int32_t bilinear_interp_q31_host(const int32_t* table, uint32_t rows, uint32_t cols, int32_t X, int32_t Y);
+int16_t bilinear_interp_q15_host(const int16_t* table, uint32_t rows, uint32_t cols, int32_t X, int32_t Y);
+int8_t bilinear_interp_q7_host(const int8_t* table, uint32_t rows, uint32_t cols, int32_t X, int32_t Y);
+
+// The quaternion functions, bit-exact with the reference's scalar branches (quaternion.hip), over n quaternions at
+// 4 words each.  d: n norms (kQtNorm), n quaternions, or n rotations of 9 words (kQtToRotation); a: n rotations for
+// kQtFromRotation.  b (kQtProduct only): the second factor, item i's at b + i * bStride, bStride 4 or 0 (one for
+// every item).  d may be a (or b at bStride 4) exactly where both hold quaternions.
+enum : int { kQtNorm = 0, kQtInverse, kQtConjugate, kQtNormalize, kQtProduct, kQtToRotation, kQtFromRotation };
+hipError_t quaternion_launch(int op, const float* a, const float* b, uint32_t bStride, float* d, uint32_t n,
+                             hipStream_t st);
+
 }  // namespace mi355x

@@ -1420,6 +1420,110 @@ void arm_svm_rbf_predict_f32(const arm_svm_rbf_instance_f32 *S, const float32_t 
 uint32_t arm_gaussian_naive_bayes_predict_f32(const arm_gaussian_naive_bayes_instance_f32 *S, const float32_t *in,
                                               float32_t *pOutputProbabilities, float32_t *pBufferB);
 
+/* Interpolation (interpolation_functions.h): linear, bilinear and cubic spline.  The f16 forms are left out.
+ *
+ * arm_linear_interp_* and arm_bilinear_interp_* take one sample and return one sample.  They are computed on the
+ * HOST, as arm_sqrt_q15 is: the table (S->pYData, pYData, S->pData) must be host-readable memory.  The vector forms
+ * on device pointers are the _batch functions of arm_math_mi355x.h.  Every result equals the reference's scalar code
+ * built without FMA contraction:
+ *   linear f32    i = (int32_t)((x - S->x1) / xSpacing); x < S->x1 gives pYData[0] (tested first), (uint32_t)i >=
+ *                 nValues - 1 gives pYData[nValues - 1], otherwise y0 + (x - x0) * ((y1 - y0) / (x1 - x0)) with x0 =
+ *                 S->x1 + i * xSpacing and x1 = S->x1 + (i + 1) * xSpacing, every operation rounded on its own.
+ *   linear q31, q15, q7   x is 12.20: a signed 12-bit index (q7: x < 0 gives pYData[0], then an unsigned one) and a
+ *                 20-bit fraction; past either end the result is the table's end; inside, the reference's shifts
+ *                 and truncations (0x7FFFFFFF - fract in q31, 0xFFFFF - fract in q15 and q7).
+ *   bilinear f32  xIndex = (int32_t)X, yIndex = (int32_t)Y; 0 outside [0, numCols - 2] x [0, numRows - 2]; otherwise
+ *                 b1 + b2 * xdiff + b3 * ydiff + b4 * xdiff * ydiff, left to right, b4 = f00 - f01 - f10 + f11.
+ *   bilinear q31, q15, q7   X and Y are 12.20; X's index is bounded by numCols - 2 and Y's by numRows - 2, the word
+ *                 is pData[xi + numCols * yi]; 0 outside; the reference's four products and shifts inside.
+ * Defined here where the reference is not: the casts (int32_t)((x - x1) / xSpacing), (int32_t)X and (int32_t)Y
+ * saturate by sign outside the int32_t range and give 0 for a NaN.  Refused (0 is returned, a NaN by the f32 forms,
+ * and arm_mi355x_last_error() is set): a null pointer, nValues == 0, a bilinear table of numRows * numCols >= 2^31
+ * words.
+ *
+ * arm_spline_init_f32 and arm_spline_f32 take host or device pointers, are synchronous and are computed on the GPU.
+ * init solves the tridiagonal system exactly as written: the forward chain li -> u[i] -> z[i] into tempBuffer (2 n - 1
+ * words), the backward chain into coeffs (b, c, d: 3 (n - 1) words), for both boundary types; it sets S->x, S->y,
+ * S->n_x and S->coeffs as the reference does (not S->type).  arm_spline_f32 walks xq as the reference does, with an
+ * interval that never goes back: output k uses interval min(n - 2, max over j <= k of f(xq[j])), f(v) the first i
+ * with v <= x[i + 1] and n - 1 where there is none (a NaN); the value is y + b t + c t t + d t t t, left to right, t =
+ * xq - x[i].  Refused (nothing written, last error set): a null pointer, n < 2 (the reference reads y[-1]), a type
+ * other than the two, a destination that overlaps a source.  blockSize == 0 writes nothing. */
+typedef struct {
+  uint32_t nValues;
+  float32_t x1;
+  float32_t xSpacing;
+  const float32_t *pYData;
+} arm_linear_interp_instance_f32;
+typedef struct {
+  uint16_t numRows;
+  uint16_t numCols;
+  const float32_t *pData;
+} arm_bilinear_interp_instance_f32;
+typedef struct {
+  uint16_t numRows;
+  uint16_t numCols;
+  const q31_t *pData;
+} arm_bilinear_interp_instance_q31;
+typedef struct {
+  uint16_t numRows;
+  uint16_t numCols;
+  const q15_t *pData;
+} arm_bilinear_interp_instance_q15;
+typedef struct {
+  uint16_t numRows;
+  uint16_t numCols;
+  const q7_t *pData;
+} arm_bilinear_interp_instance_q7;
+typedef enum { ARM_SPLINE_NATURAL = 0, ARM_SPLINE_PARABOLIC_RUNOUT = 1 } arm_spline_type;
+typedef struct {
+  arm_spline_type type;
+  const float32_t *x;
+  const float32_t *y;
+  uint32_t n_x;
+  float32_t *coeffs;
+} arm_spline_instance_f32;
+float32_t arm_linear_interp_f32(const arm_linear_interp_instance_f32 *S, float32_t x);
+q31_t arm_linear_interp_q31(const q31_t *pYData, q31_t x, uint32_t nValues);
+q15_t arm_linear_interp_q15(const q15_t *pYData, q31_t x, uint32_t nValues);
+q7_t arm_linear_interp_q7(const q7_t *pYData, q31_t x, uint32_t nValues);
+float32_t arm_bilinear_interp_f32(const arm_bilinear_interp_instance_f32 *S, float32_t X, float32_t Y);
+q31_t arm_bilinear_interp_q31(arm_bilinear_interp_instance_q31 *S, q31_t X, q31_t Y);
+q15_t arm_bilinear_interp_q15(arm_bilinear_interp_instance_q15 *S, q31_t X, q31_t Y);
+q7_t arm_bilinear_interp_q7(arm_bilinear_interp_instance_q7 *S, q31_t X, q31_t Y);
+void arm_spline_init_f32(arm_spline_instance_f32 *S, arm_spline_type type, const float32_t *x, const float32_t *y,
+                         uint32_t n, float32_t *coeffs, float32_t *tempBuffer);
+void arm_spline_f32(arm_spline_instance_f32 *S, const float32_t *xq, float32_t *pDst, uint32_t blockSize);
+
+/* The quaternion functions (quaternion_math_functions.h), f32.  Host or device pointers, synchronous.  A quaternion
+ * is 4 words (w, x, y, z), a rotation 9 words in row order.  Every result word equals the reference's scalar branch
+ * built without FMA contraction: the sums in the order written there, a correctly rounded sqrtf and division.  NaN
+ * results are NaNs, their bits are not pinned.
+ *   norm          sqrtf(w*w + x*x + y*y + z*z), the sum left to right; one word per quaternion.
+ *   inverse       (w, -x, -y, -z) each divided by that sum of squares; the zero quaternion gives NaNs.
+ *   conjugate     (w, -x, -y, -z).   normalize: each word divided by the norm; the zero quaternion gives NaNs.
+ *   product       qr[i] = qa[i] * qb[i] (Hamilton product); product_single is one such product.
+ *   quaternion2rotation   the 3 x 3 matrix of each quaternion, which need not be normalised.
+ *   rotation2quaternion   the reference's four branches with their strict comparisons: trace > 0, else r00 the
+ *                 largest diagonal word, else r11 > r22, else the last; a trace of exactly 0 takes the second test, a
+ *                 NaN trace ends in the last branch.
+ * A destination of quaternions may be a source of quaternions exactly (in place); any other overlap of a destination
+ * with a source, or a null pointer, writes nothing and sets arm_mi355x_last_error().  nbQuaternions == 0 writes
+ * nothing. */
+void arm_quaternion_norm_f32(const float32_t *pInputQuaternions, float32_t *pNorms, uint32_t nbQuaternions);
+void arm_quaternion_inverse_f32(const float32_t *pInputQuaternions, float32_t *pInverseQuaternions,
+                                uint32_t nbQuaternions);
+void arm_quaternion_conjugate_f32(const float32_t *pInputQuaternions, float32_t *pConjugateQuaternions,
+                                  uint32_t nbQuaternions);
+void arm_quaternion_normalize_f32(const float32_t *pInputQuaternions, float32_t *pNormalizedQuaternions,
+                                  uint32_t nbQuaternions);
+void arm_quaternion_product_single_f32(const float32_t *qa, const float32_t *qb, float32_t *qr);
+void arm_quaternion_product_f32(const float32_t *qa, const float32_t *qb, float32_t *qr, uint32_t nbQuaternions);
+void arm_quaternion2rotation_f32(const float32_t *pInputQuaternions, float32_t *pOutputRotations,
+                                 uint32_t nbQuaternions);
+void arm_rotation2quaternion_f32(const float32_t *pInputRotations, float32_t *pOutputQuaternions,
+                                 uint32_t nbQuaternions);
+
 #ifdef __cplusplus
 }
 #endif

@@ -661,6 +661,68 @@ arm_status arm_gaussian_naive_bayes_predict_f32_batch(const arm_gaussian_naive_b
                                                       const float32_t *d_in, float32_t *d_probabilities,
                                                       uint32_t *d_class, uint32_t nbItems, void *stream);
 
+/* Batched interpolation (arm_math.h: "Interpolation ...").  Device pointers, stream-ordered; every device table is read
+ * on `stream`, so a table written on that stream immediately before the call is seen.  S is host memory, its table
+ * pointer a device pointer.
+ * Linear: d_y[i] = arm_linear_interp_<t>(d_x[i]) for blockSize samples that share one table.  The table is staged in
+ * LDS where it fits 64 KiB (16384 f32 words; a fixed-point table is only read up to entry 2048) and read from global
+ * memory otherwise.
+ * Bilinear: d_out[i] = arm_bilinear_interp_<t>(S, d_X[i], d_Y[i]), four table reads per point from global memory.
+ * Spline, over `batch` independent items: arm_spline_init_f32_batch reads item i's n knots at d_x + i * xStride
+ * (xStride 0: one knot vector for every item, otherwise xStride >= n) and its values at d_y + i * n, and writes 3 (n -
+ * 1) words at d_coeffs + i * 3 (n - 1) (b, c, d) and 2 n - 1 words at d_temp + i * (2 n - 1) (u, z); one lane takes
+ * one item, whatever the batch.  arm_spline_f32_batch evaluates item i's blockSize queries at d_xq + i * xqStride
+ * (xqStride 0: one query vector for every item, otherwise xqStride >= blockSize) into d_dst + i * blockSize; one wave
+ * takes one item.
+ * ARM_MATH_ARGUMENT_ERROR, nothing written: a null pointer, nValues == 0, numRows * numCols >= 2^31, n < 2, a type other
+ * than ARM_SPLINE_NATURAL and ARM_SPLINE_PARABOLIC_RUNOUT, a stride below the item length, a result that overlaps a
+ * source or another result.  blockSize == 0 or batch == 0 is a successful no-op. */
+arm_status arm_linear_interp_f32_batch(const arm_linear_interp_instance_f32 *S, const float32_t *d_x, float32_t *d_y,
+                                       uint32_t blockSize, void *stream);
+arm_status arm_linear_interp_q31_batch(const q31_t *d_table, uint32_t nValues, const q31_t *d_x, q31_t *d_y,
+                                       uint32_t blockSize, void *stream);
+arm_status arm_linear_interp_q15_batch(const q15_t *d_table, uint32_t nValues, const q31_t *d_x, q15_t *d_y,
+                                       uint32_t blockSize, void *stream);
+arm_status arm_linear_interp_q7_batch(const q7_t *d_table, uint32_t nValues, const q31_t *d_x, q7_t *d_y,
+                                      uint32_t blockSize, void *stream);
+arm_status arm_bilinear_interp_f32_batch(const arm_bilinear_interp_instance_f32 *S, const float32_t *d_X,
+                                         const float32_t *d_Y, float32_t *d_out, uint32_t blockSize, void *stream);
+arm_status arm_bilinear_interp_q31_batch(const arm_bilinear_interp_instance_q31 *S, const q31_t *d_X, const q31_t *d_Y,
+                                         q31_t *d_out, uint32_t blockSize, void *stream);
+arm_status arm_bilinear_interp_q15_batch(const arm_bilinear_interp_instance_q15 *S, const q31_t *d_X, const q31_t *d_Y,
+                                         q15_t *d_out, uint32_t blockSize, void *stream);
+arm_status arm_bilinear_interp_q7_batch(const arm_bilinear_interp_instance_q7 *S, const q31_t *d_X, const q31_t *d_Y,
+                                        q7_t *d_out, uint32_t blockSize, void *stream);
+arm_status arm_spline_init_f32_batch(arm_spline_type type, const float32_t *d_x, uint32_t xStride,
+                                     const float32_t *d_y, uint32_t n, float32_t *d_coeffs, float32_t *d_temp,
+                                     uint32_t batch, void *stream);
+arm_status arm_spline_f32_batch(const float32_t *d_x, uint32_t xStride, const float32_t *d_y,
+                                const float32_t *d_coeffs, uint32_t n, const float32_t *d_xq, uint32_t xqStride,
+                                float32_t *d_dst, uint32_t blockSize, uint32_t batch, void *stream);
+
+/* Batched quaternion functions (arm_math.h: "The quaternion functions ...").  Device pointers, stream-ordered; the
+ * arrays are read and written on `stream`, so a source written on that stream immediately before the call is seen.
+ * One lane takes one quaternion: a 16-byte access where the array is 16-byte aligned, four words otherwise.  The
+ * 36-byte rotations pass through LDS so that a wave's global accesses are 64 consecutive words.
+ * arm_quaternion_product_f32_batch: bStride (words) is 4, or 0 to multiply every d_qa[i] by the one quaternion at d_qb.
+ * ARM_MATH_ARGUMENT_ERROR, nothing written: a null pointer, a bStride other than 0 and 4, a result that overlaps a
+ * source (a result of quaternions may be a source of quaternions exactly).  nbQuaternions == 0 is a successful
+ * no-op. */
+arm_status arm_quaternion_norm_f32_batch(const float32_t *d_src, float32_t *d_dst, uint32_t nbQuaternions,
+                                         void *stream);
+arm_status arm_quaternion_inverse_f32_batch(const float32_t *d_src, float32_t *d_dst, uint32_t nbQuaternions,
+                                            void *stream);
+arm_status arm_quaternion_conjugate_f32_batch(const float32_t *d_src, float32_t *d_dst, uint32_t nbQuaternions,
+                                              void *stream);
+arm_status arm_quaternion_normalize_f32_batch(const float32_t *d_src, float32_t *d_dst, uint32_t nbQuaternions,
+                                              void *stream);
+arm_status arm_quaternion_product_f32_batch(const float32_t *d_qa, const float32_t *d_qb, uint32_t bStride,
+                                            float32_t *d_qr, uint32_t nbQuaternions, void *stream);
+arm_status arm_quaternion2rotation_f32_batch(const float32_t *d_src, float32_t *d_dst, uint32_t nbQuaternions,
+                                             void *stream);
+arm_status arm_rotation2quaternion_f32_batch(const float32_t *d_src, float32_t *d_dst, uint32_t nbQuaternions,
+                                             void *stream);
+
 /* Multi-GPU complex FFT (SURVEY §8b "a multi-GPU entry point"; per item: arm_cfft_f32 /
  * _q31 / _q15, transform_functions.h:456-460).  Shard s of `nshards` is batch[s] contiguous
  * transforms at DEVICE pointer d_p1[s] on HIP device devices[s] (a device may appear in
